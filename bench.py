@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- edges aggregated/sec (GCN fwd+bwd) on coarsened subgraphs (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-products] [--layer GCNConv] [--shard K/N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-products] [--layer GCNConv] [--shard K/N] [--dump-outputs DIR]
 
 Workload (config.workload), default S-products = BASELINE.json configs[3], the north_star target: "ogbn-products
 use_community_detection, subgraph-batch DP" on synthetic data of that shape: one community graph of
@@ -106,12 +106,56 @@ def parse_args():
                          "(the collective's launch path; no peer).  tools/shard_curve.py runs N = 1, 2, 4, 8 and fits the model of DESIGN 5")
     ap.add_argument("--spectral", default="device", choices=["device", "arpack"],
                     help="spectral prelude of the contraction (not timed): thick-restart Lanczos on the GPU, or ARPACK on the host")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (f32 / f64, at most 64 MB in "
+                         "all): the loss, the updated parameters and Adam's moments.  The inputs depend on the arguments only, so two "
+                         "builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = DEFAULT_STEPS[args.workload][0]
     if args.warmup is None:
         args.warmup = DEFAULT_STEPS[args.workload][1]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
+
+
+DUMP_BYTES = 63 << 20   # data of the --dump-outputs files (+ their .npy headers: under 64 MB in all)
+
+
+def step_outputs(model, opt, loss):
+    """What a caller of the timed step holds after it: the loss it returned, the model's updated parameters and the optimiser's
+    moments (exp_avg carries the step's gradients; the Adam update itself is nearly g / |g| and hides their errors)."""
+    import numpy as np
+
+    out = {"loss": loss.detach().reshape(1).cpu().numpy()}
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    for n, p in named:
+        out["param." + n] = p.detach().cpu().numpy()
+    state = opt.state_dict()["state"]
+    for i, (n, _) in enumerate(named):
+        if i in state:
+            for k in ("exp_avg", "exp_avg_sq"):
+                out[f"adam_{k}.{n}"] = state[i][k].detach().cpu().numpy()
+    return {k: np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in out.items()}
+
+
+def write_outputs(path, arrays, limit=DUMP_BYTES):
+    """arrays -> path/<name>.npy.  Over `limit` bytes in all, every array is cut to the same fraction of its entries: a fixed sample
+    (seeded by the array's name, ascending flat positions), so that two runs write the same positions."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, limit / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def spawn_ranks(n):
@@ -439,6 +483,8 @@ def main():
     if world > 1 or emu is not None:
         trainer.comm_events = []
     dt, loss = timed(trainer, args.steps, args.warmup, step_events)
+    if args.dump_outputs and rank == 0:   # before the profiled steps below move the weights on
+        write_outputs(args.dump_outputs, step_outputs(trainer.model, trainer.opt, loss))
     loss_final = float(loss)
     if world > 1:   # every rank's share of the last timed step's loss (they add up to `loss`)
         share = trainer.local_loss.detach().to(torch.float64).view(1)
@@ -746,6 +792,8 @@ def bench_qm9(args, device, world, rank, backend):
         loss = tr.step()
     barrier()
     dt = torch.tensor([time.perf_counter() - t_start], device=device, dtype=torch.float64)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(model, tr.opt, loss))
     tot = torch.tensor([float(nnz), float(rows)], device=device, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(dt, op=torch.distributed.ReduceOp.MAX)

@@ -1,9 +1,8 @@
 """CLI surface of fit-gnn_amd/main.py vs the reference's main.py (flags, defaults, arg_correction), the Planetoid
-raw-file loader (CPU tier; reference files are read only when /root/reference is present), and an end-to-end
-GPU run of both the baseline and the FIT-GNN path on a synthetic Cora-shaped dataset."""
-import ast
+raw-file loader (CPU tier; the reference's flag table and its copy of Cora's raw files are stored under tests/golden),
+and an end-to-end GPU run of both the baseline and the FIT-GNN path on a synthetic Cora-shaped dataset."""
+import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,8 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "fit-gnn_amd"))
 import main as cli  # noqa: E402
 
-REF_MAIN = "/root/reference/main.py"
-REF_CORA = "/root/reference/Baselines/SGGC/APPNP/dataset/cora/raw"
+# the reference's parser.add_argument lines as data (tests/golden/make_cli_golden.py) and the Planetoid raw files of Cora it ships
+REF_FLAGS = os.path.join(ROOT, "tests", "golden", "cli_flags.json")
+REF_CORA = os.path.join(ROOT, "tests", "golden", "cora_raw")
+
+
+def _reference_flags(script):
+    with open(REF_FLAGS) as f:
+        return json.load(f)[script]
 
 
 def test_arg_correction_rules():
@@ -30,16 +35,8 @@ def test_arg_correction_rules():
     assert a.experiment == "random"                                # main.py:122-124
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference not mounted")
 def test_flags_and_defaults_match_reference_main_py():
-    src = open(REF_MAIN).read()
-    ref = {}
-    for m in re.finditer(r"parser\.add_argument\((.*)\)", src):
-        call = ast.parse("f(" + m.group(1).split("#")[0].rstrip().rstrip(")") + ")").body[0].value
-        name = call.args[0].value
-        kw = {k.arg: k.value for k in call.keywords}
-        default = ast.literal_eval(kw["default"]) if "default" in kw else (False if "action" in kw else None)
-        ref[name] = (default, "action" in kw, "required" in kw)
+    ref = {name: (e["default"], e["flag"], e["required"]) for name, e in _reference_flags("main.py").items()}
     assert len(ref) == 33
     mine = {a.option_strings[0]: a for a in cli.build_parser()._actions if a.option_strings and a.option_strings[0] != "-h"}
     for name, (default, is_flag, required) in ref.items():
@@ -49,24 +46,16 @@ def test_flags_and_defaults_match_reference_main_py():
         assert mine[name].required == required, name
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/inference.py"), reason="reference not mounted")
 def test_inference_flags_and_defaults_match_reference():
     import inference as icli
 
-    src = open("/root/reference/inference.py").read()
-    ref = {}
-    for m in re.finditer(r"parser\.add_argument\((.*)\)", src):
-        call = ast.parse("f(" + m.group(1).split("#")[0].rstrip().rstrip(")") + ")").body[0].value
-        kw = {k.arg: k.value for k in call.keywords}
-        ref[call.args[0].value] = (ast.literal_eval(kw["default"]) if "default" in kw else (False if "action" in kw else None),
-                                   "action" in kw)
+    ref = {name: (e["default"], e["flag"]) for name, e in _reference_flags("inference.py").items()}
     assert len(ref) == 33
     mine = {a.option_strings[0]: a for a in icli.build_parser()._actions if a.option_strings and a.option_strings[0] != "-h"}
     for name, (default, is_flag) in ref.items():
         assert name in mine and mine[name].default == default and (mine[name].nargs == 0) == is_flag, name
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CORA), reason="reference not mounted")
 def test_planetoid_loader_on_reference_cora_files():
     from fitgnn_amd import pipeline
 
