@@ -143,6 +143,19 @@ SIGNATURES = {
     "fitgnn_compose_levels": (ctypes.c_int, [c_i32, ptr, ptr, ptr, ptr, ptr]),
     "fitgnn_lift_adjacency_workspace_bytes": (c_size, [c_i32, c_i64, c_i32]),
     "fitgnn_lift_adjacency": (ctypes.c_int, [c_i32, ptr, ptr, ptr, ptr, ptr, c_i32, ptr, ptr, ptr, ptr, ptr, c_size, ptr]),
+    "fitgnn_edge_list": (ctypes.c_int, [ptr, ptr, ptr, c_i32, ptr, ptr, ptr, ptr, c_i64, ptr, ptr]),
+    "fitgnn_heavy_edge_proximity_workspace_bytes": (c_size, [c_i32]),
+    "fitgnn_heavy_edge_proximity": (ctypes.c_int, [ptr, ptr, ptr, c_i32, ptr, ptr, ptr, c_i64, ptr, ptr, c_size, ptr]),
+    "fitgnn_jc_proximity": (ctypes.c_int, [ptr, ptr, c_i64, ptr, c_i32, c_i64, ptr, ptr]),
+    "fitgnn_affinity_proximity_workspace_bytes": (c_size, [c_i32, c_i64]),
+    "fitgnn_affinity_proximity": (ctypes.c_int, [c_i32, ptr, ptr, c_i64, ptr, c_i32, c_i64, ptr, ptr, c_size, ptr]),
+    "fitgnn_edge_variation_costs_f64": (ctypes.c_int, [ptr, ptr, c_i64, ptr, ptr, c_i32, c_i64, ptr, ptr]),
+    "fitgnn_jacobi_vectors_workspace_bytes": (c_size, [c_i32, c_i32]),
+    "fitgnn_jacobi_vectors_f64": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i32, ptr, c_i32, c_i32, ptr, ptr, c_size, ptr]),
+    "fitgnn_gauss_seidel_vectors_f64": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i32, c_i32, ptr, ptr, c_i32, ptr, ptr]),
+    "fitgnn_greedy_matching_workspace_bytes": (c_size, [c_i32, c_i64, c_i32]),
+    "fitgnn_greedy_matching": (ctypes.c_int, [ptr, ptr, ptr, c_i32, ptr, ptr, ptr, c_i64, ptr, c_i32, ptr, ptr, c_i64, ptr, ptr, ptr,
+                                              ptr, ptr, ptr, c_size, ptr]),
     "fitgnn_pool_rows_workspace_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_pool_rows_f32": (ctypes.c_int, [ptr, ptr, c_i32, c_i32, ptr, c_i64, c_i32, ptr, c_i64, ptr, ptr, c_size, ptr]),
 }

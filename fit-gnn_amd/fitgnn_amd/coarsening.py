@@ -1,7 +1,7 @@
 """`coarsen()` with the reference's signature and return values, contraction step on the MI355X.
 
-Mirror of graph_coarsening/coarsening_utils.py:18-182 (`coarsen`) for the variation_neighborhoods
-method, the only one BASELINE.json's north_star names.  Per level:
+Mirror of graph_coarsening/coarsening_utils.py:18-182 (`coarsen`).  variation_neighborhoods (the method
+BASELINE.json's north_star names), per level:
 
     host   spectral prelude  A = Uk diag(lk^-1/2)            (:75-96;  ARPACK / LAPACK)
            or               A = B diag(d^-1/2) V             (:99-105)
@@ -9,6 +9,17 @@ method, the only one BASELINE.json's north_star names.  Per level:
     device greedy disjoint selection with re-costing         (:604-650)             fitgnn_greedy_select
     device assignment vector / C values                      (:212-254, :168-179)   fitgnn_build_assignment
     device adjacency lift Wc = zero_diag(P^T W P) symmetrised (:138-139, :201-205)   fitgnn_lift_adjacency
+
+The matching-based methods heavy_edge, algebraic_JC, affinity_GS and variation_edges (:115-127, :483-527,
+:658-848, :931-993) run per level:
+
+    host   test vectors X0 = randn(N, K)/sqrt(N) (JC, GS: the reference's draw, same place and order)
+           or spectral prelude as above (variation_edges)
+    device edge list tril(W) in row-major order                                           fitgnn_edge_list
+    device test-vector smoothing (20 Jacobi steps / one Gauss-Seidel sweep)    fitgnn_jacobi_vectors_f64 / _gauss_seidel_
+    device per-edge proximity (f32) or variation cost (f64)                           fitgnn_*_proximity / _edge_variation_
+    device greedy matching, stable rank (-weight, edge id), truncated as :983-985     fitgnn_greedy_matching
+    device assignment / lift as above
 
 Returned objects expose what FIT-GNN's callers touch (utils.py:159-184, :723-752, main.py:144-151):
 `C` is a scipy csc matrix (subclass whose `.dot(dense)` runs the pooling kernel), `Gc` a light graph with
@@ -288,6 +299,188 @@ def lift_adjacency(res):
     return sp.csr_matrix((wc[:m].cpu().numpy(), cc[:m].cpu().numpy(), rp.cpu().numpy()), shape=(res.n, res.n))
 
 
+# ---------------------------------------------------------------------------------------------
+# matching-based methods (coarsening_utils.py:115-127, :483-527, :658-848, :931-993)
+# ---------------------------------------------------------------------------------------------
+MATCHING_METHODS = ("heavy_edge", "algebraic_JC", "affinity_GS", "variation_edges")
+RANDOM_METHODS = ("algebraic_JC", "affinity_GS")          # draw np.random.randn test vectors at every level
+SUPPORTED_METHODS = ("variation_neighborhoods",) + MATCHING_METHODS
+
+
+def check_method(method, algorithm="greedy"):
+    """Refuse what coarsen() does not implement (no silent fall-back to another method)."""
+    if "variation_neighborhood" in method:
+        return
+    if method not in MATCHING_METHODS:
+        raise NotImplementedError(f"coarsening method '{method}' is not supported; supported: {', '.join(SUPPORTED_METHODS)}")
+    if algorithm != "greedy":
+        raise NotImplementedError(f"algorithm '{algorithm}' is not supported for '{method}' (greedy matching only)")
+
+
+def match_keep(N, r):
+    """Matches matching_greedy (:983-985) takes before it stops: n = N - k <= (1 - r) N in float64, at least one."""
+    n_target = (1 - r) * N
+    k = max(1, int(np.ceil(N - n_target)))
+    while k > 1 and N - (k - 1) <= n_target:
+        k -= 1
+    while N - k > n_target:
+        k += 1
+    return k
+
+
+class EdgeList:
+    """tril(W) in row-major order on the device (the reference's get_edge_list() numbering): src > dst per edge."""
+    __slots__ = ("N", "M", "rowptr", "col", "w", "dw", "edge_off", "src", "dst", "ew", "csr_eid", "device")
+
+    def __init__(self, G, device="cuda"):
+        L = _lib.lib()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.FitgnnError("the matching methods run on the MI355X (no CPU fallback)")
+        W = G.W
+        if W.diagonal().any():
+            raise ValueError("the matching methods need a graph without self-loops (the reference would match (i, i))")
+        self.N, self.M, self.device = G.N, int(sp.tril(W, -1).nnz), dev
+        self.rowptr, self.col = _dev(W.indptr, torch.int32, dev), _dev(W.indices, torch.int32, dev)
+        self.w, self.dw = _dev(W.data, torch.float64, dev), _dev(G.dw, torch.float64, dev)
+        m = max(self.M, 1)
+        self.edge_off = torch.empty(self.N + 1, dtype=torch.int32, device=dev)
+        self.src, self.dst = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
+        self.ew = torch.empty(m, dtype=torch.float64, device=dev)
+        self.csr_eid = torch.empty(max(int(W.nnz), 1), dtype=torch.int32, device=dev)
+        _lib.check(L.fitgnn_edge_list(_lib.dptr(self.rowptr), _lib.dptr(self.col), _lib.dptr(self.w), self.N, _lib.dptr(self.edge_off),
+                                      _lib.dptr(self.src), _lib.dptr(self.dst), _lib.dptr(self.ew), self.M, _lib.dptr(self.csr_eid),
+                                      _lib.stream_ptr(dev)), "edge_list")
+
+
+def test_vectors(el, method, X0):
+    """generate_test_vectors (:813-848) from the host draw X0 [N x K]: 20 Jacobi steps (algebraic_JC) or one Gauss-Seidel
+    sweep (affinity_GS).  Returns a device f64 [N x K] tensor."""
+    L = _lib.lib()
+    dev, N = el.device, el.N
+    X0 = np.ascontiguousarray(X0, dtype=np.float64)
+    K = int(X0.shape[1])
+    if not (1 <= K <= _lib.MAX_K):
+        raise _lib.FitgnnError(f"K={K} outside [1,{_lib.MAX_K}]")
+    X0d = _dev(X0, torch.float64, dev)
+    X = torch.empty_like(X0d)
+    st = _lib.stream_ptr(dev)
+    if method == "algebraic_JC":
+        wb = int(L.fitgnn_jacobi_vectors_workspace_bytes(N, K))
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        _lib.check(L.fitgnn_jacobi_vectors_f64(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), _lib.dptr(el.dw), N, _lib.dptr(X0d),
+                                               K, 20, _lib.dptr(X), _lib.dptr(work), wb, st), "jacobi_vectors")
+    elif method == "affinity_GS":
+        comp_off = torch.tensor([0, N], dtype=torch.int32, device=dev)
+        _lib.check(L.fitgnn_gauss_seidel_vectors_f64(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), _lib.dptr(el.dw), N, 1,
+                                                     _lib.dptr(comp_off), _lib.dptr(X0d), K, _lib.dptr(X), st), "gauss_seidel_vectors")
+    else:
+        raise ValueError(method)
+    return X
+
+
+def proximity(el, method, X=None):
+    """get_proximity_measure (:658-730) for heavy_edge / algebraic_JC / affinity_GS: device float32 [M].  X: the device test
+    vectors of test_vectors() (JC, GS)."""
+    L = _lib.lib()
+    dev, st = el.device, _lib.stream_ptr(el.device)
+    prox = torch.empty(max(el.M, 1), dtype=torch.float32, device=dev)
+    if method == "heavy_edge":
+        wb = int(L.fitgnn_heavy_edge_proximity_workspace_bytes(el.N))
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        _lib.check(L.fitgnn_heavy_edge_proximity(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), el.N, _lib.dptr(el.src),
+                                                 _lib.dptr(el.dst), _lib.dptr(el.ew), el.M, _lib.dptr(prox), _lib.dptr(work), wb, st),
+                   "heavy_edge_proximity")
+    elif method == "algebraic_JC":
+        K = int(X.shape[1])
+        _lib.check(L.fitgnn_jc_proximity(_lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(X), K, K, _lib.dptr(prox), st), "jc_proximity")
+    elif method == "affinity_GS":
+        K = int(X.shape[1])
+        wb = int(L.fitgnn_affinity_proximity_workspace_bytes(el.N, el.M))
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        _lib.check(L.fitgnn_affinity_proximity(el.N, _lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(X), K, K, _lib.dptr(prox),
+                                               _lib.dptr(work), wb, st), "affinity_proximity")
+    else:
+        raise ValueError(method)
+    return prox[: el.M]
+
+
+def edge_costs(el, A):
+    """variation_edges' per-edge cost (:495-514) from the level's spectral matrix A (host [N x K], or a device f64 tensor)."""
+    L = _lib.lib()
+    if not torch.is_tensor(A) and np.iscomplexobj(A):
+        # np.linalg.eig at later levels can return a complex basis (:98-104); the reference's Frobenius norm then sums squared
+        # moduli: the cost of the real part plus the cost of the imaginary part
+        return edge_costs(el, np.ascontiguousarray(A.real)) + edge_costs(el, np.ascontiguousarray(A.imag))
+    Ad = A if torch.is_tensor(A) else _dev(A, torch.float64, el.device)
+    K = int(Ad.shape[1])
+    if not (1 <= K <= _lib.MAX_K):
+        raise _lib.FitgnnError(f"K={K} outside [1,{_lib.MAX_K}]")
+    cost = torch.empty(max(el.M, 1), dtype=torch.float64, device=el.device)
+    _lib.check(L.fitgnn_edge_variation_costs_f64(_lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(el.dw), _lib.dptr(Ad), K, K,
+                                                 _lib.dptr(cost), _lib.stream_ptr(el.device)), "edge_variation_costs")
+    return cost[: el.M]
+
+
+class MatchLevelResult(LevelResult):
+    __slots__ = ("rounds", "weight", "comp_taken")
+
+
+def greedy_matching(el, weight, k_keep, comp_off=None, min_gain=0):
+    """matching_greedy (:931-993) on the device under the stable order (-weight, edge id): the first k_keep[c] edges of the
+    full greedy matching of every component c (node ranges comp_off, default: one component), contracted by
+    fitgnn_build_assignment; components that would keep <= min_gain pairs keep none (comp_taken counts before that filter).
+    weight: device tensor [M] (f32 proximities or f64).  Returns MatchLevelResult."""
+    L = _lib.lib()
+    dev, N, st = el.device, el.N, _lib.stream_ptr(el.device)
+    comp_off = np.array([0, N]) if comp_off is None else np.asarray(comp_off)
+    n_comp = len(comp_off) - 1
+    k_keep = np.broadcast_to(np.asarray(k_keep, dtype=np.int64), (n_comp,))
+    wd = weight.to(torch.float64).contiguous()
+    co_d, k_d = _dev(comp_off, torch.int32, dev), _dev(k_keep, torch.int64, dev)   # named: they must outlive the call
+    wb = int(L.fitgnn_greedy_matching_workspace_bytes(N, el.M, n_comp))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    sel_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    sel_mem = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
+    taken = torch.zeros(max(n_comp, 1), dtype=torch.int32, device=dev)
+    rounds = _lib.c_i32(0)
+    _lib.check(L.fitgnn_greedy_matching(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.csr_eid), N, _lib.dptr(el.edge_off),
+                                        _lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(wd), n_comp, _lib.dptr(co_d), _lib.dptr(k_d),
+                                        int(min_gain), _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(taken),
+                                        _lib.ctypes.byref(rounds), _lib.dptr(work), wb, st), "greedy_matching")
+    assign = torch.empty(N, dtype=torch.int32, device=dev)
+    cval = torch.empty(N, dtype=torch.float64, device=dev)
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
+    work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
+    _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
+                                         _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
+    res = MatchLevelResult()
+    res.N, res.n, res.assign, res.cval, res.device = N, int(n_out.item()), assign, cval, dev
+    res.rowptr, res.col, res.w = el.rowptr, el.col, el.w
+    res.cost0, res.rounds, res.weight = None, int(rounds.value), weight
+    cnt = sel_count.cpu().numpy()
+    res.sel_off = sel_off[: cnt[0] + 1].cpu().numpy()
+    res.sel_mem = sel_mem[: cnt[1]].cpu().numpy()
+    res.comp_taken = taken[:n_comp].cpu().numpy()
+    return res
+
+
+def contract_matching(G, method, r_cur, K=10, A=None, device="cuda"):
+    """One level of a matching method (:106-127): weights, greedy matching truncated at r_cur, assignment.  JC / GS draw
+    their test vectors from np.random here, as get_proximity_measure does.  A: the level's spectral matrix (variation_edges)."""
+    el = EdgeList(G, device=device)
+    if method == "variation_edges":
+        weight = -edge_costs(el, A)                       # matching_greedy(G, weights=-weights) (:522-524)
+    else:
+        X = None
+        if method in RANDOM_METHODS:
+            X = test_vectors(el, method, np.random.randn(G.N, K) / np.sqrt(G.N))   # generate_test_vectors (:816)
+        weight = proximity(el, method, X)
+    return greedy_matching(el, weight, match_keep(G.N, r_cur))
+
+
 def pool_rows(assign, cval, n, X, want_f64=False):
     """Xc = C . X on the device.  assign int32[N], cval float64[N] device tensors; X float32 [N,F] device."""
     L = _lib.lib()
@@ -350,9 +543,12 @@ class CoarseningMatrix(sp.csc_matrix):
 def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algorithm="greedy", Uk=None, lk=None,
             max_level_r=0.99, device="cuda", spectral="arpack"):
     """Same contract as graph_coarsening.coarsening_utils.coarsen (coarsening_utils.py:18-182) for
-    method in {'variation_neighborhood', 'variation_neighborhoods'}: returns (C, Gc, mapping_dict_list)."""
-    if "variation_neighborhood" not in method:
-        raise NotImplementedError(f"method '{method}' is outside the accelerated hot path (variation_neighborhoods only)")
+    method in {'variation_neighborhood', 'variation_neighborhoods', 'heavy_edge', 'algebraic_JC', 'affinity_GS',
+    'variation_edges'} (the matching methods with algorithm='greedy'): returns (C, Gc, mapping_dict_list).
+    The matching methods break ties by edge index; algebraic_JC / affinity_GS draw from np.random exactly
+    where the reference does, so a caller who seeds numpy gets the reference's test vectors."""
+    check_method(method, algorithm)
+    matching = method in MATCHING_METHODS
     if not hasattr(G, "W"):
         raise TypeError("G must expose .W (scipy sparse adjacency) and .N")
     if not isinstance(G, Graph):
@@ -370,14 +566,19 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
     for level in range(1, max_levels + 1):
         G = Gc
         r_cur = np.clip(1 - n_target / n, 0.0, max_level_r)
-        if level == 1:
-            if spectral == "device" and Uk is None and G.N > 4 * K:  # extension: the eigensolve on the MI355X
-                lk, Uk = lanczos_smallest(G.L, K, device=dev)
-            B = _spectral_level1(G, K, Uk, lk)
-            A = B
+        A = None
+        if "variation" in method:
+            if level == 1:
+                if spectral == "device" and Uk is None and G.N > 4 * K:  # extension: the eigensolve on the MI355X
+                    lk, Uk = lanczos_smallest(G.L, K, device=dev)
+                B = _spectral_level1(G, K, Uk, lk)
+                A = B
+            else:
+                B, A = _spectral_next(G, iC, B)
+        if matching:
+            res = contract_matching(G, method, r_cur, K=K, A=A, device=dev)
         else:
-            B, A = _spectral_next(G, iC, B)
-        res = contract_level(G, A, r_cur, device=dev)
+            res = contract_level(G, A, r_cur, device=dev)
         assign_h = res.assign.cpu().numpy()
         iC = sp.csc_matrix((res.cval.cpu().numpy(), (assign_h, np.arange(G.N))), shape=(res.n, G.N))
         if iC.shape[1] - iC.shape[0] <= 2:  # :131-135 avoid too many levels for so few nodes
@@ -391,10 +592,13 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
             coords = (iC.power(2)).dot(G.coords)  # coarsen_vector :190-191 (plot coordinates only)
         Gc = Graph(Wc, coords=coords)
         n = Gc.N
-        # level mapping :168-179: keys 0..N-1 of the ORIGINAL graph, identity-padded past the level's size
-        md = {i: int(assign_h[i]) for i in range(G.N)}
-        for i in range(G.N, N):
-            md[i] = res.n + (i - G.N)
+        if matching:
+            md = {i: i for i in range(N)}  # :168: the matching methods keep the identity dict at every level
+        else:
+            # level mapping :168-179: keys 0..N-1 of the ORIGINAL graph, identity-padded past the level's size
+            md = {i: int(assign_h[i]) for i in range(G.N)}
+            for i in range(G.N, N):
+                md[i] = res.n + (i - G.N)
         mapping_dict_list.append(md)
         if n <= n_target:
             break
@@ -470,7 +674,8 @@ def _dense_prelude_batch(W, off, comps, K, A, Kc):
         Kc[ids] = k
 
 
-def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=0.99, device="cuda", spectral="arpack"):
+def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=0.99, device="cuda", spectral="arpack",
+                  method="variation_neighborhoods"):
     """coarsen() (coarsening_utils.py:18-182, method variation_neighborhoods) applied independently to every connected
     component of the block-diagonal adjacency W (scipy sparse [N x N]); component c = node range
     comp_off[c]:comp_off[c+1] and must be connected.  Per level ONE launch each of the family, cost, selection (one
@@ -478,7 +683,14 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
     when the reference's driver would (target reached :180, or a level that removes <= 2 nodes :131-135, which is not
     applied).  The spectral prelude stays on the host per component (level 1: ARPACK as the reference, or
     spectral='dense'; later levels: the K x K eigenproblem of :98-104).  A0: optional list of per-component level-1
-    matrices A (n_c x K_c), e.g. from injected (Uk, lk).  Returns BatchCoarsening."""
+    matrices A (n_c x K_c), e.g. from injected (Uk, lk).  method: also the deterministic matching methods heavy_edge and
+    variation_edges (one edge list, one proximity / cost launch and one matching over all components per level; the
+    matching is component-agnostic and truncated per component).  Returns BatchCoarsening."""
+    check_method(method)
+    if method in RANDOM_METHODS:
+        raise NotImplementedError(f"coarsen_batch: '{method}' draws random test vectors per component and level; use coarsen() "
+                                  "per component (the reference's draw order)")
+    matching = method in MATCHING_METHODS
     L = _lib.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -508,7 +720,9 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         N = G.N
         r_cur = np.clip(1 - n_target / np.maximum(n_cur, 1), 0.0, max_level_r)
         n_reduce = np.where(active, np.floor(r_cur * n_cur), 0).astype(np.int64)  # :612 per component
-        if level == 1:
+        if method == "heavy_edge":
+            pass                               # no spectral prelude
+        elif level == 1:
             Kc = np.where(size0 <= K, size0, K).astype(np.int32)  # eigsh(dense, k=K >= N) returns N pairs (:85-86)
             Kmax = int(max(K, Kc.max()))
             A = np.zeros((N, Kmax))
@@ -531,7 +745,7 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         else:
             B = iC.dot(B)                      # :97, all components at once (rows are independent)
             LB = G.L.dot(B)
-            A = np.zeros_like(B)
+            A = np.zeros(B.shape, dtype=complex if method == "variation_edges" else B.dtype)  # edge costs take |.|^2 of a complex A
             for c in np.nonzero(active)[0]:    # :98-104, K x K per component
                 b, e, k = int(off[c]), int(off[c + 1]), int(node_K_comp[c])
                 Bc = B[b:e, :k]
@@ -540,44 +754,19 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
                 d[mask] = 1
                 dinvsqrt = d ** (-1 / 2)
                 dinvsqrt[mask] = 0
-                A[b:e, :k] = np.real(Bc @ np.diag(dinvsqrt) @ V)
-        node_K = np.repeat(node_K_comp, np.diff(off)).astype(np.int32)
-        # ---- device: family, costs, per-component selection, assignment ----
-        Wl = G.W
-        rowptr, col = _dev(Wl.indptr, torch.int32, dev), _dev(Wl.indices, torch.int32, dev)
-        w, dw = _dev(Wl.data, torch.float64, dev), _dev(G.dw, torch.float64, dev)
-        Ad, nK = _dev(A, torch.float64, dev), _dev(node_K, torch.int32, dev)
-        lda = int(A.shape[1])
-        nnz = int(Wl.nnz)
-        set_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        set_mem = torch.empty(nnz + N, dtype=torch.int32, device=dev)
-        _lib.check(L.fitgnn_closed_neighbourhoods(_lib.dptr(rowptr), _lib.dptr(col), N, _lib.dptr(set_off), _lib.dptr(set_mem), st),
-                   "closed_neighbourhoods")
-        set_len = (set_off[1:] - set_off[:-1]).contiguous()
-        cost0 = torch.empty(N, dtype=torch.float64, device=dev)
-        _lib.check(L.fitgnn_variation_costs_batch_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad),
-                                                      lda, lda, _lib.dptr(nK), _lib.dptr(set_off), _lib.dptr(set_len),
-                                                      _lib.dptr(set_mem), N, _lib.dptr(cost0), st), "variation_costs_batch")
-        wb = int(L.fitgnn_greedy_select_batch_workspace_bytes(N, nnz + N, n_comp))
-        work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        sel_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        sel_mem = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
-        sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
-        gain_d = torch.zeros(n_comp, dtype=torch.int64, device=dev)
-        off_d, n_reduce_d = _dev(off, torch.int32, dev), _dev(n_reduce, torch.int64, dev)  # named: they must outlive the call
-        _lib.check(L.fitgnn_greedy_select_batch(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad), lda,
-                                                lda, N, _lib.dptr(set_off), _lib.dptr(set_mem), _lib.dptr(cost0), n_comp,
-                                                _lib.dptr(off_d), _lib.dptr(n_reduce_d),
-                                                2, _lib.dptr(nK), _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count),
-                                                _lib.dptr(gain_d), _lib.dptr(work), wb, st), "greedy_select_batch")
-        assign = torch.empty(N, dtype=torch.int32, device=dev)
-        cval = torch.empty(N, dtype=torch.float64, device=dev)
-        n_out = torch.zeros(1, dtype=torch.int32, device=dev)
-        wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
-        work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
-        _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
-                                             _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
-        gain = gain_d.cpu().numpy()
+                Ac = Bc @ np.diag(dinvsqrt) @ V
+                A[b:e, :k] = Ac if np.iscomplexobj(A) else np.real(Ac)
+        if matching:
+            # ---- device: edge list, proximity / cost, one matching over all components, assignment ----
+            el = EdgeList(G, device=dev)
+            weight = -edge_costs(el, A) if method == "variation_edges" else proximity(el, method)
+            k_keep = [match_keep(int(n_cur[c]), r_cur[c]) if active[c] else 0 for c in range(n_comp)]
+            mres = greedy_matching(el, weight, k_keep, comp_off=off, min_gain=2)
+            assign, cval, n_out_h = mres.assign, mres.cval, mres.n
+            gain = mres.comp_taken.astype(np.int64)
+            rowptr, col, w = el.rowptr, el.col, el.w
+        else:
+            assign, cval, gain, n_out_h, rowptr, col, w = _select_level_batch(G, A, node_K_comp, off, n_comp, n_reduce, dev, st)
         applied = active & (gain > 2)          # :131-135: a level removing <= 2 nodes is not applied and ends the loop
         levels[applied] += 1
         active = applied.copy()
@@ -586,7 +775,7 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         _lib.check(L.fitgnn_compose_levels(N0, _lib.dptr(assign), _lib.dptr(cval), _lib.dptr(assign_tot), _lib.dptr(cval_tot), st),
                    "compose_levels")
         res = LevelResult()
-        res.N, res.n, res.assign, res.cval, res.device = N, int(n_out.item()), assign, cval, dev
+        res.N, res.n, res.assign, res.cval, res.device = N, n_out_h, assign, cval, dev
         res.rowptr, res.col, res.w = rowptr, col, w
         Wc = lift_adjacency(res)
         assign_h = assign.cpu().numpy()
@@ -594,7 +783,7 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         n_cur = np.where(applied, n_cur - gain, n_cur)
         new_off = np.zeros(n_comp + 1, dtype=np.int64)
         np.cumsum(n_cur, out=new_off[1:])
-        assert int(new_off[-1]) == res.n, (level, int(new_off[-1]), res.n, gain.tolist(), n_reduce.tolist(), sel_count.cpu().tolist())
+        assert int(new_off[-1]) == res.n, (level, int(new_off[-1]), res.n, gain.tolist(), n_reduce.tolist())
         off = new_off
         G = Graph(Wc)
         active &= n_cur > n_target             # :180
@@ -605,3 +794,47 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
     out.n_clusters = int(off[-1])
     out._dev = (assign_tot, cval_tot)
     return out
+
+
+def _select_level_batch(G, A, node_K_comp, off, n_comp, n_reduce, dev, st):
+    """coarsen_batch's variation_neighborhoods level on the device: family, costs, per-component selection, assignment.
+    Returns (assign, cval, gain, n_out, rowptr, col, w)."""
+    L = _lib.lib()
+    N = G.N
+    node_K = np.repeat(node_K_comp, np.diff(off)).astype(np.int32)
+    # ---- device: family, costs, per-component selection, assignment ----
+    Wl = G.W
+    rowptr, col = _dev(Wl.indptr, torch.int32, dev), _dev(Wl.indices, torch.int32, dev)
+    w, dw = _dev(Wl.data, torch.float64, dev), _dev(G.dw, torch.float64, dev)
+    Ad, nK = _dev(A, torch.float64, dev), _dev(node_K, torch.int32, dev)
+    lda = int(A.shape[1])
+    nnz = int(Wl.nnz)
+    set_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    set_mem = torch.empty(nnz + N, dtype=torch.int32, device=dev)
+    _lib.check(L.fitgnn_closed_neighbourhoods(_lib.dptr(rowptr), _lib.dptr(col), N, _lib.dptr(set_off), _lib.dptr(set_mem), st),
+               "closed_neighbourhoods")
+    set_len = (set_off[1:] - set_off[:-1]).contiguous()
+    cost0 = torch.empty(N, dtype=torch.float64, device=dev)
+    _lib.check(L.fitgnn_variation_costs_batch_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad),
+                                                  lda, lda, _lib.dptr(nK), _lib.dptr(set_off), _lib.dptr(set_len),
+                                                  _lib.dptr(set_mem), N, _lib.dptr(cost0), st), "variation_costs_batch")
+    wb = int(L.fitgnn_greedy_select_batch_workspace_bytes(N, nnz + N, n_comp))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    sel_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    sel_mem = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
+    gain_d = torch.zeros(n_comp, dtype=torch.int64, device=dev)
+    off_d, n_reduce_d = _dev(off, torch.int32, dev), _dev(n_reduce, torch.int64, dev)  # named: they must outlive the call
+    _lib.check(L.fitgnn_greedy_select_batch(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad), lda,
+                                            lda, N, _lib.dptr(set_off), _lib.dptr(set_mem), _lib.dptr(cost0), n_comp,
+                                            _lib.dptr(off_d), _lib.dptr(n_reduce_d),
+                                            2, _lib.dptr(nK), _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count),
+                                            _lib.dptr(gain_d), _lib.dptr(work), wb, st), "greedy_select_batch")
+    assign = torch.empty(N, dtype=torch.int32, device=dev)
+    cval = torch.empty(N, dtype=torch.float64, device=dev)
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
+    work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
+    _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
+                                         _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
+    return assign, cval, gain_d.cpu().numpy(), int(n_out.item()), rowptr, col, w

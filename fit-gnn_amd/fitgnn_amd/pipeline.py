@@ -141,7 +141,17 @@ class Coarsened:
 def coarsening_classification(args, data, coarsening_ratio, coarsening_method, device="cuda", batched=True):
     """utils.py:143-184: components sorted by size (descending, stable), coarsen() on every component with more
     than one node (Loukas r = 1 - --coarsening_ratio is passed by main.py:278), node -> cluster map from the
-    level mapping dicts; single nodes are their own cluster."""
+    level mapping dicts; single nodes are their own cluster.
+
+    The matching methods (heavy_edge, algebraic_JC, variation_edges) take the node -> cluster map of utils.py:167-182: the
+    row of the single non-zero in each column of C -- the same row the composed level dicts give for variation_neighborhoods,
+    so one construction serves both.  affinity_GS is refused here: the reference maps it through its identity level dicts
+    (every node its own meta-node), which no caller can use; coarsen() supports it.  The random methods (algebraic_JC) run
+    coarsen() per component, which keeps the reference's np.random draw order (component by component, level by level)."""
+    coarsening.check_method(coarsening_method)
+    if coarsening_method == "affinity_GS":
+        raise NotImplementedError("affinity_GS is supported by coarsening.coarsen() but not by the pipeline: the reference maps "
+                                  "every node to its own meta-node for it (utils.py:182 on identity level dicts)")
     N = data.num_nodes
     ei = np.asarray(data.edge_index)
     W = sp.csr_matrix((np.ones(ei.shape[1]), (ei[0], ei[1])), shape=(N, N))
@@ -154,13 +164,13 @@ def coarsening_classification(args, data, coarsening_ratio, coarsening_method, d
     assign = np.zeros(N, dtype=np.int64)
     out.comp_cluster_off = []
     multi = [H for H in comps if len(H.info["orig_idx"]) > 1]
-    if len(multi) > 4 and batched:
+    if len(multi) > 4 and batched and coarsening_method not in coarsening.RANDOM_METHODS:
         # many components (Cora: 78, CiteSeer: 438): ONE batched contraction instead of a device round trip per component
         # (same per-component prelude, same kernels with one wavefront per component: identical partitions)
         idxs = [np.asarray(H.info["orig_idx"], dtype=np.int64) for H in multi]
         perm = np.concatenate(idxs)
         comp_off = np.concatenate([[0], np.cumsum([len(i) for i in idxs])])
-        bc = coarsening.coarsen_batch(W[perm][:, perm], comp_off, r=coarsening_ratio, device=device)
+        bc = coarsening.coarsen_batch(W[perm][:, perm], comp_off, r=coarsening_ratio, device=device, method=coarsening_method)
         per = {}
         for c, (H, idx) in enumerate(zip(multi, idxs)):
             b, e, cb, ce = int(comp_off[c]), int(comp_off[c + 1]), int(bc.cluster_off[c]), int(bc.cluster_off[c + 1])
@@ -177,7 +187,7 @@ def coarsening_classification(args, data, coarsening_ratio, coarsening_method, d
                 C, Gc = per[id(H)]
             else:
                 C, Gc, maps = coarsening.coarsen(H, r=coarsening_ratio, method=coarsening_method, device=device)
-            a = sp.csc_matrix(C).indices.astype(np.int64)  # composed mapping dicts == row of C's single entry
+            a = sp.csc_matrix(C).indices.astype(np.int64)  # composed mapping dicts == row of C's single entry (== :167-180)
             assign[idx] = off + a
             off += C.shape[0]
             out.all_C.append(C); out.all_Gc.append(Gc)

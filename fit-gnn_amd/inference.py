@@ -48,7 +48,7 @@ def build_parser():
     p.add_argument('--use_community_detection', action='store_true')
     p.add_argument('--normalize_features', action='store_true')
     p.add_argument('--coarsening_ratio', type=float, default=0.5)
-    p.add_argument('--coarsening_method', type=str, default='variation_neighborhoods')
+    p.add_argument('--coarsening_method', type=str, default='variation_neighborhoods', choices=train_cli.COARSENING_METHODS)
     p.add_argument('--task', type=str, default='node_cls')
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--multi_prop', action='store_true')
@@ -166,6 +166,8 @@ def main(argv=None):
     args.train_fitgnn = True
     data, args = train_cli.process_dataset(args)
     if args.task in ("graph_cls", "graph_reg"):
+        if args.coarsening_method != "variation_neighborhoods":
+            raise NotImplementedError(f"graph-level tasks coarsen with variation_neighborhoods only, not '{args.coarsening_method}'")
         return graph_inference(args, data)
     from fitgnn_amd import network, pipeline
     from fitgnn_amd.csr import csr_for

@@ -34,6 +34,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
+# --coarsening_method values the node-level pipeline runs (coarsening.coarsen() also takes affinity_GS; the pipeline refuses it,
+# pipeline.coarsening_classification).  Anything else fails here, at argument parsing: no method falls back to another.
+COARSENING_METHODS = ('variation_neighborhoods', 'heavy_edge', 'algebraic_JC', 'variation_edges')
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument('--dataset', type=str, default='cora')
@@ -58,7 +63,7 @@ def build_parser():
     p.add_argument('--use_community_detection', action='store_true')
     p.add_argument('--normalize_features', action='store_true')
     p.add_argument('--coarsening_ratio', type=float, default=0.5)
-    p.add_argument('--coarsening_method', type=str, default='variation_neighborhoods')
+    p.add_argument('--coarsening_method', type=str, default='variation_neighborhoods', choices=COARSENING_METHODS)
     p.add_argument('--output_dir', type=str, required=True)
     p.add_argument('--task', type=str, default='node_cls')
     p.add_argument('--seed', type=int, default=None)
@@ -225,6 +230,8 @@ def main(argv=None):
         co = pipeline.coarsening_classification(args, data, 1 - args.coarsening_ratio, args.coarsening_method, device=args.device)
         return pipeline.node_regression(args, path, data, co, device=args.device)
     if args.task in ('graph_reg', 'graph_cls'):
+        if not args.baseline and args.coarsening_method != 'variation_neighborhoods':
+            raise NotImplementedError(f"graph-level tasks coarsen with variation_neighborhoods only, not '{args.coarsening_method}'")
         if args.baseline:
             return pipeline.graph_baseline(args, path, data, device=args.device)
         return pipeline.graph_regression(args, path, data, device=args.device)

@@ -650,6 +650,66 @@ int fitgnn_build_assignment(int32_t N, const int32_t *sel_off, const int32_t *se
 int fitgnn_compose_levels(int32_t N0, const int32_t *assign_l, const double *cval_l, int32_t *assign_tot,
                           double *cval_tot, void *stream);
 
+/* ---- matching-based coarsening methods (coarsening_utils.py: heavy_edge, algebraic_JC, affinity_GS :658-848,
+ * variation_edges :483-527, matching_greedy :931-993).  W is a symmetric CSR with ascending columns (w == NULL: all ones);
+ * the edges are the entries of tril(W, -1) in row-major order (the reference's get_edge_list() numbering): edge e = (e_src[e],
+ * e_dst[e]) with e_src > e_dst. */
+
+/* The edge list: edge_off int32[N+1] = first edge of every row (edge_off[N] = M), e_src / e_dst int32[m_cap], e_w f64[m_cap]
+ * (may be NULL) = W's entry; csr_eid int32[nnz] (may be NULL) = the edge of every CSR entry, both directions (-1 on the
+ * diagonal).  Edges at positions >= m_cap are not written. */
+int fitgnn_edge_list(const int32_t *rowptr, const int32_t *col, const double *w, int32_t N, int32_t *edge_off, int32_t *e_src,
+                     int32_t *e_dst, double *e_w, int64_t m_cap, int32_t *csr_eid, void *stream);
+
+/* heavy_edge (:680-686): prox f32[M] = e_w / max(wmax[src], wmax[dst]), wmax = column maxima of W + 1e-5. */
+size_t fitgnn_heavy_edge_proximity_workspace_bytes(int32_t N);
+int fitgnn_heavy_edge_proximity(const int32_t *rowptr, const int32_t *col, const double *w, int32_t N, const int32_t *e_src,
+                                const int32_t *e_dst, const double *e_w, int64_t M, float *prox, void *work, size_t work_bytes,
+                                void *stream);
+
+/* algebraic_JC (:689-698): prox f32[M] = min_k 1 / max((X[src,k] - X[dst,k])^2, 1e-6); X f64 [N x K] row-major (ldx). */
+int fitgnn_jc_proximity(const int32_t *e_src, const int32_t *e_dst, int64_t M, const double *X, int32_t K, int64_t ldx, float *prox,
+                        void *stream);
+
+/* affinity_GS (:701-715): c_e = (x_s.x_d)^2 / ((x_s.x_s)^2 (x_d.x_d)^2), prox f32[M] = c_e / (cmax[src] cmax[dst]) with cmax the
+ * maximum of c over a node's edges (the row maxima of the reference's dense N x N c; no dense matrix is formed). */
+size_t fitgnn_affinity_proximity_workspace_bytes(int32_t N, int64_t M);
+int fitgnn_affinity_proximity(int32_t N, const int32_t *e_src, const int32_t *e_dst, int64_t M, const double *X, int32_t K,
+                              int64_t ldx, float *prox, void *work, size_t work_bytes, void *stream);
+
+/* variation_edges (:495-514): cost f64[M] = ||B^T L2 B||_F = |A[src] - A[dst]|^2 / 4 * (2 dw[src] + 2 dw[dst]) (equal up to
+ * rounding); A f64 [N x K] row-major (lda). */
+int fitgnn_edge_variation_costs_f64(const int32_t *e_src, const int32_t *e_dst, int64_t M, const double *dw, const double *A,
+                                    int32_t K, int64_t lda, double *cost, void *stream);
+
+/* Jacobi test vectors (:834-848): X = `iterations` steps x <- 0.5 x + 0.5 D^-1 (D - L) x from X0, with the reference's float32
+ * degrees and reciprocals (D = diag(f32(dw)), L = diag(dw) - W).  X0, X f64 [N x K] row-major (ld K), X0 != X; one launch per
+ * step, ping-pong through the workspace. */
+size_t fitgnn_jacobi_vectors_workspace_bytes(int32_t N, int32_t K);
+int fitgnn_jacobi_vectors_f64(const int32_t *rowptr, const int32_t *col, const double *w, const double *dw, int32_t N,
+                              const double *X0, int32_t K, int32_t iterations, double *X, void *work, size_t work_bytes, void *stream);
+
+/* One Gauss-Seidel sweep (:822-832): X = -(D + L_lower)^-1 L_upper X0 on L = diag(dw) - W (W with zero diagonal).  A forward
+ * substitution: one wavefront per component [comp_off[c], comp_off[c+1]) (device int32[n_comp+1]; W must not couple two
+ * components) walks its rows in order -- deterministic, no workgroup waits on another.  X0, X f64 [N x K] (ld K), X0 != X. */
+int fitgnn_gauss_seidel_vectors_f64(const int32_t *rowptr, const int32_t *col, const double *w, const double *dw, int32_t N,
+                                    int32_t n_comp, const int32_t *comp_off, const double *X0, int32_t K, double *X, void *stream);
+
+/* Greedy heavy-edge matching (matching_greedy :931-993) with the stable order rank = (-weight ascending, edge id ascending; NaN
+ * last), on every component [comp_off[c], comp_off[c+1]) (device int32[n_comp+1]) at once: the greedy matching over all edges is
+ * computed by locally-dominant rounds (each unmatched node points at its best-ranked edge to an unmatched node, mutual pointers
+ * match) driven from the host -- this call SYNCHRONISES `stream` once per 1..64 rounds --, then the first k_keep[c] (device
+ * int64[n_comp]) matched edges of component c in rank order are kept: the reference's truncated scan.  A component that would
+ * keep <= min_gain pairs keeps none (coarsening_utils.py:131-135 does not apply such a level: pass 2 for a batch, 0 otherwise).  weight f64[M] (f32
+ * proximities convert exactly); edge arrays from fitgnn_edge_list.  Output in fitgnn_greedy_select's format, ready for
+ * fitgnn_build_assignment: one pair (e_src, e_dst) per kept edge in (component, rank) order, so the larger id keeps its row.
+ * comp_taken int32[n_comp] (may be NULL): pairs per component BEFORE the min_gain filter.  rounds (HOST int32, may be NULL): live rounds run. */
+size_t fitgnn_greedy_matching_workspace_bytes(int32_t N, int64_t M, int32_t n_comp);
+int fitgnn_greedy_matching(const int32_t *rowptr, const int32_t *col, const int32_t *csr_eid, int32_t N, const int32_t *edge_off,
+                           const int32_t *e_src, const int32_t *e_dst, int64_t M, const double *weight, int32_t n_comp,
+                           const int32_t *comp_off, const int64_t *k_keep, int64_t min_gain, int32_t *sel_off, int32_t *sel_mem, int32_t *sel_count,
+                           int32_t *comp_taken, int32_t *rounds, void *work, size_t work_bytes, void *stream);
+
 /* Adjacency lift Wc = zero_diag(Pinv^T W Pinv), then (Wc + Wc^T)/2 (coarsening_utils.py:138-139, :201-205),
  * with SciPy's summation order (bit-identical to the reference).  Outputs a CSR with ascending
  * columns: rowptr_c int32[n+1], col_c/w_c capacity nnz(W), nnz_c int32[1]. */
