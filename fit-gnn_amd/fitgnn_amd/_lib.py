@@ -16,6 +16,7 @@ ptr = ctypes.c_void_p
 EPI_BIAS, EPI_ELU, EPI_DROPOUT, EPI_SEED_DEVICE = 1, 2, 4, 8
 SPMM_GATHER = 0x100
 MAX_K = 16
+QUALITY_MAX_K = 64
 
 # name -> (restype, argtypes); mirrors include/fitgnn_hip.h one to one
 SIGNATURES = {
@@ -158,6 +159,15 @@ SIGNATURES = {
                                               ptr, ptr, ptr, c_size, ptr]),
     "fitgnn_pool_rows_workspace_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_pool_rows_f32": (ctypes.c_int, [ptr, ptr, c_i32, c_i32, ptr, c_i64, c_i32, ptr, c_i64, ptr, ptr, c_size, ptr]),
+    "fitgnn_coarse_laplacian_workspace_bytes": (c_size, [c_i32, c_i64, c_i32]),
+    "fitgnn_coarse_laplacian": (ctypes.c_int, [c_i32, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, c_i32, ptr, ptr, ptr, ptr, ptr, c_size, ptr]),
+    "fitgnn_project_lift_workspace_bytes": (c_size, [c_i32, c_i32]),
+    "fitgnn_project_lift_f64": (ctypes.c_int, [ptr, ptr, c_i32, c_i32, ptr, c_i64, c_i32, ptr, c_i64, ptr, c_i64, ptr, c_size, ptr]),
+    "fitgnn_laplacian_gram_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "fitgnn_laplacian_gram_f64": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i32, ptr, c_i64, c_i32, ptr, c_i64, c_i32, ptr, c_i64, ptr, c_size,
+                                                 ptr]),
+    "fitgnn_cross_atb_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "fitgnn_cross_atb_f64": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, c_i64, c_i32, c_i32, ptr, c_i64, ptr, c_size, ptr]),
 }
 
 _lib = None

@@ -838,3 +838,237 @@ def _select_level_batch(G, A, node_K_comp, off, n_comp, n_reduce, dev, st):
     _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
                                          _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
     return assign, cval, gain_d.cpu().numpy(), int(n_out.item()), rowptr, col, w
+
+
+# ---------------------------------------------------------------------------------------------
+# coarsening quality (coarsening_utils.py:257-351): k x k results only, no dense N x N or |E| x N object
+# ---------------------------------------------------------------------------------------------
+QUALITY_DEVICE_MAX_KMAX = 55          # spectral='device': kmax + 5 pairs, 2 (kmax + 5) + 7 <= 127 Lanczos basis vectors
+
+
+def _col_tiles(k):
+    w = _lib.QUALITY_MAX_K
+    return [(c, min(k, c + w)) for c in range(0, k, w)]
+
+
+def _off(t, row0, col0):
+    """Device pointer of t[row0, col0] (a contiguous 2-D f64 tensor)."""
+    return _lib.ctypes.c_void_p(t.data_ptr() + (row0 * t.shape[1] + col0) * t.element_size())
+
+
+def coarse_laplacian(W, dw, assign, cval, n):
+    """Lc = C L C^T (scipy csr, diagonal stored) on the device.  W: scipy csr (no self-loops); assign / cval: device tensors."""
+    L = _lib.lib()
+    dev = assign.device
+    N, nnz = int(W.shape[0]), int(W.nnz)
+    rowptr, col = _dev(W.indptr, torch.int32, dev), _dev(W.indices, torch.int32, dev)
+    w, dwd = _dev(W.data, torch.float64, dev), _dev(dw, torch.float64, dev)
+    wb = int(L.fitgnn_coarse_laplacian_workspace_bytes(N, nnz, n))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    rp = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    cc = torch.empty(max(nnz + n, 1), dtype=torch.int32, device=dev)
+    vv = torch.empty(max(nnz + n, 1), dtype=torch.float64, device=dev)
+    nz = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(L.fitgnn_coarse_laplacian(N, _lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), nnz, _lib.dptr(dwd), _lib.dptr(assign),
+                                         _lib.dptr(cval), n, _lib.dptr(rp), _lib.dptr(cc), _lib.dptr(vv), _lib.dptr(nz), _lib.dptr(work), wb,
+                                         _lib.stream_ptr(dev)), "coarse_laplacian")
+    m = int(nz.item())
+    return sp.csr_matrix((vv[:m].cpu().numpy(), cc[:m].cpu().numpy(), rp.cpu().numpy()), shape=(n, n))
+
+
+def project_lift(assign, cval, n, U, want_Y=True):
+    """(C U [n x k], Y = C^T C U [N x k]) on the device; U: device f64 [N x k].  Columns in tiles of QUALITY_MAX_K."""
+    L = _lib.lib()
+    dev = U.device
+    U = U.contiguous()
+    N, k = int(U.shape[0]), int(U.shape[1])
+    CU = torch.empty((n, k), dtype=torch.float64, device=dev)
+    Y = torch.empty((N, k), dtype=torch.float64, device=dev) if want_Y else None
+    wb = int(L.fitgnn_project_lift_workspace_bytes(N, n))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    for c0, c1 in _col_tiles(k):
+        _lib.check(L.fitgnn_project_lift_f64(_lib.dptr(assign), _lib.dptr(cval), N, n, _off(U, 0, c0), k, c1 - c0, _off(CU, 0, c0), k,
+                                             _off(Y, 0, c0) if want_Y else None, k, _lib.dptr(work), wb, _lib.stream_ptr(dev)), "project_lift")
+    return CU, Y
+
+
+def laplacian_gram(W, dw, Y):
+    """G = Y^T L Y (device f64 [k x k]) with L = diag(dw) - W; one CSR pass per (column tile, column tile) pair."""
+    L = _lib.lib()
+    dev = Y.device
+    Y = Y.contiguous()
+    N, k = int(Y.shape[0]), int(Y.shape[1])
+    rowptr = _dev(W.indptr, torch.int32, dev)
+    # an edgeless graph still hands the kernel non-NULL entry arrays (never read)
+    col = _dev(W.indices if W.nnz else np.zeros(1), torch.int32, dev)
+    w, dwd = _dev(W.data if W.nnz else np.zeros(1), torch.float64, dev), _dev(dw, torch.float64, dev)
+    G = torch.empty((k, k), dtype=torch.float64, device=dev)
+    for p0, p1 in _col_tiles(k):
+        for q0, q1 in _col_tiles(k):
+            wb = int(L.fitgnn_laplacian_gram_workspace_bytes(N, p1 - p0, q1 - q0))
+            work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+            _lib.check(L.fitgnn_laplacian_gram_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dwd), N, _off(Y, 0, p0), k,
+                                                   p1 - p0, _off(Y, 0, q0), k, q1 - q0, _off(G, p0, q0), k, _lib.dptr(work), wb,
+                                                   _lib.stream_ptr(dev)), "laplacian_gram")
+    return G
+
+
+def cross_atb(A, B):
+    """A^T B (device f64 [k1 x k2]) for device f64 A [n x k1], B [n x k2]."""
+    L = _lib.lib()
+    dev = A.device
+    A, B = A.contiguous(), B.contiguous()
+    n, k1, k2 = int(A.shape[0]), int(A.shape[1]), int(B.shape[1])
+    assert int(B.shape[0]) == n
+    out = torch.empty((k1, k2), dtype=torch.float64, device=dev)
+    for p0, p1 in _col_tiles(k1):
+        for q0, q1 in _col_tiles(k2):
+            wb = int(L.fitgnn_cross_atb_workspace_bytes(n, p1 - p0, q1 - q0))
+            work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+            _lib.check(L.fitgnn_cross_atb_f64(_off(A, 0, p0), k1, p1 - p0, _off(B, 0, q0), k2, q1 - q0, n, _off(out, p0, q0), k2,
+                                              _lib.dptr(work), wb, _lib.stream_ptr(dev)), "cross_atb")
+    return out
+
+
+def _quality_inputs(G, C):
+    """Host checks of coarsening_quality's inputs (before any device work).  Returns (W csr, dw, assign, cval, n)."""
+    if not hasattr(G, "W"):
+        raise TypeError("G must expose .W (scipy sparse adjacency) and .N")
+    W = sp.csr_matrix(G.W, dtype=np.float64)
+    W.eliminate_zeros()
+    W.sort_indices()
+    N = W.shape[0]
+    if W.shape != (N, N):
+        raise ValueError(f"W must be square, got {W.shape}")
+    if W.diagonal().any():
+        raise ValueError("coarsening_quality needs a graph without self-loops (S^T S = L, which the metrics rest on, fails there)")
+    Cc = sp.csc_matrix(C)
+    if Cc.shape[1] != N:
+        raise ValueError(f"C has {Cc.shape[1]} columns, the graph has {N} nodes")
+    Cc.sort_indices()
+    if not np.all(np.diff(Cc.indptr) == 1):
+        raise NotImplementedError("coarsening_quality needs a C with exactly one non-zero per column (what coarsen() produces)")
+    dw = np.ravel(W.sum(axis=0))
+    return W, dw, Cc.indices.astype(np.int32), Cc.data.astype(np.float64), int(Cc.shape[0])
+
+
+def _lanczos_pairs(Lmat, k):
+    """The k smallest eigenpairs by lanczos_smallest, run for k + 5 pairs: its stopping rule bounds every wanted residual by
+    tol times the largest shifted eigenvalue, so the last wanted pairs are the loosest; the 5 extra ones absorb that."""
+    N = Lmat.shape[0]
+    K = k + 5
+    m = min(127, N - 1, 4 * K + 20)
+    if 2 * K + 7 > m:
+        raise ValueError(f"spectral='device' cannot serve kmax={k} on a graph of {N} nodes (lanczos_smallest keeps at most "
+                         f"min(127, N - 1) basis vectors and needs 2 (kmax + 5) + 7 of them); use spectral='arpack'")
+    l, U = lanczos_smallest(Lmat, K, m=m)
+    return l[:k], np.ascontiguousarray(U[:, :k])
+
+
+def coarsening_quality(G, C, kmax=30, Uk=None, lk=None, device="cuda", spectral="arpack", Uc=None, lc=None, timings=None):
+    """coarsening_quality (coarsening_utils.py:257-351) with the reference's arguments and returned dict: r, m, error_eigenvalue,
+    angle_matrix, error_subspace, error_sintheta, with the reference's shapes in every branch (U = Uk whole when
+    len(lk) >= kmax; the dense eig(Lc) branch when kmax > n / 2; kmax clipped to [1, n] and [2, n]).
+
+    The reference's dense S (|E| x N) and M = S Pi U diag(l^-1/2) are never formed: ||M[:, :k+1]||_2 is the square root of the
+    largest eigenvalue of the leading block of D U^T Pi L Pi U D (S^T S = L without self-loops).  On the device: Lc = C L C^T,
+    C U and Y = C^T C U, G = Y^T L Y (one CSR pass per 64-column tile pair), the angle matrix (C U)^T Uc.  On the host: the
+    eigenvalues of the leading blocks of D G D, the Frobenius norms, the coarse eigenproblem of the dense branch.
+
+    spectral='arpack': the reference's eigsh(..., which='SM', tol=1e-3) calls and np.linalg.eigh for the dense branch;
+    spectral='device': lanczos_smallest (tol 1e-5, kmax + 5 pairs) for L and Lc (kmax <= QUALITY_DEVICE_MAX_KMAX; the dense
+    branch stays the n x n eigh, n < 2 kmax).  Uc, lc (extension): injected coarse eigenpairs, used instead of any coarse eigensolve.
+    timings (extension): a dict that receives the seconds of each stage (the stream is synchronised between stages).
+    Unlike the reference, the caller's lk is not modified (the reference sets lk[0] = 1 in place).
+    C: a CoarseningMatrix or any scipy n x N matrix with exactly one non-zero per column (else NotImplementedError).
+    Raises ValueError for a graph with self-loops or a C whose width is not G.N; there is no CPU fallback."""
+    import time
+
+    import scipy.sparse.linalg as spla
+
+    W, dw, assign_h, cval_h, n = _quality_inputs(G, C)
+    if spectral not in ("arpack", "device"):
+        raise ValueError(f"spectral must be 'arpack' or 'device', got {spectral!r}")
+    if spectral == "device" and kmax > QUALITY_DEVICE_MAX_KMAX:
+        raise ValueError(f"spectral='device' serves kmax <= {QUALITY_DEVICE_MAX_KMAX} (lanczos_smallest: at most 127 basis vectors)")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.FitgnnError("coarsening_quality runs on the MI355X (no CPU fallback)")
+    N = W.shape[0]
+    tm = timings if timings is not None else {}
+
+    def stage(name, t0):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+        tm[name] = tm.get(name, 0.0) + time.perf_counter() - t0
+
+    Lfull = (sp.diags(dw, 0) - W).tocsc()
+    t0 = time.perf_counter()
+    if (Uk is not None) and (lk is not None) and (len(lk) >= kmax):
+        U, l = np.asarray(Uk), np.array(lk, dtype=np.float64)
+    elif hasattr(G, "U") and hasattr(G, "e"):
+        U, l = np.asarray(G.U), np.array(G.e, dtype=np.float64)
+    elif spectral == "device":
+        l, U = _lanczos_pairs(Lfull, kmax)
+    else:
+        l, U = spla.eigsh(Lfull, k=kmax, which="SM", tol=1e-3)
+    stage("eig_L", t0)
+    l = np.array(l, dtype=np.float64)
+    l[0] = 1
+    linv = l ** (-0.5)
+    linv[0] = 0
+
+    t0 = time.perf_counter()
+    assign, cval = _dev(assign_h, torch.int32, dev), _dev(cval_h, torch.float64, dev)
+    Lc = coarse_laplacian(W, dw, assign, cval, n)
+    stage("Lc", t0)
+
+    t0 = time.perf_counter()
+    if Uc is not None and lc is not None:
+        Uc, lc = np.asarray(Uc), np.asarray(lc)
+    elif kmax > n / 2:
+        lc, Uc = np.linalg.eigh(Lc.toarray())      # graph_utils.eig: ascending
+        o = lc.argsort()
+        lc, Uc = np.real(lc[o]), Uc[:, o]
+    elif spectral == "device":
+        lc, Uc = _lanczos_pairs(Lc, kmax)
+    else:
+        lc, Uc = spla.eigsh(Lc, k=kmax, which="SM", tol=1e-3)
+    stage("eig_Lc", t0)
+
+    metrics = {"r": 1 - n / N, "m": int((np.count_nonzero(Lc.data) - n) / 2)}
+    ke = int(np.clip(kmax, 1, n))
+    err = np.abs(l[:ke] - lc[:ke]) / l[:ke]
+    err[0] = 0
+    metrics["error_eigenvalue"] = err
+
+    kl = int(np.clip(ke, 2, n))
+    kU = U.shape[1]
+    kg = min(kl, kU)                       # M's columns the loop reads
+    t0 = time.perf_counter()
+    Ud = _dev(np.real(U), torch.float64, dev)
+    CU, Y = project_lift(assign, cval, n, Ud)
+    stage("project", t0)
+    t0 = time.perf_counter()
+    Gd = laplacian_gram(W, dw, Y[:, :kg]).cpu().numpy()
+    stage("gram", t0)
+    t0 = time.perf_counter()
+    Ucd = _dev(np.real(Uc), torch.float64, dev)
+    ang = cross_atb(CU, Ucd).cpu().numpy()
+    if np.iscomplexobj(Uc):
+        ang = ang + 1j * cross_atb(CU, _dev(np.imag(Uc), torch.float64, dev)).cpu().numpy()
+    stage("cross", t0)
+    metrics["angle_matrix"] = ang
+
+    MtM = linv[:kg, None] * Gd * linv[None, :kg]
+    MtM = (MtM + MtM.T) / 2
+    error_subspace = np.zeros(kl)
+    error_sintheta = np.zeros(kl)
+    for kIdx in range(1, kl):
+        b = min(kIdx + 1, kg)
+        lam = float(np.linalg.eigvalsh(MtM[:b, :b])[-1])
+        error_subspace[kIdx] = np.abs(np.sqrt(max(lam, 0.0)) - 1)
+        error_sintheta[kIdx] = np.linalg.norm(ang[0:kIdx + 1, kIdx + 1:], ord="fro") ** 2
+    metrics["error_subspace"] = error_subspace
+    metrics["error_sintheta"] = error_sintheta
+    return metrics

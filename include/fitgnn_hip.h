@@ -769,6 +769,47 @@ int fitgnn_pool_rows_f32(const int32_t *assign, const double *cval, int32_t N, i
                          int64_t ldx, int32_t F, float *Xc, int64_t ldxc, double *Xc64, void *work,
                          size_t work_bytes, void *stream);
 
+/* ---- coarsening quality (coarsening_utils.py:257-351 coarsening_quality; graph_utils.py:45-61 get_S).  The reference forms the
+ * dense incidence matrix S (|E| x N) and M = S Pi U diag(l^-1/2); these calls compute the k x k quantities it needs instead:
+ * M^T M = D U^T Pi L Pi U D because S^T S = L for a graph without self-loops (D = diag(l^-1/2), Pi = C^T C).  C is given as in
+ * fitgnn_build_assignment's output: assign int32[N] in [0, n) and cval f64[N] (one non-zero per column).  All arithmetic is f64,
+ * every sum runs in a fixed order (no floating-point atomics): two launches give identical bits.  k1, k2, k <= FITGNN_QUALITY_MAX_K. */
+#define FITGNN_QUALITY_MAX_K 64
+
+/* Lc = C L C^T (:287 Lc = C.dot(G.L.dot(C.T))) as a CSR with ascending columns, diagonal included.  W: symmetric CSR without
+ * self-loops (w == NULL: all ones), nnz = rowptr[N]; dw f64[N] its degrees, L = diag(dw) - W.  Off-diagonal entries are
+ * -(C W C^T)[a][b], built by fitgnn_lift_adjacency on the c-scaled weights (symmetrised; pairs whose sum is exactly zero are not
+ * stored); the diagonal of cluster a is sum_{i in a} (c_i^2 d_i - c_i sum_{j in a} w_ij c_j) over its members in ascending order
+ * and is ALWAYS stored, also when it is zero (the reference's sparse product would drop such an entry: count non-zero values to
+ * reproduce its Lc.nnz).  Outputs rowptr_c int32[n+1], col_c / val_c capacity nnz + n, nnz_c int32[1].  Synchronises `stream` once
+ * (the lift's size read-back). */
+size_t fitgnn_coarse_laplacian_workspace_bytes(int32_t N, int64_t nnz, int32_t n);
+int fitgnn_coarse_laplacian(int32_t N, const int32_t *rowptr, const int32_t *col, const double *w, int64_t nnz, const double *dw,
+                            const int32_t *assign, const double *cval, int32_t n, int32_t *rowptr_c, int32_t *col_c, double *val_c,
+                            int32_t *nnz_c, void *work, size_t work_bytes, void *stream);
+
+/* Project and lift (the Pi U of :322 M = S Pi U diag(linv), and the C U of :311 angle_matrix = U^T C^T Uc):
+ * CU[a][c] = sum_{i in a} cval_i U[i][c] over the members in ascending order (f64[n x k], ldcu), then Y[i][c] = cval_i CU[assign_i][c]
+ * (f64[N x k], ldy; Y == NULL: CU only).  U f64[N x k] row-major (ldu). */
+size_t fitgnn_project_lift_workspace_bytes(int32_t N, int32_t n);
+int fitgnn_project_lift_f64(const int32_t *assign, const double *cval, int32_t N, int32_t n, const double *U, int64_t ldu, int32_t k,
+                            double *CU, int64_t ldcu, double *Y, int64_t ldy, void *work, size_t work_bytes, void *stream);
+
+/* Laplacian Gram G = Y1^T L Y2 (f64[k1 x k2], ldg) with L = diag(dw) - W (W as above): ONE pass over W's CSR forms
+ * z_i = dw_i Y2[i] - sum_j w_ij Y2[j] per row and accumulates Y1[i] z_i^T into per-workgroup partials over a row split that depends
+ * only on N and the widths, then a fixed-order reduction.  With Y1 = Y2 = Pi U this is U^T Pi L Pi U (the metric's M^T M up to D).
+ * Y1 f64[N x k1] (ld1), Y2 f64[N x k2] (ld2). */
+size_t fitgnn_laplacian_gram_workspace_bytes(int32_t N, int32_t k1, int32_t k2);
+int fitgnn_laplacian_gram_f64(const int32_t *rowptr, const int32_t *col, const double *w, const double *dw, int32_t N, const double *Y1,
+                              int64_t ld1, int32_t k1, const double *Y2, int64_t ld2, int32_t k2, double *G, int64_t ldg, void *work,
+                              size_t work_bytes, void *stream);
+
+/* Tall-skinny cross product out = A^T B (f64[k1 x k2], ldo) over n rows: A f64[n x k1] (lda), B f64[n x k2] (ldb), with the same
+ * partial / fixed-order reduction as the Gram (:311 angle_matrix = (C U)^T Uc). */
+size_t fitgnn_cross_atb_workspace_bytes(int32_t n, int32_t k1, int32_t k2);
+int fitgnn_cross_atb_f64(const double *A, int64_t lda, int32_t k1, const double *B, int64_t ldb, int32_t k2, int32_t n, double *out,
+                         int64_t ldo, void *work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
