@@ -800,21 +800,16 @@ extern "C" int fitgnn_appnp_blocks_f32(const int32_t *rowptr, const int32_t *col
     const int cap_rows = (max_rows + 3) / 4 * 4, cap_entries = (max_entries + 3) / 4 * 4 + 4;
     const size_t lds = (size_t)(cap_rows + 4) * sizeof(int32_t) + (size_t)cap_entries * (sizeof(int32_t) + sizeof(float));
     const void *fn = backward ? (const void *)appnp_blocks_kernel<true> : (const void *)appnp_blocks_kernel<false>;
-    int threads = kAppnpBlockThreads;
-    if (const char *ev = getenv("FITGNN_APPNP_BLOCK_THREADS")) {   // tuning knob: 64 .. 1024, whole wavefronts
-        const int t = atoi(ev);
-        if (t >= 64 && t <= kAppnpBlockThreads && t % 64 == 0) threads = t;
-    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
     if (backward)
-        hipLaunchKernelGGL(appnp_blocks_kernel<true>, dim3((unsigned)n_blocks), dim3(threads), lds, (hipStream_t)stream, rowptr, col,
-                           val, blocks, n_blocks, (const float4 *)X, (float4 *)Y, (float4 *)T1, (float4 *)T2, h4, K, alpha, cap_rows);
+        hipLaunchKernelGGL(appnp_blocks_kernel<true>, dim3((unsigned)n_blocks), dim3(kAppnpBlockThreads), lds, (hipStream_t)stream, rowptr,
+                           col, val, blocks, n_blocks, (const float4 *)X, (float4 *)Y, (float4 *)T1, (float4 *)T2, h4, K, alpha, cap_rows);
     else
-        hipLaunchKernelGGL(appnp_blocks_kernel<false>, dim3((unsigned)n_blocks), dim3(threads), lds, (hipStream_t)stream, rowptr, col,
-                           val, blocks, n_blocks, (const float4 *)X, (float4 *)Y, (float4 *)T1, (float4 *)T2, h4, K, alpha, cap_rows);
+        hipLaunchKernelGGL(appnp_blocks_kernel<false>, dim3((unsigned)n_blocks), dim3(kAppnpBlockThreads), lds, (hipStream_t)stream, rowptr,
+                           col, val, blocks, n_blocks, (const float4 *)X, (float4 *)Y, (float4 *)T1, (float4 *)T2, h4, K, alpha, cap_rows);
     return (int)hipGetLastError();
 }
 
@@ -852,7 +847,7 @@ template <bool BWD>
 __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                          const float *__restrict__ val, const int32_t *__restrict__ ranges, int32_t n_ranges,
                                                          const float4 *__restrict__ X, float4 *__restrict__ Y, int32_t h4, int32_t K, float alpha,
-                                                         int32_t max_rows, int32_t max_entries, int32_t slice, int32_t dbg) {
+                                                         int32_t max_rows, int32_t max_entries, int32_t slice) {
     extern __shared__ __attribute__((aligned(16))) unsigned char al_lds[];
     const LdsPlan P = appnp_lds_plan(max_rows, max_entries, slice);
     float4 *buf = reinterpret_cast<float4 *>(al_lds);          // the slice of the signal: ONE buffer (see the step loop)
@@ -882,7 +877,7 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
     for (int i = tid; i < n; i += T)
         if (s_rp[i + 1] - s_rp[i] > kLdsShort) s_long[atomicAdd(s_cnt, 1)] = (uint16_t)i;
     __syncthreads();
-    const int n_long = *s_cnt;
+    const int n_long = __builtin_amdgcn_readfirstlane(*s_cnt);   // workgroup-uniform: n_long and n_long << lw in SGPRs, not two VGPRs
     const float beta = 1.0f - alpha;
     for (int c0 = 0; c0 < h4;) {
         // this slice: w = the largest power of two <= min(slice, h4 - c0) columns
@@ -935,7 +930,6 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
         for (int k = 0; k < K; ++k) {
             const float4 *cur = buf;
             float4 yv[kLdsKeep];
-            if (!(dbg & 2))
 #pragma unroll
             for (int jh = 0; jh < kLdsKeep; jh += kLdsFly) {   // kLdsFly items' eight operand reads in flight (all four items': spills at 1 024 threads)
             if (BWD) {   // the running alpha-sum first (its operand is not live beside the eight gathers below)
@@ -988,66 +982,63 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
                 }
             }
             }
-            if (!(dbg & 1)) {
-                // the long rows, 8 / w at a time per wavefront: lane = (group, entry slot 0..7, slice column); a lane sums entries
-                // e0 + slot, e0 + slot + 8, ... in order (four in flight), the eight slots fold by xor shuffles in a fixed tree
-                const int q_l = lane & (w - 1), slot = (lane >> lw) & 7, grp = lane >> (lw + 3);
-                const int rpw = 8 >> lw;
-                for (int jb = 0; jb < n_long; jb += W * rpw) {
-                    const int j = jb + wave * rpw + grp;
-                    const bool on = j < n_long;
-                    int row = 0, e = 0, e1 = 0;
-                    if (on) {
-                        row = s_long[j];
-                        e = s_rp[row] + slot;
-                        e1 = s_rp[row + 1];
-                    }
-                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    for (; e < e1; e += 32) {
-                        int c[4];
-                        float v[4];
+            // the long rows, 8 / w at a time per wavefront: lane = (group, entry slot 0..7, slice column); a lane sums entries
+            // e0 + slot, e0 + slot + 8, ... in order (four in flight), the eight slots fold by xor shuffles in a fixed tree
+            const int q_l = lane & (w - 1), slot = (lane >> lw) & 7, grp = lane >> (lw + 3);
+            const int rpw = 8 >> lw;
+            for (int jb = 0; jb < n_long; jb += W * rpw) {
+                const int j = jb + wave * rpw + grp;
+                const bool on = j < n_long;
+                int row = 0, e = 0, e1 = 0;
+                if (on) {
+                    row = s_long[j];
+                    e = s_rp[row] + slot;
+                    e1 = s_rp[row + 1];
+                }
+                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (; e < e1; e += 32) {
+                    int c[4];
+                    float v[4];
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const bool has = e + 8 * t < e1;
-                            c[t] = s_col[has ? e + 8 * t : e];
-                            v[t] = has ? s_val[e + 8 * t] : 0.f;
-                        }
-                        float4 x[4];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) x[t] = cur[(c[t] << lw) + q_l];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            acc.x = fmaf(v[t], x[t].x, acc.x); acc.y = fmaf(v[t], x[t].y, acc.y);
-                            acc.z = fmaf(v[t], x[t].z, acc.z); acc.w = fmaf(v[t], x[t].w, acc.w);
-                        }
+                    for (int t = 0; t < 4; ++t) {
+                        const bool has = e + 8 * t < e1;
+                        c[t] = s_col[has ? e + 8 * t : e];
+                        v[t] = has ? s_val[e + 8 * t] : 0.f;
                     }
+                    float4 x[4];
 #pragma unroll
-                    for (int st = 4; st >= 1; st >>= 1) {
-                        const int off = st << lw;
-                        acc.x += __shfl_xor(acc.x, off, 64); acc.y += __shfl_xor(acc.y, off, 64);
-                        acc.z += __shfl_xor(acc.z, off, 64); acc.w += __shfl_xor(acc.w, off, 64);
+                    for (int t = 0; t < 4; ++t) x[t] = cur[(c[t] << lw) + q_l];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        acc.x = fmaf(v[t], x[t].x, acc.x); acc.y = fmaf(v[t], x[t].y, acc.y);
+                        acc.z = fmaf(v[t], x[t].z, acc.z); acc.w = fmaf(v[t], x[t].w, acc.w);
                     }
-                    if (on && slot == 0) {
-                        const int i = (row << lw) + q_l;
-                        float4 y = make_float4(beta * acc.x, beta * acc.y, beta * acc.z, beta * acc.w);
-                        float4 kp = s_keep[(j << lw) + q_l];
-                        if (BWD) {
-                            const float4 x = cur[i];
-                            kp.x = fmaf(alpha, x.x, kp.x); kp.y = fmaf(alpha, x.y, kp.y); kp.z = fmaf(alpha, x.z, kp.z); kp.w = fmaf(alpha, x.w, kp.w);
-                            s_keep[(j << lw) + q_l] = kp;
-                        } else {
-                            y.x = fmaf(alpha, kp.x, y.x); y.y = fmaf(alpha, kp.y, y.y); y.z = fmaf(alpha, kp.z, y.z); y.w = fmaf(alpha, kp.w, y.w);
-                        }
-                        s_ylong[(j << lw) + q_l] = y;
+                }
+#pragma unroll
+                for (int st = 4; st >= 1; st >>= 1) {
+                    const int off = st << lw;
+                    acc.x += __shfl_xor(acc.x, off, 64); acc.y += __shfl_xor(acc.y, off, 64);
+                    acc.z += __shfl_xor(acc.z, off, 64); acc.w += __shfl_xor(acc.w, off, 64);
+                }
+                if (on && slot == 0) {
+                    const int i = (row << lw) + q_l;
+                    float4 y = make_float4(beta * acc.x, beta * acc.y, beta * acc.z, beta * acc.w);
+                    float4 kp = s_keep[(j << lw) + q_l];
+                    if (BWD) {
+                        const float4 x = cur[i];
+                        kp.x = fmaf(alpha, x.x, kp.x); kp.y = fmaf(alpha, x.y, kp.y); kp.z = fmaf(alpha, x.z, kp.z); kp.w = fmaf(alpha, x.w, kp.w);
+                        s_keep[(j << lw) + q_l] = kp;
+                    } else {
+                        y.x = fmaf(alpha, kp.x, y.x); y.y = fmaf(alpha, kp.y, y.y); y.z = fmaf(alpha, kp.z, y.z); y.w = fmaf(alpha, kp.w, y.w);
                     }
+                    s_ylong[(j << lw) + q_l] = y;
                 }
             }
             __syncthreads();   // every gather of the step done
 #pragma unroll
             for (int j = 0; j < kLdsKeep; ++j)
                 if ((it_en[j] & 31u) > 0) buf[tid + j * T] = yv[j];
-            if (!(dbg & 1))
-                for (int i = tid; i < (n_long << lw); i += T) buf[((int)s_long[i >> lw] << lw) + (i & (w - 1))] = s_ylong[i];
+            for (int i = tid; i < (n_long << lw); i += T) buf[((int)s_long[i >> lw] << lw) + (i & (w - 1))] = s_ylong[i];
             __syncthreads();
         }
         float4 *fin = buf;
@@ -1095,18 +1086,16 @@ extern "C" int fitgnn_appnp_lds_f32(const int32_t *rowptr, const int32_t *col, c
     if (!rowptr || !col || !val || !ranges || !X || !Y) return FITGNN_E_BADARG;
     if ((((uintptr_t)X | (uintptr_t)Y) % 16) != 0) return FITGNN_E_ALIGN;
     const void *fn = backward ? (const void *)appnp_lds_kernel<true> : (const void *)appnp_lds_kernel<false>;
-    const char *dv = getenv("FITGNN_APPNP_LDS_DEBUG");
-    const int dbg = dv ? atoi(dv) : 0;
     if (P.bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.bytes);
         if (e != hipSuccess) return (int)e;
     }
     if (backward)
         hipLaunchKernelGGL(appnp_lds_kernel<true>, dim3((unsigned)n_ranges), dim3(threads), P.bytes, (hipStream_t)stream, rowptr, col, val, ranges,
-                           n_ranges, (const float4 *)X, (float4 *)Y, h4, K, alpha, max_rows, max_entries, slice, dbg);
+                           n_ranges, (const float4 *)X, (float4 *)Y, h4, K, alpha, max_rows, max_entries, slice);
     else
         hipLaunchKernelGGL(appnp_lds_kernel<false>, dim3((unsigned)n_ranges), dim3(threads), P.bytes, (hipStream_t)stream, rowptr, col, val, ranges,
-                           n_ranges, (const float4 *)X, (float4 *)Y, h4, K, alpha, max_rows, max_entries, slice, dbg);
+                           n_ranges, (const float4 *)X, (float4 *)Y, h4, K, alpha, max_rows, max_entries, slice);
     return (int)hipGetLastError();
 }
 

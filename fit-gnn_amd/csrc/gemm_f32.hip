@@ -22,7 +22,6 @@
 // operand traffic is (TI + TJ) x 4 bytes per 2 TI TJ flops = 64 flop/byte at 256 x 256, 2.4 TB/s at the fp32 MFMA peak.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 #include "common.h"
 #include "fitgnn_hip.h"
@@ -105,7 +104,7 @@ __device__ __forceinline__ void frag(float (&f)[4], const float *lds, int o, int
 
 // nchunks > 1: split over k.  Workgroup (chunk, tile) reduces k in [chunk * chunk_k, +chunk_k) and stores its tile into
 // partial[chunk] (an [I x J] matrix each); sum_chunks_kernel adds them in a fixed order.
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool PIPE = false>
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb,
                                                                    long I, int J, long K, float *__restrict__ C, long ldc, int tiles_i,
                                                                    int tiles_j, int nchunks, long chunk_k) {
@@ -151,12 +150,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
     }
     __syncthreads();
     // The stage loop: the next stage's operand slabs are requested before a stage is multiplied and stored to the other LDS buffer
-    // after it.  Two deeper forms were built on rocprofv3's "MFMA pipe busy 80 % of the SIMD cycles at 2.31 GHz" (tools/pmc_gemm.sh)
-    // and measured out (tools/gemm_shape_probe.py, profiles/r04_gemm_shape_probe_*.log): (a) PIPE (opt-in, FITGNN_GEMM_DEEP=1 on the
-    // small tile shapes) requests the next-but-ONE stage as well (two register sets used alternately: a small tile's stage is 1-2 us of
-    // products per workgroup, about a global load's round trip): 0-10 % SLOWER on every shape (238 -> 253 us on the 165 000 x 512 x 128
-    // table product, 113 -> 125 on 19 717 x 512 x 512); (b) a loop pipelined across its barrier (the last k-octet's fragments read
-    // before it, multiplied after it under the next stage's first LDS reads): +-1 % -- removed.
+    // after it.  Two deeper forms were built on rocprofv3's "MFMA pipe busy 80 % of the SIMD cycles at 2.31 GHz" (tools/pmc_gemm.sh),
+    // measured out and removed (profiles/r04_gemm_shape_probe_*.log): (a) a two-stage look-ahead that requested the next-but-ONE
+    // stage as well (two register sets used alternately: a small tile's stage is 1-2 us of products per workgroup, about a global
+    // load's round trip): 0-10 % SLOWER on every shape (238 -> 253 us on the 165 000 x 512 x 128 table product, 113 -> 125 on
+    // 19 717 x 512 x 512; profiles/r04_gemm_shape_probe_two_stage_lookahead.log); (b) a loop pipelined across its barrier (the last
+    // k-octet's fragments read before it, multiplied after it under the next stage's first LDS reads): +-1 %.
     auto read_frags = [&](float (&fa)[MI][4], float (&fb)[NJ][4], const float *sa, const float *sb, int kk) {
 #pragma unroll
         for (int i = 0; i < MI; ++i) frag<AKM, G::TI>(fa[i], sa, wm * (32 * MI) + i * 32, kk, lane);
@@ -183,47 +182,20 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
             multiply(fa, fb);
         }
     };
-    if (!PIPE) {
-        for (int s = 0; s < nstage; ++s) {
-            const bool more = s + 1 < nstage;   // workgroup-uniform
-            if (more) {
-                const long k0 = k_begin + (long)(s + 1) * kBK;
-                load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k0, k_end);
-                load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k0, k_end);
-            }
-            products(s);
-            if (more) {
-                float *na = lds_f + ((s + 1) & 1) * G::STAGE_DW;
-                store_slab<AKM, G::TI, G::NA, G::THREADS>(ra, na);
-                store_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, na + G::A_DW);
-            }
-            __syncthreads();
+    for (int s = 0; s < nstage; ++s) {
+        const bool more = s + 1 < nstage;   // workgroup-uniform
+        if (more) {
+            const long k0 = k_begin + (long)(s + 1) * kBK;
+            load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k0, k_end);
+            load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k0, k_end);
         }
-    } else {
-        float4 ra2[G::NA], rb2[G::NB];
-        if (nstage > 1) {   // stage 1 on its way while stage 0 is multiplied
-            load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k_begin + kBK, k_end);
-            load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k_begin + kBK, k_end);
+        products(s);
+        if (more) {
+            float *na = lds_f + ((s + 1) & 1) * G::STAGE_DW;
+            store_slab<AKM, G::TI, G::NA, G::THREADS>(ra, na);
+            store_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, na + G::A_DW);
         }
-        // one stage: `cur` holds stage s + 1 (requested a stage ago), `nxt` receives stage s + 2
-        auto body = [&](int s, float4 (&cur_a)[G::NA], float4 (&cur_b)[G::NB], float4 (&nxt_a)[G::NA], float4 (&nxt_b)[G::NB]) {
-            if (s + 2 < nstage) {
-                const long k0 = k_begin + (long)(s + 2) * kBK;
-                load_slab<AKM, G::TI, G::NA, G::THREADS>(nxt_a, A, lda, i0, I, k0, k_end);
-                load_slab<BKM, G::TJ, G::NB, G::THREADS>(nxt_b, B, ldb, j0, (long)J, k0, k_end);
-            }
-            products(s);
-            if (s + 1 < nstage) {
-                float *na = lds_f + ((s + 1) & 1) * G::STAGE_DW;
-                store_slab<AKM, G::TI, G::NA, G::THREADS>(cur_a, na);
-                store_slab<BKM, G::TJ, G::NB, G::THREADS>(cur_b, na + G::A_DW);
-            }
-            __syncthreads();
-        };
-        for (int s = 0; s < nstage; s += 2) {
-            body(s, ra, rb, ra2, rb2);
-            if (s + 1 < nstage) body(s + 1, ra2, rb2, ra, rb);
-        }
+        __syncthreads();
     }
 
     // C/D layout of the 32 x 32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
@@ -298,13 +270,11 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
         else p.shape = S256;
     } else if (J <= 64) {
         p.shape = S128x64;   // the head on the loss rows (47 classes): a 128-column tile multiplied mostly padding
-    } else if (getenv("FITGNN_GEMM_NO_SMALL_TILES")) {
-        p.shape = J <= 128 ? S256x128 : S256;
     } else {
         // One CU works through ceil(tiles / 256) tiles of TI x TJ outputs each, whatever shares the CU meanwhile; the smaller shapes
         // lose a little per flop (operands re-read more often; 128 x 128 does not fill its third round evenly) and win whenever the
         // 256 x 256 grid is coarse: 19 717 rows (154 tiles) 146 -> 111 us, 4 861 rows (38 tiles) 136 -> 45 us, a rank's 20 625 loss rows
-        // 135 -> 120 us; from ~90 000 rows on 256 x 256 is the fastest again (414 vs 423 / 440 us)  [tools/gemm_shape_probe.py]
+        // 135 -> 120 us; from ~90 000 rows on 256 x 256 is the fastest again (414 vs 423 / 440 us)  [profiles/r04_gemm_shape_probe_*.log]
         // (64 x 64: a 128-molecule QM9 batch, 4 861 rows = 304 tiles of 64 x 128, still leaves every fifth CU with two tiles)
         const int cand[4] = {J <= 128 ? S256x128 : S256, S128, S64x128, S64x64};
         const double eff[4] = {1.0, K <= 256 ? 1.0 : 0.85, 0.94, 0.85};   // short k: two workgroups per CU hide each other's stores
@@ -320,10 +290,6 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
         // a long k on a grid of a round or two is split over k below: 128 x 128 tiles give the chunking four times the workgroups
         // for the same partial traffic (S-physics' layer 0, 34 493 x 512 x 8 448: 2.57 ms against 2.67-2.82 with 256 x 256 tiles)
         if (K >= 4096 && tiles_of(S256) <= 512 && J > 128) p.shape = S128;
-    }
-    if (const char *force = getenv("FITGNN_GEMM_SHAPE")) {   // experiments
-        const int f = atoi(force);
-        if (f >= 0 && f <= S64x64 && !(f == S64x512 && !tn)) p.shape = f;
     }
     const int TI = kShape[p.shape].ti, TJ = kShape[p.shape].tj;
     const double slots = 256.0 * kShape[p.shape].per_cu;
@@ -345,10 +311,6 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
         const double t = ceil(ntile * (double)c / slots) * t_tile / (double)c + (double)(c + 1) * (double)I * (double)J * 4.0 / 3.0e12 + 4e-6;
         if (t < 0.92 * best) { best = t; p.nchunks = (int)c; }
     }
-    if (const char *force = getenv("FITGNN_GEMM_CHUNKS")) {   // experiments: a fixed chunk count (clamped to what K allows)
-        const long c = atol(force);
-        p.nchunks = (int)(c <= 1 ? 1 : (c + 7) / 8 * 8);
-    }
     if (p.nchunks > 1) {
         const long per = (K + p.nchunks - 1) / p.nchunks;
         p.chunk_k = (per + kBK - 1) / kBK * kBK;   // (a last chunk may come out empty: it stores zeros)
@@ -360,8 +322,7 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
     p.main_rows = 0; p.rem_tiles_i = 0; p.rem_chunks = 1; p.rem_chunk_k = K;
     const long T = (long)p.tiles_i * p.tiles_j;
     const long full = T / 256, rem = T % 256;
-    if (!akm && kShape[p.shape].per_cu == 1 && p.nchunks == 1 && full >= 1 && rem > 0 && rem <= 96 && K >= 8 * 2 * kBK &&
-        !getenv("FITGNN_GEMM_CHUNKS") && !getenv("FITGNN_GEMM_NO_TAIL")) {
+    if (!akm && kShape[p.shape].per_cu == 1 && p.nchunks == 1 && full >= 1 && rem > 0 && rem <= 96 && K >= 8 * 2 * kBK) {
         const long main_tiles_i = full * 256 / p.tiles_j;
         if (main_tiles_i >= 1 && main_tiles_i < p.tiles_i) {
             p.main_rows = main_tiles_i * TI;
@@ -373,15 +334,15 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
     return p;
 }
 
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool PIPE = false>
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM>
 int launch(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s) {
     using G = Geo<WM, WN, MI, NJ, AKM, BKM>;
     static std::atomic<uint64_t> lds_done{0};
-    if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, PIPE>, G::LDS_BYTES, lds_done)) return rc;
+    if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM>, G::LDS_BYTES, lds_done)) return rc;
     unsigned grid;
     if (p.nchunks > 1) grid = (unsigned)(p.tiles_i * p.tiles_j * ((p.nchunks + 7) / 8 * 8));   // chunk = xcd + 8 * (slot / tiles)
     else grid = (unsigned)((p.tiles_i + 7) / 8 * 8 * p.tiles_j);
-    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, PIPE>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J, K,
+    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J, K,
                        c, ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k);
     return (int)hipGetLastError();
 }
@@ -393,18 +354,10 @@ int launch_shape(const Plan &p, const float *a, long lda, const float *b, long l
     }
     switch (p.shape) {
         case S256x128: return launch<4, 1, 2, 4, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S128:
-            if (getenv("FITGNN_GEMM_DEEP")) return launch<2, 2, 2, 2, AKM, BKM, true>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-            return launch<2, 2, 2, 2, AKM, BKM, false>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S64x128:
-            if (getenv("FITGNN_GEMM_DEEP")) return launch<2, 2, 1, 2, AKM, BKM, true>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-            return launch<2, 2, 1, 2, AKM, BKM, false>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S128x64:
-            if (getenv("FITGNN_GEMM_DEEP")) return launch<4, 1, 1, 2, AKM, BKM, true>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-            return launch<4, 1, 1, 2, AKM, BKM, false>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S64x64:
-            if (getenv("FITGNN_GEMM_DEEP")) return launch<2, 2, 1, 1, AKM, BKM, true>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-            return launch<2, 2, 1, 1, AKM, BKM, false>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        case S128: return launch<2, 2, 2, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        case S64x128: return launch<2, 2, 1, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        case S128x64: return launch<4, 1, 1, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        case S64x64: return launch<2, 2, 1, 1, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
         default: return launch<4, 2, 2, 4, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
     }
 }
@@ -416,6 +369,16 @@ extern "C" size_t fitgnn_gemm_exact_workspace_bytes(int64_t I, int32_t J, int64_
     const Plan p = make_plan((long)I, J, (long)K, a_kmajor != 0, b_kmajor != 0);
     if (p.main_rows > 0) return (size_t)p.rem_chunks * (size_t)(I - p.main_rows) * (size_t)J * sizeof(float);
     return p.nchunks > 1 ? (size_t)p.nchunks * (size_t)I * (size_t)J * sizeof(float) : 0;
+}
+
+extern "C" int fitgnn_gemm_exact_plan(int64_t I, int32_t J, int64_t K, int32_t a_kmajor, int32_t b_kmajor, int32_t *shape, int32_t *nchunks,
+                                      int64_t *main_rows) {
+    if (I <= 0 || J <= 0 || K <= 0 || !shape || !nchunks || !main_rows) return FITGNN_E_BADARG;
+    const Plan p = make_plan((long)I, J, (long)K, a_kmajor != 0, b_kmajor != 0);
+    *shape = p.shape;
+    *nchunks = p.nchunks;
+    *main_rows = p.main_rows;
+    return 0;
 }
 
 extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmajor, const float *b, int64_t ldb, int32_t b_kmajor,

@@ -20,8 +20,6 @@
 
 #include <algorithm>
 
-#include <cstdlib>
-
 #include "common.h"
 #include "fitgnn_hip.h"
 
@@ -1518,8 +1516,7 @@ namespace {
 inline void rows_plan(int32_t n_rows, int32_t *rows_per_range, int32_t *n_ranges) {
     const int want = 8192;
     int per = (n_rows + want - 1) / want;
-    int least = 32;
-    if (const char *e = getenv("FITGNN_ROWS_MIN")) least = atoi(e) > 0 ? atoi(e) : 32;   // experiments
+    const int least = 32;
     if (per < least) per = least;
     *rows_per_range = per;
     *n_ranges = (n_rows + per - 1) / per;

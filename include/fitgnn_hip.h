@@ -333,6 +333,12 @@ int fitgnn_gemm_nt_f32(const float *a, int64_t lda, const float *b, int64_t ldb,
 size_t fitgnn_gemm_exact_workspace_bytes(int64_t I, int32_t J, int64_t K, int32_t a_kmajor, int32_t b_kmajor);
 int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmajor, const float *b, int64_t ldb, int32_t b_kmajor,
                           int64_t I, int32_t J, int64_t K, float *c, int64_t ldc, void *workspace, void *stream);
+/* The launch plan fitgnn_gemm_exact_f32 makes for these extents and forms (host only, no GPU work): the output tile shape
+ * (0 = 256 x 256, 1 = 256 x 128, 2 = 64 x 512, 3 = 128 x 128, 4 = 64 x 128, 5 = 128 x 64, 6 = 64 x 64), the number of k chunks
+ * (1 = no split over k), and the rows [0, main_rows) of the first of two launches whose second one takes the remaining rows
+ * split over k (0 = no such tail launch). */
+int fitgnn_gemm_exact_plan(int64_t I, int32_t J, int64_t K, int32_t a_kmajor, int32_t b_kmajor, int32_t *shape, int32_t *nchunks,
+                           int64_t *main_rows);
 
 /* Pre-split b operand for the tall-GEMM kernels: b [N x K] given by element strides (b[n * stride_n + k * stride_k]; so
  * b = W^T needs no transposed copy) is converted ONCE per call into bf16 hi/lo fragments laid out as the kernel's LDS image,

@@ -1,5 +1,7 @@
 """CPU tier: the C-ABI library loads and exports every symbol include/fitgnn_hip.h declares; host-only
 size queries work; product code refuses CPU tensors (no fallback)."""
+import ctypes
+import glob
 import os
 import re
 
@@ -204,3 +206,43 @@ def test_round4_graph_step_entry_points_check_their_arguments_without_a_gpu():
     n9 = [None] * 9
     assert L.fitgnn_batch_gather(128, *n13, 11, None, 1, 11, 64, 64, 64, 64, *n9, 11, None, None, None, None, None, 0, None) == -1   # NULL arrays
     assert L.fitgnn_batch_gather(128, *n13, 8, None, 1, 11, 64, 64, 64, 64, *n9, 11, None, None, None, None, None, 0, None) == -1    # ld_ax_g < K
+
+
+def _exact_plan(L, I, J, K, akm, bkm):
+    shape, nchunks, main_rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    assert L.fitgnn_gemm_exact_plan(I, J, K, akm, bkm, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows)) == 0
+    return shape.value, nchunks.value, main_rows.value
+
+
+# (I, J, K, a_kmajor, b_kmajor) -> (tile shape, k chunks, rows of the first launch before a tail launch; 0 = none) for the products
+# DESIGN.md section 4 quotes, in the forms they run in: forward x W^T (0, 0), grad_x = dH W (0, 1), grad_W = dH^T x (1, 1).
+# Tile shapes: 0 = 256 x 256, 3 = 128 x 128, 4 = 64 x 128, 5 = 128 x 64, 6 = 64 x 64.
+EXACT_PLANS = {
+    (19717, 512, 512, 0, 0): (4, 1, 0), (19717, 512, 512, 0, 1): (4, 1, 0), (512, 512, 19717, 1, 1): (3, 32, 0),
+    (4861, 512, 512, 0, 0): (6, 1, 0), (4861, 512, 512, 0, 1): (6, 1, 0), (512, 512, 4861, 1, 1): (3, 32, 0),   # a QM9 batch
+    (20625, 512, 512, 0, 0): (4, 1, 0), (20625, 512, 512, 0, 1): (4, 1, 0), (512, 512, 20625, 1, 1): (3, 32, 0),   # a rank's loss rows
+    (20625, 48, 512, 0, 0): (5, 1, 0),                                                                              # ... their head
+    (34493, 512, 8448, 0, 0): (3, 8, 0), (512, 8448, 34493, 1, 1): (3, 16, 0),                                      # S-physics' layer 0
+    (165000, 512, 128, 0, 0): (3, 1, 0), (512, 128, 165000, 1, 1): (3, 120, 0),                                     # the table product
+    (165000, 512, 512, 0, 0): (0, 1, 163840), (165000, 512, 512, 0, 1): (0, 1, 163840),                            # 5 rounds + a tail
+    (90549, 512, 512, 0, 0): (0, 1, 0),
+}
+
+
+def test_exact_gemm_plans_of_the_configurations():
+    """make_plan (csrc/gemm_f32.hip) through fitgnn_gemm_exact_plan: the tile shape, k split and tail launch of the measured shapes."""
+    L = _lib.lib()
+    got = {dims: _exact_plan(L, *dims) for dims in EXACT_PLANS}
+    assert got == EXACT_PLANS
+    sh, nc, mr = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    assert L.fitgnn_gemm_exact_plan(0, 8, 8, 0, 0, ctypes.byref(sh), ctypes.byref(nc), ctypes.byref(mr)) == -1
+    assert L.fitgnn_gemm_exact_plan(8, 8, 8, 0, 0, None, None, None) == -1
+
+
+def test_library_sources_do_not_read_the_environment():
+    """What the library computes and how it launches depends on its arguments alone: no getenv in its sources."""
+    files = [f for d in ("fit-gnn_amd/csrc", "include") for f in glob.glob(os.path.join(ROOT, d, "**", "*"), recursive=True)
+             if f.endswith((".hip", ".h", ".hpp", ".c", ".cpp", ".cc"))]
+    assert len(files) >= 15
+    hits = [f"{os.path.relpath(f, ROOT)}:{n}" for f in files for n, line in enumerate(open(f), 1) if re.search(r"getenv\s*\(", line)]
+    assert not hits, hits

@@ -1,5 +1,7 @@
 """GPU tier: CSR SpMM / gcn_norm / fused epilogue kernels through the C ABI vs the CPU oracle.
 Tolerance: 1e-4 relative fp32 (BASELINE.json north_star)."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -702,28 +704,40 @@ def test_exact_fp32_gemm_matches_f64(mods, form, dims):
     assert float(ops.gemm_exact(torch.zeros_like(a), b, form).abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("form,dims", [("nt", (4861, 512, 512)), ("nn", (19717, 512, 512)), ("nt", (3000, 260, 100)), ("nn", (700, 96, 132))])
-def test_exact_fp32_gemm_tile_shapes_give_the_same_bits(mods, form, dims, monkeypatch):
-    """Without a k split every output element is ONE MFMA chain over k in ascending order whatever tile it sits in: the 256 x 256,
-    128 x 128 and 64 x 128 tile shapes (csrc/gemm_f32.hip: make_plan takes the smaller ones for grids under a round) give
-    bit-identical products."""
+def _exact_plan(L, I, J, K, akm, bkm):
+    """(tile shape, k chunks, first rows before a tail launch) of the plan fitgnn_gemm_exact_f32 makes (fitgnn_gemm_exact_plan)."""
+    shape, nchunks, main_rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    assert L.fitgnn_gemm_exact_plan(I, J, K, akm, bkm, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows)) == 0
+    return shape.value, nchunks.value, main_rows.value
+
+
+# (rows, columns) of a slice of a 30 000 x 512 product -> the tile shape its own plan takes (0 = 256 x 256, 3 = 128 x 128,
+# 4 = 64 x 128, 6 = 64 x 64); per k, as make_plan weighs 128 x 128 tiles higher for a short k
+_SHORT_K_SLICES = {(30000, 512): 0, (7000, 500): 3, (20625, 512): 3, (3000, 512): 4, (19717, 512): 4, (4861, 512): 6, (1000, 260): 6}
+TILE_SHAPE_SLICES = {100: _SHORT_K_SLICES, 132: _SHORT_K_SLICES,
+                     512: {(30000, 512): 0, (7000, 500): 4, (19717, 512): 4, (4861, 512): 6, (1000, 260): 6}}
+
+
+@pytest.mark.parametrize("form,dims", [("nt", (30000, 512, 100)), ("nn", (30000, 132, 512)), ("nt", (30000, 512, 512)), ("nn", (30000, 512, 512))])
+def test_exact_fp32_gemm_tile_shapes_give_the_same_bits(mods, form, dims):
+    """Without a k split every output element is ONE MFMA chain over k in ascending order whatever tile it sits in, and the rows
+    and columns of a product are independent: a slice of the operands, multiplied with the tile shape its own plan takes, gives
+    exactly that slice of the whole product.  The slices cover the 256 x 256, 128 x 128, 64 x 128 and 64 x 64 tile shapes
+    (csrc/gemm_f32.hip: make_plan takes the smaller ones for grids under a round); no plan here splits k or has a tail launch."""
     _lib, csr, ops, orc, gorc = mods
+    L = _lib.lib()
+    (I, J, K), bkm = (dims if form == "nt" else (dims[0], dims[2], dims[1])), int(form == "nn")
     g = torch.Generator().manual_seed(sum(dims))
-    if form == "nt":
-        I, J, K = dims
-        a, b = torch.randn(I, K, generator=g).cuda(), torch.randn(J, K, generator=g).cuda()
-    else:
-        I, K, J = dims
-        a, b = torch.randn(I, K, generator=g).cuda(), torch.randn(K, J, generator=g).cuda()
-    outs = []
-    for shape in ("0", "3", "4", "6"):   # S256, S128, S64x128, S64x64
-        monkeypatch.setenv("FITGNN_GEMM_SHAPE", shape)
-        monkeypatch.setenv("FITGNN_GEMM_NO_TAIL", "1")
-        outs.append(ops.gemm_exact(a, b, form))
-    monkeypatch.delenv("FITGNN_GEMM_SHAPE")
-    monkeypatch.delenv("FITGNN_GEMM_NO_TAIL")
-    assert all(torch.equal(outs[0], o) for o in outs[1:])
-    assert torch.equal(outs[0], ops.gemm_exact(a, b, form))   # (none of these shapes has a k split or a tail launch in its default plan)
+    a = torch.randn(I, K, generator=g).cuda()
+    b = torch.randn(J, K, generator=g).cuda() if form == "nt" else torch.randn(K, J, generator=g).cuda()
+    assert _exact_plan(L, I, J, K, 0, bkm) == (0, 1, 0)
+    whole = ops.gemm_exact(a, b, form)
+    slices = TILE_SHAPE_SLICES[K]
+    for (m, n), shape in slices.items():
+        assert _exact_plan(L, m, n, K, 0, bkm) == (shape, 1, 0), (m, n)
+        got = ops.gemm_exact(a[:m], b[:n] if form == "nt" else b[:, :n], form)
+        assert torch.equal(got, whole[:m, :n]), (form, K, m, n, shape)
+    assert set(slices.values()) == ({0, 3, 4, 6} if K <= 256 else {0, 4, 6})   # (at k = 512, 128 x 128 is never the cheapest)
 
 
 def test_exact_fp32_gemm_is_the_default_policy_and_differentiates(mods):
