@@ -26,15 +26,16 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // a_src[i] = h_i . att_src,  a_dst[i] = h_i . att_dst          (one wave per row)
+// vec: 16-byte loads (C, ldh multiples of 4 and h, att_src, att_dst 16-byte aligned: decided by the host)
 __global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict__ h, int64_t ldh, int32_t n, int32_t C,
                                                          const float *__restrict__ att_src, const float *__restrict__ att_dst,
-                                                         float *__restrict__ a_src, float *__restrict__ a_dst) {
+                                                         float *__restrict__ a_src, float *__restrict__ a_dst, bool vec) {
     const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (row >= n) return;
     const float *hr = h + (int64_t)row * ldh;
     float s = 0.f, d = 0.f;
-    if ((C & 3) == 0 && (ldh & 3) == 0) {
+    if (vec) {
         for (int c = lane * 4; c < C; c += 256) {
             const float4 v = *reinterpret_cast<const float4 *>(hr + c);
             const float4 as = *reinterpret_cast<const float4 *>(att_src + c);
@@ -285,8 +286,9 @@ extern "C" int fitgnn_gat_scores_f32(const float *h, int64_t ldh, int32_t n, int
     if (n < 0 || C < 0 || ldh < C) return FITGNN_E_BADARG;
     if (n == 0) return 0;
     if (!h || !att_src || !att_dst || !a_src || !a_dst) return FITGNN_E_BADARG;
+    const bool vec = (C % 4 == 0) && (ldh % 4 == 0) && ((((uintptr_t)h | (uintptr_t)att_src | (uintptr_t)att_dst) % 16) == 0);
     hipLaunchKernelGGL(gat_scores_kernel, wave_grid(n), dim3(256), 0, (hipStream_t)stream, h, ldh, n, C, att_src, att_dst, a_src,
-                       a_dst);
+                       a_dst, vec);
     return (int)hipGetLastError();
 }
 

@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 import torch
+from graph_fixtures import star_blocks
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
@@ -217,27 +218,6 @@ def test_head_backward_folded_into_epilogue_kernel(mods, H, C):
     assert rel_err(dZ.cpu(), dZ_ref.cpu()) < 1e-5
     assert rel_err(db.cpu(), db_ref.cpu()) < 1e-4
     assert rel_err(dWl.cpu(), (dy.double().t() @ out.double()).float()) < 1e-5
-
-
-def star_blocks(sizes, centres, seed, extra=0.02):
-    """Block-diagonal batch of star-shaped subgraphs: in every block the first `centres` rows link to all the others
-    (--extra_node subgraphs, utils.py:235-239), plus a few random leaf -- leaf edges."""
-    rng = np.random.default_rng(seed)
-    src, dst, off = [], [], 0
-    for s in sizes:
-        c = min(centres, max(s - 1, 0))
-        for h in range(c):
-            leaves = np.arange(c, s)
-            src += [off + h] * len(leaves) + (off + leaves).tolist()
-            dst += (off + leaves).tolist() + [off + h] * len(leaves)
-        m = int(extra * s * s)
-        if m and s > 2:
-            a, b = rng.integers(0, s, size=m), rng.integers(0, s, size=m)
-            k = a != b
-            src += (off + a[k]).tolist() + (off + b[k]).tolist()
-            dst += (off + b[k]).tolist() + (off + a[k]).tolist()
-        off += s
-    return torch.tensor(np.unique(np.array([src, dst]), axis=1), dtype=torch.long), off
 
 
 @pytest.mark.parametrize("H", [512, 256, 100])
