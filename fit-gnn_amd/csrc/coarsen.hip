@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "fitgnn_hip.h"
+#include "match_arith.h"
 #include "scan.h"
 #include "variation_cost.h"
 
@@ -942,7 +943,7 @@ __global__ void assign_sets_kernel(const int32_t *__restrict__ sel_off, const in
     if (s >= sel_count[0]) return;
     const int o = sel_off[s], nc = sel_off[s + 1] - o;
     const int32_t r = sel_mem[o];  // sets are sorted: the minimum member keeps the row (:239)
-    const double v = 1.0 / sqrt((double)nc);
+    const double v = fitgnn_match::set_cval(nc);
     for (int t = lane; t < nc; t += 64) { root[sel_mem[o + t]] = r; cval[sel_mem[o + t]] = v; }
 }
 __global__ void survivor_flag_kernel(int32_t N, const int32_t *__restrict__ root, int32_t *__restrict__ flag) {

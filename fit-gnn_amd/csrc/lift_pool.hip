@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "fitgnn_hip.h"
+#include "match_arith.h"
 
 namespace {
 
@@ -44,9 +45,8 @@ __global__ void lift_stage1_kernel(int32_t N, const int32_t *__restrict__ rowptr
     const int v = col[e];
     const int b = assign[v];
     if (assign[u] == b) { key[e] = kInvalid; val[e] = 0.0; return; }  // feeds only the diagonal (zero_diag)
-    const double pv = cval[v] * (1.0 / cval[v]);
     key[e] = (uint64_t)u * (uint64_t)n + (uint64_t)b;
-    val[e] = (w ? w[e] : 1.0) * pv;
+    val[e] = fitgnn_match::lift_mul(w ? w[e] : 1.0, fitgnn_match::lift_p(cval[v]));
 }
 
 __global__ void run_head_kernel(const uint64_t *__restrict__ key, int32_t m, int32_t *__restrict__ flag) {
@@ -71,13 +71,12 @@ __global__ void run_sum_kernel(const uint64_t *__restrict__ key, const double *_
     const bool head = k != kInvalid && (i == 0 || key[i - 1] != k);
     if (!head) return;
     double s = val[i];
-    for (int j = i + 1; j < m && key[j] == k; ++j) s = s + val[j];
+    for (int j = i + 1; j < m && key[j] == k; ++j) s = fitgnn_match::lift_add(s, val[j]);
     const int r = run_idx[i];
     if (MODE == 1) {
         const int u = (int)(k / (uint64_t)n), b = (int)(k % (uint64_t)n);
-        const double pu = cval[u] * (1.0 / cval[u]);
         okey[r] = (uint64_t)assign[u] * (uint64_t)n + (uint64_t)b;
-        oval[r] = s * pu;
+        oval[r] = fitgnn_match::lift_mul(s, fitgnn_match::lift_p(cval[u]));
     } else {
         okey[r] = k;
         oval[r] = s;
@@ -115,7 +114,7 @@ __global__ void symmetrise_kernel(const uint64_t *__restrict__ ukey, const doubl
     const uint64_t tk = b * (uint64_t)n + a;
     const int p = lower_bound_u64(ukey, cnt, tk);
     const double t = (p < cnt && ukey[p] == tk) ? usum[p] : 0.0;
-    const double v = (usum[i] + t) / 2.0;
+    const double v = fitgnn_match::lift_sym(usum[i], t);
     sym[i] = v;
     keep[i] = v != 0.0 ? 1 : 0;
 }

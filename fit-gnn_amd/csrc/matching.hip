@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "fitgnn_hip.h"
+#include "match_arith.h"
 #include "scan.h"
 
 namespace {
@@ -91,10 +92,8 @@ __global__ void heavy_edge_kernel(const int32_t *__restrict__ e_src, const int32
                                   int64_t M, const unsigned long long *__restrict__ wmax_bits, float *__restrict__ prox) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= M) return;
-    const double wi = __longlong_as_double((long long)wmax_bits[e_src[e]]) + 1e-5;
-    const double wj = __longlong_as_double((long long)wmax_bits[e_dst[e]]) + 1e-5;
-    const double m = wj > wi ? wj : wi;  // Python's max([wi, wj]): the first unless the second is larger
-    prox[e] = (float)(e_w[e] / m);
+    prox[e] = fitgnn_match::heavy_edge_prox(e_w[e], __longlong_as_double((long long)wmax_bits[e_src[e]]),
+                                            __longlong_as_double((long long)wmax_bits[e_dst[e]]));
 }
 
 __device__ __forceinline__ double group_sum(double v) {
@@ -116,11 +115,7 @@ __global__ void jc_proximity_kernel(const int32_t *__restrict__ e_src, const int
     const int k = threadIdx.x % kGroup;
     if (e >= M) return;  // whole groups leave together (256 / kGroup groups per block)
     double v = __builtin_inf();
-    if (k < K) {
-        const double d = X[(int64_t)e_src[e] * ldx + k] - X[(int64_t)e_dst[e] * ldx + k];
-        const double d2 = d * d;
-        v = 1.0 / (d2 > 1e-6 ? d2 : 1e-6);
-    }
+    if (k < K) v = fitgnn_match::jc_term(X[(int64_t)e_src[e] * ldx + k], X[(int64_t)e_dst[e] * ldx + k]);
     v = group_min(v);
     if (k == 0) prox[e] = (float)v;
 }
@@ -183,13 +178,8 @@ __global__ void jacobi_step_kernel(const int32_t *__restrict__ rowptr, const int
     const int k = threadIdx.x % kGroup;
     if (i >= N || k >= K) return;
     double acc = 0.0;
-    for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) acc += (w ? w[p] : 1.0) * x[(int64_t)col[p] * K + k];
-    const float degf = (float)dw[i];
-    // f32 reciprocal computed in f64 and rounded once: the correctly rounded float32 1/deg
-    const double dinv = degf == 0.0f ? 0.0 : (double)(float)(1.0 / (double)degf);
-    const double xi = x[i * K + k];
-    const double mx = dinv * (acc + ((double)degf - dw[i]) * xi);
-    y[i * K + k] = 0.5 * xi + 0.5 * mx;
+    for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) acc = fitgnn_match::jacobi_acc(acc, w ? w[p] : 1.0, x[(int64_t)col[p] * K + k]);
+    y[i * K + k] = fitgnn_match::jacobi_update(acc, x[i * K + k], dw[i]);
 }
 
 // One Gauss-Seidel sweep x <- -(D + L_lower)^-1 L_upper x (:822-832) on L = diag(dw) - W (zero diagonal of W):
@@ -229,15 +219,7 @@ __global__ __launch_bounds__(64) void gauss_seidel_kernel(const int32_t *__restr
 __global__ void match_keys_kernel(const double *__restrict__ weight, int64_t M, uint64_t *__restrict__ keys, int32_t *__restrict__ ids) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= M) return;
-    const double v = -weight[e];
-    uint64_t b;
-    if (v != v) {
-        b = ~0ull;
-    } else {
-        b = (uint64_t)__double_as_longlong(v == 0.0 ? 0.0 : v);
-        b = (b >> 63) ? ~b : (b | (1ull << 63));
-    }
-    keys[e] = b;
+    keys[e] = fitgnn_match::match_sort_key(weight[e]);
     ids[e] = (int32_t)e;
 }
 __global__ void node_comp_kernel(int32_t n_comp, const int32_t *__restrict__ comp_off, int32_t *__restrict__ comp_of) {

@@ -16,6 +16,9 @@ ptr = ctypes.c_void_p
 EPI_BIAS, EPI_ELU, EPI_DROPOUT, EPI_SEED_DEVICE = 1, 2, 4, 8
 SPMM_GATHER = 0x100
 MAX_K = 16
+MATCH_HEAVY_EDGE, MATCH_ALGEBRAIC_JC = 0, 1
+MATCH_SMALL_MAX_NODES, MATCH_SMALL_MAX_NNZ, MATCH_SMALL_MAX_K, MATCH_SMALL_LDS_BUDGET = 128, 1024, 12, 65536
+MATCH_DONE, MATCH_TOO_BIG, MATCH_BAD_INPUT = 1, 2, 3
 QUALITY_MAX_K = 64
 
 # name -> (restype, argtypes); mirrors include/fitgnn_hip.h one to one
@@ -158,6 +161,9 @@ SIGNATURES = {
     "fitgnn_greedy_matching_workspace_bytes": (c_size, [c_i32, c_i64, c_i32]),
     "fitgnn_greedy_matching": (ctypes.c_int, [ptr, ptr, ptr, c_i32, ptr, ptr, ptr, c_i64, ptr, c_i32, ptr, ptr, c_i64, ptr, ptr, ptr,
                                               ptr, ptr, ptr, c_size, ptr]),
+    "fitgnn_match_small_lds_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32]),
+    "fitgnn_match_small": (ctypes.c_int, [c_i32, ptr, ptr, ptr, ptr, c_i32, c_i32, ctypes.c_double, c_i32, c_i32, ctypes.c_double, ptr,
+                                          c_i64, ptr, c_i32, c_i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     "fitgnn_pool_rows_workspace_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_pool_rows_f32": (ctypes.c_int, [ptr, ptr, c_i32, c_i32, ptr, c_i64, c_i32, ptr, c_i64, ptr, ptr, c_size, ptr]),
     "fitgnn_coarse_laplacian_workspace_bytes": (c_size, [c_i32, c_i64, c_i32]),

@@ -547,6 +547,11 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
     'variation_edges'} (the matching methods with algorithm='greedy'): returns (C, Gc, mapping_dict_list).
     The matching methods break ties by edge index; algebraic_JC / affinity_GS draw from np.random exactly
     where the reference does, so a caller who seeds numpy gets the reference's test vectors."""
+    return _coarsen(G, K, r, max_levels, method, algorithm, Uk, lk, max_level_r, device, spectral)[:3]
+
+
+def _coarsen(G, K, r, max_levels, method, algorithm, Uk, lk, max_level_r, device, spectral):
+    """coarsen()'s body: (C, Gc, mapping_dict_list, applied levels)."""
     check_method(method, algorithm)
     matching = method in MATCHING_METHODS
     if not hasattr(G, "W"):
@@ -563,6 +568,7 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
     Gc = G
     mapping_dict_list = []
     B = iC = None
+    applied = 0
     for level in range(1, max_levels + 1):
         G = Gc
         r_cur = np.clip(1 - n_target / n, 0.0, max_level_r)
@@ -592,6 +598,7 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
             coords = (iC.power(2)).dot(G.coords)  # coarsen_vector :190-191 (plot coordinates only)
         Gc = Graph(Wc, coords=coords)
         n = Gc.N
+        applied += 1
         if matching:
             md = {i: i for i in range(N)}  # :168: the matching methods keep the identity dict at every level
         else:
@@ -604,7 +611,7 @@ def coarsen(G, K=10, r=0.5, max_levels=10, method="variation_neighborhood", algo
             break
     a = assign_tot.cpu().numpy()
     C = CoarseningMatrix(sp.csc_matrix((cval_tot.cpu().numpy(), (a, np.arange(N))), shape=(int(a.max()) + 1 if N else 0, N)))
-    return C, Gc, mapping_dict_list
+    return C, Gc, mapping_dict_list, applied
 
 
 # ---------------------------------------------------------------------------------------------
@@ -614,8 +621,10 @@ class BatchCoarsening:
     """Result of coarsen_batch: `assign` int64[N] (global cluster id of every node; a component's clusters are a
     contiguous id range in ascending order of their minimum member, i.e. per-component id = assign - cluster_off[c]),
     `cval` float64[N] (the non-zero of C in that node's column), `comp_off` / `cluster_off` int64[n_comp+1],
-    `Wc` scipy csr (block-diagonal coarse adjacency, global cluster ids), `levels` per-component level count."""
-    __slots__ = ("assign", "cval", "comp_off", "cluster_off", "Wc", "levels", "n_clusters", "_dev")
+    `Wc` scipy csr (block-diagonal coarse adjacency, global cluster ids), `levels` per-component level count, `fallback`
+    int64 ids of the components coarsen_in_order handed to coarsen() (over the whole-component kernel's LDS budget; empty
+    for coarsen_batch)."""
+    __slots__ = ("assign", "cval", "comp_off", "cluster_off", "Wc", "levels", "n_clusters", "fallback", "_dev")
 
     def C(self):
         N = len(self.assign)
@@ -792,7 +801,215 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
     out.cval = cval_tot.cpu().numpy()
     out.comp_off, out.cluster_off, out.Wc, out.levels = comp_off, off, G.W, levels
     out.n_clusters = int(off[-1])
+    out.fallback = np.zeros(0, dtype=np.int64)
     out._dev = (assign_tot, cval_tot)
+    return out
+
+
+class DrawPool:
+    """Gaussians of the global np.random stream drawn ahead in chunks, handed out in order, and given back: sync() leaves the
+    global state exactly where it would be had only the consumed draws been taken.  Exact because the legacy RandomState
+    keeps its cached second Gaussian across calls: randn(a) followed by randn(b) draws what randn(a + b) draws and ends in
+    the same state."""
+
+    ADVANCE = 1 << 20   # draws per randn call while advancing the state (bounds the host memory of a long chain)
+
+    def __init__(self, chunk=1 << 22):
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        self.chunk = int(chunk)
+        self.rebase()
+
+    def rebase(self):
+        """Start from the current global state (nothing drawn ahead, nothing consumed)."""
+        self._base = np.random.get_state()
+        self._buf = np.empty(0)
+        self._used = 0
+        self.consumed = 0
+
+    def ensure(self, need):
+        """The unconsumed draws, at least `need` of them (drawing chunks ahead as needed)."""
+        rest = self._buf[self._used:]
+        if rest.size < need:
+            rest = np.concatenate([rest, np.random.randn(max(self.chunk, int(need) - rest.size))])
+            self._buf, self._used = rest, 0
+        return rest
+
+    def consume(self, k):
+        k = int(k)
+        if k < 0 or self._used + k > self._buf.size:
+            raise ValueError(f"consume({k}): only {self._buf.size - self._used} draws are available")
+        self._used += k
+        self.consumed += k
+
+    def sync(self):
+        """Put the global state at base + consumed and rebase there."""
+        np.random.set_state(self._base)
+        left = self.consumed
+        while left > 0:
+            step = min(left, self.ADVANCE)
+            np.random.randn(step)
+            left -= step
+        self.rebase()
+
+
+IN_ORDER_METHODS = ("heavy_edge", "algebraic_JC")
+
+
+def _small_fits(n, nnz, method, K):
+    """Components the whole-component kernel takes (fitgnn_match_small's LDS budget)."""
+    ok = (n <= _lib.MATCH_SMALL_MAX_NODES) & (nnz <= _lib.MATCH_SMALL_MAX_NNZ)
+    if method == "algebraic_JC" and not (1 <= K <= _lib.MATCH_SMALL_MAX_K):
+        ok[:] = False
+    return ok
+
+
+def coarsen_in_order(W, comp_off, r=0.5, K=10, max_levels=10, method="algebraic_JC", max_level_r=0.99, device="cuda",
+                     chunk=1 << 22):
+    """coarsen() (method heavy_edge or algebraic_JC) on every component comp_off[c]:comp_off[c+1] of the block-diagonal
+    symmetric adjacency W, one after another in component order -- the reference's per-component loop (utils.py:163-182,
+    :398-411), including its np.random draw order: per component, assign / cval / Wc / levels and the global np.random state
+    afterwards are bit-identical to calling coarsen() on each component of more than one node in turn.
+
+    Components within the LDS budget (FITGNN_MATCH_SMALL_MAX_NODES nodes, _MAX_NNZ stored entries) are coarsened whole on
+    the device by fitgnn_match_small: algebraic_JC as one chain that reads the draws from a host pool of `chunk` Gaussians
+    (DrawPool), heavy_edge as one workgroup per component.  A component over the budget runs coarsen() at its place in the
+    order, with the global state at exactly that position.  Returns a BatchCoarsening (levels: applied levels)."""
+    if method not in IN_ORDER_METHODS:
+        raise NotImplementedError(f"coarsen_in_order: method '{method}' is not supported; supported: {', '.join(IN_ORDER_METHODS)}")
+    L = _lib.lib()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.FitgnnError("coarsen_in_order needs the MI355X (no CPU fallback)")
+    st = _lib.stream_ptr(dev)
+    W = sp.csr_matrix(W).astype(np.float64)
+    W.sum_duplicates()
+    W.eliminate_zeros()
+    W.sort_indices()
+    comp_off = np.asarray(comp_off, dtype=np.int64)
+    n_comp, N0 = len(comp_off) - 1, int(comp_off[-1])
+    if W.shape != (N0, N0):
+        raise ValueError(f"W is {W.shape}, comp_off spans {N0} nodes")
+    if W.diagonal().any():
+        raise ValueError("the matching methods need a graph without self-loops (the reference would match (i, i))")
+    if (W != W.T).nnz:
+        raise ValueError("coarsen_in_order needs an exactly symmetric W")
+    coo = W.tocoo()
+    comp_of = np.repeat(np.arange(n_comp), np.diff(comp_off))
+    if N0 and (comp_of[coo.row] != comp_of[coo.col]).any():
+        raise ValueError("W couples two components: it must be block-diagonal over comp_off")
+    r = float(np.clip(r, 0, 0.999))
+    size = np.diff(comp_off)
+    nnz = W.indptr[comp_off[1:]] - W.indptr[comp_off[:-1]]
+    mcode = _lib.MATCH_ALGEBRAIC_JC if method == "algebraic_JC" else _lib.MATCH_HEAVY_EDGE
+    fits = _small_fits(size, nnz, method, K)
+    # device outputs at the input's node / entry slots (fitgnn_match_small's layout)
+    rowptr, col, w = _dev(W.indptr, torch.int32, dev), _dev(W.indices, torch.int32, dev), _dev(W.data, torch.float64, dev)
+    co_d = _dev(comp_off, torch.int32, dev)
+    assign = torch.empty(max(N0, 1), dtype=torch.int32, device=dev)
+    cval = torch.empty(max(N0, 1), dtype=torch.float64, device=dev)
+    n_out = torch.zeros(max(n_comp, 1), dtype=torch.int32, device=dev)
+    levels = torch.zeros(max(n_comp, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(max(n_comp, 1), dtype=torch.int32, device=dev)
+    wc_rowptr = torch.zeros(N0 + n_comp + 1, dtype=torch.int32, device=dev)
+    wc_col = torch.empty(max(int(W.nnz), 1), dtype=torch.int32, device=dev)
+    wc_w = torch.empty(max(int(W.nnz), 1), dtype=torch.float64, device=dev)
+    cap_n = int(max(size[fits].max(initial=1), 1))
+    cap_z = int(nnz[fits].max(initial=0))
+    fallback = {}                                           # component -> (C, Gc, applied levels) from coarsen()
+
+    def run_coarsen(c):
+        b, e = int(comp_off[c]), int(comp_off[c + 1])
+        C, Gc, _, lv = _coarsen(Graph(W[b:e, b:e]), K, r, max_levels, method, "greedy", None, None, max_level_r, dev, "arpack")
+        fallback[c] = (sp.csc_matrix(C), Gc.W, lv)
+
+    def launch(c0, c1, draws=None, sqrt_n=None, progress=None):
+        nd = 0 if draws is None else int(draws.numel())
+        _lib.check(L.fitgnn_match_small(mcode, _lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(co_d), int(c0), int(c1), r,
+                                        int(K), int(max_levels), float(max_level_r), _lib.dptr(draws), nd, _lib.dptr(sqrt_n), cap_n,
+                                        cap_z, _lib.dptr(assign), _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(levels),
+                                        _lib.dptr(status), _lib.dptr(wc_rowptr), _lib.dptr(wc_col), _lib.dptr(wc_w),
+                                        _lib.dptr(progress), st), "match_small")
+
+    if method == "heavy_edge":
+        if fits.any():
+            launch(0, n_comp)
+        for c in np.nonzero(~fits & (size > 1))[0]:
+            run_coarsen(int(c))
+    else:
+        pool = DrawPool(chunk)
+        sqrt_n = _dev(np.sqrt(np.arange(_lib.MATCH_SMALL_MAX_NODES + 1)), torch.float64, dev)
+        progress = torch.zeros(2, dtype=torch.int64, device=dev)
+        c = 0
+        while c < n_comp:
+            if size[c] <= 1:                                # the reference coarsens components of more than one node
+                c += 1
+                continue
+            if not fits[c]:                                 # coarsen() at its place in the draw order
+                pool.sync()
+                run_coarsen(c)
+                pool.rebase()
+                c += 1
+                continue
+            c1 = c
+            while c1 < n_comp and fits[c1]:
+                c1 += 1
+            draws = _dev(pool.ensure(K * int(size[c]) * max_levels), torch.float64, dev)
+            launch(c, c1, draws, sqrt_n, progress)
+            done, used = (int(v) for v in progress.cpu().numpy())
+            if done <= c and used == 0:
+                raise _lib.FitgnnError(f"match_small made no progress at component {c} (status {int(status[c].item())})")
+            pool.consume(used)
+            c = done
+        pool.sync()
+    st_h = status[:n_comp].cpu().numpy()
+    bad = np.nonzero(st_h == _lib.MATCH_BAD_INPUT)[0]
+    if bad.size:
+        raise ValueError(f"coarsen_in_order: component {int(bad[0])} is malformed (unsorted, out-of-component or diagonal entries)")
+    todo = fits & (size > 1) & (st_h != _lib.MATCH_DONE)
+    if todo.any():
+        raise _lib.FitgnnError(f"match_small left {int(todo.sum())} components undone (first: {int(np.nonzero(todo)[0][0])})")
+
+    # ---- assemble the block-diagonal result: device components from their slots, coarsen() ones from C / Gc ----
+    n_c = np.where(size > 1, n_out[:n_comp].cpu().numpy(), size).astype(np.int64)
+    lv = np.where(size > 1, levels[:n_comp].cpu().numpy(), 0).astype(np.int64)
+    a_loc = assign[:N0].cpu().numpy().astype(np.int64)
+    cv = cval[:N0].cpu().numpy()
+    rp_h, col_h, w_h = wc_rowptr.cpu().numpy().astype(np.int64), wc_col.cpu().numpy(), wc_w.cpu().numpy()
+    p_in = W.indptr[comp_off[:-1]].astype(np.int64)
+    single = size <= 1                                      # one node, no level: identity, no entries
+    a_loc[np.repeat(single, size)] = 0
+    cv[np.repeat(single, size)] = 1.0
+    rp_h[(comp_off[:-1] + np.arange(n_comp))[single]] = 0
+    rp_h[(comp_off[:-1] + np.arange(n_comp) + size)[single]] = 0
+    for c, (C, Wc, lvc) in fallback.items():
+        b, e = int(comp_off[c]), int(comp_off[c + 1])
+        a_loc[b:e], cv[b:e] = C.indices, C.data
+        n_c[c], lv[c] = C.shape[0], lvc
+        Wc = sp.csr_matrix(Wc)
+        rp_h[b + c: b + c + Wc.shape[0] + 1] = Wc.indptr
+        col_h[p_in[c]: p_in[c] + Wc.nnz], w_h[p_in[c]: p_in[c] + Wc.nnz] = Wc.indices, Wc.data
+    cluster_off = np.zeros(n_comp + 1, dtype=np.int64)
+    np.cumsum(n_c, out=cluster_off[1:])
+    rows_base = comp_off[:-1] + np.arange(n_comp)          # component c's local rowptr starts here
+    row_comp = np.repeat(np.arange(n_comp), n_c)
+    row_local = np.arange(int(cluster_off[-1])) - cluster_off[row_comp]
+    r0 = rp_h[rows_base[row_comp] + row_local]
+    r1 = rp_h[rows_base[row_comp] + row_local + 1]
+    lens = r1 - r0
+    indptr = np.zeros(int(cluster_off[-1]) + 1, dtype=np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    ent_row = np.repeat(np.arange(int(cluster_off[-1])), lens)
+    src = p_in[row_comp[ent_row]] + r0[ent_row] + (np.arange(int(indptr[-1])) - indptr[ent_row])
+    n_cl = int(cluster_off[-1])
+    Wc_all = sp.csr_matrix((w_h[src], col_h[src].astype(np.int64) + cluster_off[row_comp[ent_row]], indptr), shape=(n_cl, n_cl))
+    out = BatchCoarsening()
+    out.assign = a_loc + np.repeat(cluster_off[:-1], size)
+    out.cval = cv
+    out.comp_off, out.cluster_off, out.Wc, out.levels = comp_off, cluster_off, Wc_all, lv
+    out.n_clusters = n_cl
+    out.fallback = np.array(sorted(fallback), dtype=np.int64)
+    out._dev = (torch.as_tensor(out.assign.astype(np.int32)).to(dev), torch.as_tensor(out.cval).to(dev))
     return out
 
 

@@ -89,6 +89,20 @@ def synthetic_graph_classes(n_graphs, seed=0, n_features=3, n_classes=2, mean_no
     return dict(node_ptr=node_ptr, edge_index=ei, x=np.concatenate(xs), y=cls.reshape(-1, 1).astype(np.float32))
 
 
+GRAPH_MATCHING_METHODS = ("heavy_edge", "algebraic_JC", "variation_edges")
+
+
+def _require_connected(W, node_ptr, method):
+    """The graph-level matching path coarsens every graph as ONE component (the reference coarsens a graph's components one
+    by one, largest first: utils.py:378-379); refuse a disconnected graph up front."""
+    size = np.diff(node_ptr)
+    _, lab = sp.csgraph.connected_components(W, directed=False)
+    graph_of = np.repeat(np.arange(len(size)), size)
+    bad = np.nonzero(lab != lab[node_ptr[graph_of]])[0]     # a node outside its graph's first node's component
+    if bad.size:
+        raise ValueError(f"GraphSet(method='{method}'): every graph must be connected; graph {int(graph_of[bad[0]])} is not")
+
+
 class GraphSet:
     """All graphs of a graph-level dataset, coarsened and assembled once, resident on the device.
 
@@ -98,14 +112,26 @@ class GraphSet:
     quirk iii); `gs_core` marks the true own nodes.  network.*_graph_gs pools x[mask] per graph."""
 
     def __init__(self, mol, ratio=0.5, extra_node=False, device="cuda", spectral="dense", reference_mask=True,
-                 cluster_node=False):
+                 cluster_node=False, method="variation_neighborhoods"):
         dev = torch.device(device)
         node_ptr, ei = np.asarray(mol["node_ptr"]), np.asarray(mol["edge_index"])
         N, G = int(node_ptr[-1]), len(node_ptr) - 1
-        self.n_graphs, self.node_ptr = G, node_ptr
+        self.n_graphs, self.node_ptr, self.method = G, node_ptr, method
         W = sp.csr_matrix((np.ones(ei.shape[1]), (ei[0], ei[1])), shape=(N, N))
         # main.py:370-377 passes Loukas r = 1 - coarsening_ratio; every graph is one connected component here
-        self.co = coarsening.coarsen_batch(W, node_ptr, r=1 - ratio, device=dev, spectral=spectral)
+        if method == "variation_neighborhoods":
+            self.co = coarsening.coarsen_batch(W, node_ptr, r=1 - ratio, device=dev, spectral=spectral)
+        elif method in GRAPH_MATCHING_METHODS:
+            _require_connected(W, node_ptr, method)
+            if method == "algebraic_JC":   # draws per graph and level: graph order is the reference's draw order
+                self.co = coarsening.coarsen_in_order(W, node_ptr, r=1 - ratio, method=method, device=dev)
+            elif method == "heavy_edge":
+                self.co = coarsening.coarsen_batch(W, node_ptr, r=1 - ratio, device=dev, method=method)
+            else:              # variation_edges: the same level-1 spectral prelude as the default method (dense: reproducible)
+                self.co = coarsening.coarsen_batch(W, node_ptr, r=1 - ratio, device=dev, method=method, spectral=spectral)
+        else:
+            raise NotImplementedError(f"GraphSet: coarsening method '{method}' is not supported for graph-level tasks; supported: "
+                                      f"variation_neighborhoods, {', '.join(GRAPH_MATCHING_METHODS)}")
         co = self.co
         self.cluster_ptr = np.asarray(co.cluster_off)
         n = co.n_clusters

@@ -454,6 +454,21 @@ def node_classification_baseline(args, path, data, device="cuda", log=print):
     return all_loss, all_acc, all_time
 
 
+def graph_method(args):
+    """--coarsening_method for a graph-level task: variation_neighborhoods or a deterministic / in-order matching method
+    (graph_data.GRAPH_MATCHING_METHODS); affinity_GS is refused as in coarsening_classification."""
+    from . import graph_data
+
+    m = getattr(args, "coarsening_method", "variation_neighborhoods")
+    if m == "affinity_GS":
+        raise NotImplementedError("affinity_GS is supported by coarsening.coarsen() but not by the pipeline (see "
+                                  "coarsening_classification)")
+    if m != "variation_neighborhoods" and m not in graph_data.GRAPH_MATCHING_METHODS:
+        raise NotImplementedError(f"graph-level tasks coarsen with variation_neighborhoods, {', '.join(graph_data.GRAPH_MATCHING_METHODS)}; "
+                                  f"not '{m}'")
+    return m
+
+
 def graph_regression(args, path, mol, device="cuda", log=print):
     """run.graph_regression (run.py:707-830) / run.graph_classification (run.py:575-706) on a graph_data.GraphSet:
     50/25/25 split of a random permutation (utils.py:23-39), {Regress,Classify}_graph_gc / _gs, L1 / cross-entropy
@@ -463,7 +478,7 @@ def graph_regression(args, path, mol, device="cuda", log=print):
     from .train import GraphTrainer
 
     gset = graph_data.GraphSet(mol, ratio=args.coarsening_ratio, extra_node=bool(args.extra_node), device=device,
-                               cluster_node=bool(args.cluster_node))
+                               cluster_node=bool(args.cluster_node), method=graph_method(args))
     G = gset.n_graphs
     gen = torch.Generator().manual_seed(0 if args.seed is None else args.seed)
     idx = torch.randperm(G, generator=gen).tolist()

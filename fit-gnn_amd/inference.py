@@ -95,13 +95,13 @@ def graph_inference(args, mol):
     the uncoarsened graph; accuracy (graph_cls) or L1 loss (graph_reg) over the samples; one CSV row per model."""
     import types
 
-    from fitgnn_amd import graph_data, network
+    from fitgnn_amd import graph_data, network, pipeline
     from fitgnn_amd.train import _cat_pieces
 
     dev = torch.device(args.device)
     cls_task = args.task == "graph_cls"
     gset = graph_data.GraphSet(mol, ratio=args.coarsening_ratio, extra_node=bool(args.extra_node), device=dev,
-                               cluster_node=bool(args.cluster_node))
+                               cluster_node=bool(args.cluster_node), method=pipeline.graph_method(args))
     rng = np.random.default_rng(args.seed)
     ids = rng.choice(gset.n_graphs, size=min(args.num_test_samples, gset.n_graphs), replace=False).tolist()
     use_gc = args.exp_setup == "Gc_train_2_Gc_infer"
@@ -166,8 +166,6 @@ def main(argv=None):
     args.train_fitgnn = True
     data, args = train_cli.process_dataset(args)
     if args.task in ("graph_cls", "graph_reg"):
-        if args.coarsening_method != "variation_neighborhoods":
-            raise NotImplementedError(f"graph-level tasks coarsen with variation_neighborhoods only, not '{args.coarsening_method}'")
         return graph_inference(args, data)
     from fitgnn_amd import network, pipeline
     from fitgnn_amd.csr import csr_for

@@ -230,8 +230,6 @@ def main(argv=None):
         co = pipeline.coarsening_classification(args, data, 1 - args.coarsening_ratio, args.coarsening_method, device=args.device)
         return pipeline.node_regression(args, path, data, co, device=args.device)
     if args.task in ('graph_reg', 'graph_cls'):
-        if not args.baseline and args.coarsening_method != 'variation_neighborhoods':
-            raise NotImplementedError(f"graph-level tasks coarsen with variation_neighborhoods only, not '{args.coarsening_method}'")
         if args.baseline:
             return pipeline.graph_baseline(args, path, data, device=args.device)
         return pipeline.graph_regression(args, path, data, device=args.device)

@@ -716,6 +716,43 @@ int fitgnn_greedy_matching(const int32_t *rowptr, const int32_t *col, const int3
                            const int32_t *comp_off, const int64_t *k_keep, int64_t min_gain, int32_t *sel_off, int32_t *sel_mem, int32_t *sel_count,
                            int32_t *comp_taken, int32_t *rounds, void *work, size_t work_bytes, void *stream);
 
+/* Whole-component matching coarsening (coarsen() :60-182 with method heavy_edge or algebraic_JC, every level) of small
+ * components, one wavefront per component with its state in LDS; bit-identical, component by component, to the multi-launch
+ * path (fitgnn_edge_list .. fitgnn_lift_adjacency, per-element arithmetic shared through csrc/match_arith.h).
+ * W: block-diagonal over comp_off (device int32[n_comp+1]), symmetric, ascending columns, no diagonal (w == NULL: all ones).
+ * Components [c_begin, c_end) are processed; a component of <= 1 node keeps its node (no level, no draws).
+ * r: Loukas' r already clipped to [0, 0.999]; K (algebraic_JC, <= FITGNN_MATCH_SMALL_MAX_K): test vectors per level;
+ * max_level_r: the per-level clip.  LDS budget: components of up to max_nodes nodes and max_nnz stored entries; heavy_edge
+ * sizes every workgroup for those caps, algebraic_JC's single workgroup takes the full budget (128 nodes, 1024 entries,
+ * K = 12: 61.6 KiB).  fitgnn_match_small_lds_bytes() returns the size, or 0 if it exceeds FITGNN_MATCH_SMALL_LDS_BUDGET, a cap exceeds
+ * FITGNN_MATCH_SMALL_MAX_NODES / _MAX_NNZ (then fitgnn_match_small returns FITGNN_E_BADARG).  A component over the caps gets
+ * status FITGNN_MATCH_TOO_BIG and no output -- never skipped silently; a malformed one (column out of the component, unsorted
+ * row, diagonal entry, asymmetric pattern) FITGNN_MATCH_BAD_INPUT.
+ * algebraic_JC: ONE workgroup walks the components in order (the reference's draw order).  Level l of a component reads the
+ * next n_l*K values of draws (f64[n_draws], a Gaussian stream) row-major and divides them by sqrt_n[n_l] (f64[max_nodes+1],
+ * sqrt(n) as the host computes it).  The walk stops before a component over the caps (status TOO_BIG) or whose worst case
+ * K*N*max_levels exceeds the draws left; progress (device int64[2]) = {first component not done, draws consumed}.
+ * heavy_edge: one workgroup per component, all in one launch; draws / sqrt_n / progress unused (may be NULL).
+ * Outputs per component c (node range [b, b+N), entry range [p, p+nnz) of the input): assign int32 / cval f64 at [b, b+N)
+ * (cluster within the component, C's value), n_out[c] clusters, levels[c] applied levels, status[c] = FITGNN_MATCH_DONE, and
+ * the final coarse adjacency as a component-local CSR: wc_rowptr int32 at [b + c, b + c + n_out[c] + 1), wc_col int32 /
+ * wc_w f64 at [p, p + wc_rowptr[b + c + n_out[c]]) (the coarse graph has no more entries than the input). */
+#define FITGNN_MATCH_HEAVY_EDGE 0
+#define FITGNN_MATCH_ALGEBRAIC_JC 1
+#define FITGNN_MATCH_SMALL_MAX_NODES 128
+#define FITGNN_MATCH_SMALL_MAX_NNZ 1024
+#define FITGNN_MATCH_SMALL_MAX_K 12 /* algebraic_JC: test vectors per level */
+#define FITGNN_MATCH_SMALL_LDS_BUDGET 65536
+#define FITGNN_MATCH_DONE 1
+#define FITGNN_MATCH_TOO_BIG 2
+#define FITGNN_MATCH_BAD_INPUT 3
+size_t fitgnn_match_small_lds_bytes(int32_t method, int32_t max_nodes, int32_t max_nnz, int32_t K);
+int fitgnn_match_small(int32_t method, const int32_t *rowptr, const int32_t *col, const double *w, const int32_t *comp_off,
+                       int32_t c_begin, int32_t c_end, double r, int32_t K, int32_t max_levels, double max_level_r,
+                       const double *draws, int64_t n_draws, const double *sqrt_n, int32_t max_nodes, int32_t max_nnz,
+                       int32_t *assign, double *cval, int32_t *n_out, int32_t *levels, int32_t *status, int32_t *wc_rowptr,
+                       int32_t *wc_col, double *wc_w, int64_t *progress, void *stream);
+
 /* Adjacency lift Wc = zero_diag(Pinv^T W Pinv), then (Wc + Wc^T)/2 (coarsening_utils.py:138-139, :201-205),
  * with SciPy's summation order (bit-identical to the reference).  Outputs a CSR with ascending
  * columns: rowptr_c int32[n+1], col_c/w_c capacity nnz(W), nnz_c int32[1]. */
