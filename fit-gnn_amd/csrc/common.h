@@ -34,6 +34,45 @@ __host__ __device__ __forceinline__ bool dropout_keep(uint64_t bits, int sub, ui
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// Cache policy of the GCN step's once-touched HBM streams: a stream whose bit is set in FITGNN_NT_STREAMS is loaded / stored with the
+// non-temporal hint (global_load / global_store ... nt), the others with the default policy.  Everything re-read from L2 or the
+// Infinity Cache (CSR, tile and block tables, compact operands, column-sum partials, gathered operand rows) keeps the default.
+// The default mask holds the streams tools/nt_probe.py measured faster with nt (profiles/r05_nt_probe_S-products.log);
+// `make EXTRA=-DFITGNN_NT_STREAMS=<mask>` builds another mix for the probe.
+enum NtStream : uint32_t {
+    kNtOutTable = 1u << 0,   // whole-subgraph SpMM over a row-indirected table (layer 0 forward): output row stores
+    kNtOutPlain = 1u << 1,   // whole-subgraph SpMM, plain operand (layer 1 forward): output row stores
+    kNtOutTwoHop = 1u << 2,  // two-hop backward: stores of G
+    kNtWinPlain = 1u << 3,   // plain whole-subgraph launch: window staging loads of the dense operand
+    kNtWinTwoHop = 1u << 4,  // two-hop launch: window staging loads (side-table rows and `prev` slices of simple rows)
+    kNtPrev = 1u << 5,       // side-table kernel: its rows' `prev` slices, read once
+    kNtWinTable = 1u << 6,   // layer-0 launch: window staging loads from the de-duplicated table (rows re-read ~50x)
+    kNtSideStore = 1u << 7,  // side-table kernel: stores of ZT
+    kNtSegLoad = 1u << 8,    // segment sum: member row loads
+    kNtSegStore = 1u << 9,   // segment sum: output row stores
+};
+#ifndef FITGNN_NT_STREAMS
+#define FITGNN_NT_STREAMS (fitgnn::kNtOutPlain | fitgnn::kNtOutTwoHop | fitgnn::kNtPrev | fitgnn::kNtSideStore | fitgnn::kNtSegLoad)
+#endif
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+template <uint32_t S>
+__device__ __forceinline__ float4 load4(const float *p) {
+    if constexpr ((FITGNN_NT_STREAMS & S) != 0u) {
+        const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *reinterpret_cast<const float4 *>(p);
+    }
+}
+template <uint32_t S>
+__device__ __forceinline__ void store4(float *p, const float4 &v) {
+    if constexpr ((FITGNN_NT_STREAMS & S) != 0u) {
+        __builtin_nontemporal_store(nt_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<nt_f4 *>(p));
+    } else {
+        *reinterpret_cast<float4 *>(p) = v;
+    }
+}
+
 }  // namespace fitgnn
 
 // Raise a kernel's dynamic-LDS limit ONCE per process and device (done: one bit per device ordinal).  hipFuncSetAttribute is a

@@ -259,8 +259,8 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const int32_t *__restr
                 const bool has = k + j < cnt;
                 const int node = __builtin_amdgcn_readlane(my, has ? k + j : k);
                 const float *src = Xs + (int64_t)node * ldx;
-                if (VEC == 4) {
-                    const float4 q = *reinterpret_cast<const float4 *>(src);
+                if constexpr (VEC == 4) {
+                    const float4 q = fitgnn::load4<fitgnn::kNtSegLoad>(src);
                     v[j][0] = q.x; v[j][1 % VEC] = q.y; v[j][2 % VEC] = q.z; v[j][3 % VEC] = q.w;
                 } else {
                     v[j][0] = src[0];
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const int32_t *__restr
     }
     if (!live) return;
     float *dst = out + (int64_t)sgm * ldo + f0;
-    if (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(acc[0], acc[1 % VEC], acc[2 % VEC], acc[3 % VEC]);
+    if constexpr (VEC == 4) fitgnn::store4<fitgnn::kNtSegStore>(dst, make_float4(acc[0], acc[1 % VEC], acc[2 % VEC], acc[3 % VEC]));
     else dst[0] = acc[0];
 }
 

@@ -106,7 +106,8 @@ __device__ __forceinline__ typename Pack<VEC>::T epilogue_value(typename Pack<VE
     return acc;
 }
 
-template <int VEC, bool BWD_OK = true, bool NOEPI = false>
+// NT: the fitgnn::NtStream bit that selects the cache policy of the row store (0: default policy)
+template <int VEC, bool BWD_OK = true, bool NOEPI = false, uint32_t NT = 0>
 __device__ __forceinline__ void finish_row(typename Pack<VEC>::T acc, int row, int col0, int H, float *__restrict__ Y,
                                            int64_t ldy, const float (&bv)[VEC], const RowEpilogue &E, float (&cs)[VEC],
                                            const typename Pack<VEC>::T &o) {
@@ -115,7 +116,8 @@ __device__ __forceinline__ void finish_row(typename Pack<VEC>::T acc, int row, i
 #ifdef FITGNN_SPMM_NOSTORE
     if (Pack<VEC>::get(out, 0) == 12345.678f)
 #endif
-    *reinterpret_cast<T *>(Y + (int64_t)row * ldy + col0) = out;
+    if constexpr (VEC == 4 && NT != 0) fitgnn::store4<NT>(Y + (int64_t)row * ldy + col0, out);
+    else *reinterpret_cast<T *>(Y + (int64_t)row * ldy + col0) = out;
 }
 
 template <int VEC, bool BWD_OK = true>
@@ -402,6 +404,9 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
     int32_t zero_from, const float *__restrict__ Xc2 = nullptr, int64_t ldxc = 0, const int32_t *__restrict__ row_p = nullptr,
     const float *__restrict__ row_w = nullptr, int32_t xc_zero_from = 0) {
     static_assert(!TWO || (XROW && !BWD && NOEPI), "the two-hop form is a plain product over a table");
+    // cache policy per stream (common.h): output rows, window rows
+    constexpr uint32_t kNtOut = TWO ? fitgnn::kNtOutTwoHop : BWD ? 0u : XROW ? fitgnn::kNtOutTable : fitgnn::kNtOutPlain;
+    constexpr uint32_t kNtWin = TWO ? fitgnn::kNtWinTwoHop : XROW ? fitgnn::kNtWinTable : fitgnn::kNtWinPlain;
     // zero_from (XROW): operand rows >= zero_from are rows of zeros (the tail of a compact operand, ops.ZERO_ROWS): they are not
     // loaded -- as window rows they are staged as zeros, as gathered entries they read the LDS slot kZeroSlot -- so an operand
     // that is zero on most rows costs LDS reads and FMAs, not a memory round trip per gathered entry (measured on the compact
@@ -489,13 +494,13 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
                 const int rr = min(r, r1 - 1);
                 const float *rowp = sr >= 0 ? Xs + sr * ldx : prev + (uint64_t)rr * (uint64_t)H + (uint64_t)colc2;
                 const int pp = __builtin_amdgcn_readlane(xp_next, j);
-                const T a = *reinterpret_cast<const T *>(rowp);
+                const T a = fitgnn::load4<kNtWin>(rowp);
                 pv[j] = r < r1 ? a : P::zero();
                 sr_pub[j] = (int)sr;
                 pp_pub[j] = pp;
                 w_pub[j] = __int_as_float(__builtin_amdgcn_readlane(xw_next, j));
             } else if (r < r1 && !is_zero_row(sr)) {
-                pv[j] = *reinterpret_cast<const T *>(Xs + sr * ldx);   // wave-uniform
+                pv[j] = fitgnn::load4<kNtWin>(Xs + sr * ldx);   // wave-uniform
             }
         }
         if (XROW) fetch_indices(r1, min(r1 + kBlkRows, blk.row_end));  // the piece after: its rows are requested next time round
@@ -723,7 +728,7 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
                     for (int u = 0; u < kRowBatch; ++u) P::fma(acc, wq[u], xq[u]);
                 }
             }
-            if (live) finish_row<4, BWD, NOEPI>(acc, row, col0, H, Y, ldy, bv, rowepi, cs, o_prev);
+            if (live) finish_row<4, BWD, NOEPI, kNtOut>(acc, row, col0, H, Y, ldy, bv, rowepi, cs, o_prev);
         }
 
         SSTAMP(s_p2);
@@ -775,7 +780,7 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
         if (my_long[q] < 0) continue;
         const T o_prev = prev_row<4, BWD>(rowepi, my_long[q], col0, H, live);
         gather_long(q, 0x7fffffff);
-        if (live) finish_row<4, BWD, NOEPI>(acc_long[q], my_long[q], col0, H, Y, ldy, bv, rowepi, cs, o_prev);
+        if (live) finish_row<4, BWD, NOEPI, kNtOut>(acc_long[q], my_long[q], col0, H, Y, ldy, bv, rowepi, cs, o_prev);
     }
     if ((BWD || TWO) && col_part) write_col_part<4>(reinterpret_cast<float *>(s_win), cs, col_part, b, H, col0, live);
 #ifdef FITGNN_SPMM_STAMPS
@@ -1159,7 +1164,7 @@ __global__ __launch_bounds__(kThreads) void two_hop_rows_kernel(
     const float keep_scale = (epi & FITGNN_EPI_DROPOUT) ? 1.0f / (1.0f - p_drop) : 1.0f;
     const RowEpilogue rowepi{epi | FITGNN_EPI_BACKWARD, keep_scale, (epi & FITGNN_EPI_DROPOUT) ? 1.0f - p_drop : 1.0f,
                              fitgnn::dropout_threshold(p_drop), seed, mask, prev};
-    const T o = *reinterpret_cast<const T *>(prev + (uint64_t)row * (uint64_t)H + (uint64_t)colc);
+    const T o = fitgnn::load4<fitgnn::kNtPrev>(prev + (uint64_t)row * (uint64_t)H + (uint64_t)colc);
     const int e0 = rowptr[row], e1 = rowptr[row + 1];
     T u = P::zero();
     for (int base = e0; base < e1; base += 64) {
@@ -1178,7 +1183,7 @@ __global__ __launch_bounds__(kThreads) void two_hop_rows_kernel(
     float none[4] = {0.f, 0.f, 0.f, 0.f};
     const float bv[4] = {0.f, 0.f, 0.f, 0.f};
     const T z = epilogue_value<4, true, false>(u, row, colc, H, bv, rowepi, none, o);   // (clamped column: see the two-hop kernel)
-    if (live) *reinterpret_cast<T *>(ZT + (int64_t)i * ldz + col0) = z;
+    if (live) fitgnn::store4<fitgnn::kNtSideStore>(ZT + (int64_t)i * ldz + col0, z);
 }
 
 // Direct-gather variant for very sparse batches (few non-zeros per row, e.g. PubMed-like subgraphs with
