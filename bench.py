@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- edges aggregated/sec (GCN fwd+bwd) on coarsened subgraphs (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-products] [--layer GCNConv] [--shard K/N] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-products] [--layer GCNConv] [--shard K/N] [--dump-outputs DIR] [--full]
 
 Workload (config.workload), default S-products = BASELINE.json configs[3], the north_star target: "ogbn-products
 use_community_detection, subgraph-batch DP" on synthetic data of that shape: one community graph of
@@ -25,10 +25,16 @@ the parent then spawns N fresh children itself BEFORE it touches torch or the GP
 Prints ONE JSON line (rank 0): the metric (dense products in the reference's fp32 arithmetic: csrc/gemm_f32.hip), `roofline` for
 the SpMM kernel over ALL FOUR products of the step (HIP events around each launch inside the timed region; per-launch entries
 with the number of products they carry and their own compulsory bytes; `traffic` = HBM bytes per product from the committed PMC
-passes; `copy_ceiling_GBps` = the library's own stream-copy kernel in this process), `ms_per_step_bf16x3` (the same step with the
-dense products as a 3 x bf16 split: secondary), `ms_per_step_pruned` / `value_pruned` (the last layer's forward aggregation on the loss
-rows alone: fewer edges, its own count: secondary), at N>1 `allreduce_ms` and the ranks' nnz', and at N=1 `cpu_baseline` (the torch-CPU
-oracle of the same step on an evenly spaced sample of loader batches + the C oracle of the contraction, on this host).
+passes) and at N>1 `allreduce_ms` and the ranks' nnz'.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds what takes
+runs of its own after the timed region: `ms_per_step_bf16x3` (the same step with the dense products as a 3 x bf16 split),
+`ms_per_step_dense_on_all_rows`, `ms_per_step_pruned` / `value_pruned` (the last layer's forward aggregation on the loss rows alone:
+fewer edges, its own count), `gemm_kernels` (HIP events over five more steps), `roofline.copy_ceiling_GBps` (the library's own
+stream-copy kernel in this process), `t_assemble_s` as the assembly once more (else the first call's time), S-qm9's eager SpMM
+roofline, and at N=1 `cpu_baseline` (the torch-CPU oracle of the same step on an evenly spaced sample of loader batches + the C
+oracle of the contraction, on this host).  The others are null, empty or absent without it; `full` on the line says which kind
+of run it was.
 """
 import argparse
 import json
@@ -59,10 +65,13 @@ def parse_args():
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--dropout", type=float, default=0.5, help="F.dropout's p (network.py:33: the default 0.5); 0 makes the step "
                     "deterministic across shardings (the dropout hash is keyed on a rank's own row numbers)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16x3", action="store_true", help="skip the re-timing of the step with the dense products as a 3 x bf16 split")
-    ap.add_argument("--no-all-rows", action="store_true", help="skip the re-timing with every dense operation over all union rows")
-    ap.add_argument("--no-pruned", action="store_true", help="skip the re-timing of the step with the last layer on the clusters' own nodes only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the re-timed variants of the step, the GEMM "
+                         "kernels' events, the copy ceiling, the CPU baseline (see the --no-* options to skip some of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-bf16x3", action="store_true", help="--full: skip the re-timing of the step with the dense products as a 3 x bf16 split")
+    ap.add_argument("--no-all-rows", action="store_true", help="--full: skip the re-timing with every dense operation over all union rows")
+    ap.add_argument("--no-pruned", action="store_true", help="--full: skip the re-timing of the step with the last layer on the clusters' own nodes only")
     ap.add_argument("--fold", action="store_true", help="A/B: epilogue backward folded into the transposed SpMM (slower, see DESIGN.md)")
     ap.add_argument("--prune-unused-rows", action="store_true",
                     help="NOT the headline configuration: last layer only on the clusters' own nodes (the extra nodes' outputs "
@@ -413,10 +422,10 @@ def main():
     else:
         info.update(union_rows=int(mine_sizes[0]), nnz_prime=int(mine_sizes[1]))
     # t_assemble_first_call_s: this process's FIRST assembly -- it includes the one-time paging-in of the library sort / unique / scan
-    # kernels' code objects (0.2-0.8 s, box dependent); t_assemble_s: the same assembly once more = what the algorithm takes
+    # kernels' code objects (0.2-0.8 s, box dependent); t_assemble_s (--full): the same assembly once more = what the algorithm takes
     info["t_assemble_first_call_s"] = round(t5 - t4, 3)
     info["t_assemble_s"] = info["t_assemble_first_call_s"]
-    if world == 1 and emu is None and args.layer == "GCNConv":
+    if args.full and world == 1 and emu is None and args.layer == "GCNConv":
         t_w = time.time()
         sub_w, _ = workloads.assemble(args.workload, ei_d, assign_d, n_clusters, clusters=mine)
         torch.cuda.synchronize()
@@ -496,13 +505,15 @@ def main():
         torch.cuda.synchronize()
         comm_ms = float(np.mean([a.elapsed_time(b) for a, b in trainer.comm_events[args.warmup:]]))
     trainer.comm_events = None
-    # a few more steps, outside the timed region, with events around the hand-written GEMM launches (secondary figures:
+    # --full: a few more steps, outside the timed region, with events around the hand-written GEMM launches (secondary figures:
     # their markers would cost the headline 1 %)
-    trainer.cfg.profile_gemm = []
-    for _ in range(min(args.steps, 5)):
-        trainer.step()
-    torch.cuda.synchronize()
-    gemm_events, trainer.cfg.profile_gemm = trainer.cfg.profile_gemm, None
+    gemm_events = []
+    if args.full:
+        trainer.cfg.profile_gemm = []
+        for _ in range(min(args.steps, 5)):
+            trainer.step()
+        torch.cuda.synchronize()
+        gemm_events, trainer.cfg.profile_gemm = trainer.cfg.profile_gemm, None
 
     edges_per_step = 4.0 * batch.nnz   # GCN / GAT: two layers x (aggregation forward + its adjoint backward)
     if args.layer == "APPNP":
@@ -523,7 +534,7 @@ def main():
             e2 = _pruned_edges(tr2, batch)
         return dict(ms_per_step=dt2 / k2 * 1e3, value=e2 * k2 / dt2, steps=k2, loss=float(loss2), edges_per_step=e2)
 
-    secondary = emu is None and args.layer == "GCNConv"
+    secondary = args.full and emu is None and args.layer == "GCNConv"
     # secondary: the same step with the dense products as a 3 x bf16 split (narrower than the reference's fp32: never the headline)
     bf16x3 = retime("high") if (secondary and not args.no_bf16x3 and args.gemm_precision == "exact") else None
     # the same step with the last layer transform-first and every dense operation over all union rows
@@ -641,23 +652,25 @@ def main():
                            "frac": float(np.sum([f for _, f in v]) / (np.sum([d for d, _ in v]) * 1e-3) / 1e12 /
                                          (157.3 if name.startswith("gemm_f32") else 2500.0))}
                     for name, v in by_kernel.items()}
-    gemm_ms_per_step = float(np.sum([d for v in by_kernel.values() for d, _ in v]) / max(min(args.steps, 5), 1))
-    # device-to-device copy ceiling of this GPU, same process, after the timed region (read + write bytes / time)
-    # (fitgnn_stream_copy_f32: one workgroup per 16-KiB chunk, 16-byte non-temporal accesses -- the fastest shape of
-    # tools/microbench/copy_probe.hip; 2 x 4 GiB moved per launch, far beyond the 256-MiB Infinity Cache)
-    from fitgnn_amd import _lib
-    src = torch.rand(1 << 30, dtype=torch.float32, device=device)
-    dst = torch.empty_like(src)
-    copy = lambda: _lib.check(_lib.lib().fitgnn_stream_copy_f32(_lib.dptr(src), _lib.dptr(dst), src.numel(), _lib.stream_ptr(device)), "stream_copy")  # noqa: E731
-    copy()
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record()
-    for _ in range(5):
+    gemm_ms_per_step = float(np.sum([d for v in by_kernel.values() for d, _ in v]) / max(min(args.steps, 5), 1)) if args.full else None
+    copy_gbs = None
+    if args.full:
+        # device-to-device copy ceiling of this GPU, same process, after the timed region (read + write bytes / time)
+        # (fitgnn_stream_copy_f32: one workgroup per 16-KiB chunk, 16-byte non-temporal accesses -- the fastest shape of
+        # tools/microbench/copy_probe.hip; 2 x 4 GiB moved per launch, far beyond the 256-MiB Infinity Cache)
+        from fitgnn_amd import _lib
+        src = torch.rand(1 << 30, dtype=torch.float32, device=device)
+        dst = torch.empty_like(src)
+        copy = lambda: _lib.check(_lib.lib().fitgnn_stream_copy_f32(_lib.dptr(src), _lib.dptr(dst), src.numel(), _lib.stream_ptr(device)), "stream_copy")  # noqa: E731
         copy()
-    c1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 5 * 2 * src.numel() * 4 / (c0.elapsed_time(c1) * 1e-3) / 1e9
-    del src, dst
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0.record()
+        for _ in range(5):
+            copy()
+        c1.record()
+        torch.cuda.synchronize()
+        copy_gbs = 5 * 2 * src.numel() * 4 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+        del src, dst
 
     run_cfg = dict(workload=args.workload, hidden=H, classes=C, gemm_precision=args.gemm_precision, two_hop=not args.no_two_hop,
                    dropout=args.dropout, dedup=not args.no_dedup, layer=args.layer)
@@ -716,8 +729,9 @@ def main():
                      "launches": launches,
                      "best_launch": None if best is None else {"launch": best["launch"], "frac": best["frac"], "avg_us": best["avg_us"]},
                      "spmm_edges_per_s": (edges_per_step / (sum_ms * 1e-3)) if launches else None,
-                     "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs},
+                     "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": None if copy_gbs is None else achieved / copy_gbs},
         "run_config": run_cfg,
+        "full": args.full,
         "gpu_warm": warm_info,
         "gemm_kernels": gemm_summary, "gemm_ms_per_step": gemm_ms_per_step,
         "loss": loss_final,
@@ -728,7 +742,7 @@ def main():
     if emu is not None:
         out["scaling"] = "strong (one rank of %d stepped alone: `value` is THIS shard's edges/s, not a job's)" % emu[1]
         out["config"]["parallelism"] = "rank %d of dp%d, alone on one GPU (RCCL group of one)" % (info["emulated"]["rank"], emu[1])
-    if rank == 0 and world == 1 and emu is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and emu is None and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(batch, sd0, 2, layer=args.layer)
         out["cpu_baseline"]["cpu_model"] = cpu_model()
         out["cpu_baseline"]["host_cores"] = os.cpu_count()
@@ -801,10 +815,10 @@ def bench_qm9(args, device, world, rank, backend):
     dt = float(dt.item())
     nnz_total, rows_total = float(tot[0]), float(tot[1])
     n_batches = len(tr.batches)
-    # the SpMM launches of one EAGER epoch's first batches (HIP events cannot be read back from inside a replayed hipGraph): their mean
-    # duration against the §8(d) bytes of a batch -- these batches are ~10^4 rows: the launches are latency-, not bandwidth-bound
+    # --full: the SpMM launches of one EAGER epoch's first batches (HIP events cannot be read back from inside a replayed hipGraph): their
+    # mean duration against the §8(d) bytes of a batch -- these batches are ~10^4 rows: the launches are latency-, not bandwidth-bound
     launches, achieved = [], float("nan")
-    if world == 1:
+    if args.full and world == 1:
         import types
         ev_cfg = cfg.replace(profile=[])   # (no gradient sink: these passes run outside the trainer)
         model.set_op_config(ev_cfg)
@@ -857,8 +871,9 @@ def bench_qm9(args, device, world, rank, backend):
                                "the launches are latency-bound, and the epoch is bound by its launches per batch step)",
                      "launches": launches},
         "loss": float(loss),
+        "full": args.full,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_qm9(gset, mol, model, tr)
         out["cpu_baseline"]["cpu_model"] = cpu_model()
         out["cpu_baseline"]["host_cores"] = os.cpu_count()

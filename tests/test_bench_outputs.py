@@ -1,5 +1,6 @@
 """bench.py --dump-outputs: what the timed step computed, written as .npy files (CPU tier: the writer, the size cap, the argument
-checks; GPU tier: two runs with the same arguments write the same arrays, and the dumped loss is the line's)."""
+checks; GPU tier: two runs with the same arguments write the same arrays, and the dumped loss is the line's).  And --full: a plain
+run times the same steps as a --full run and leaves out what --full adds after them."""
 import importlib.util
 import json
 import os
@@ -31,6 +32,13 @@ def test_steps_and_dump_arguments(bench, monkeypatch):
         monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
         with pytest.raises(SystemExit):
             bench.parse_args()
+
+
+def test_full_is_off_by_default(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse_args().full is True
 
 
 def test_step_outputs_hold_loss_parameters_and_moments(bench):
@@ -97,3 +105,36 @@ def test_bench_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
         assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), f
         assert np.array_equal(a, b), f
     assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == line["loss"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_same_steps_and_full_adds_the_secondary_figures(tmp_path):
+    """A plain run and a --full run with the same arguments: the same timed steps (the same loss and dumped arrays), the headline
+    fields in both; only the --full line carries the re-timed variants, the GEMM kernels' events, the copy ceiling and the CPU
+    baseline."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    common = ["--workload", "S-cora", "--steps", "3", "--warmup", "1", "--gpu-warm-seconds", "0"]
+    lines = {}
+    for d, extra in (("plain", []), ("full", ["--full"])):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra + ["--dump-outputs", str(tmp_path / d)],
+                             env=env, cwd=tmp_path, check=True, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+        lines[d] = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["metric"].startswith("edges aggregated/sec") and line["unit"] == "edges/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert len(line["roofline"]["launches"]) > 0
+    assert plain["full"] is False and full["full"] is True
+    assert plain["loss"] == full["loss"]
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == sorted(os.listdir(tmp_path / "full"))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f
+    assert "cpu_baseline" not in plain and plain["gemm_kernels"] == {} and plain["gemm_ms_per_step"] is None
+    assert plain["roofline"]["copy_ceiling_GBps"] is None
+    assert all(plain[k] is None for k in ("ms_per_step_bf16x3", "ms_per_step_dense_on_all_rows", "ms_per_step_pruned"))
+    assert full["cpu_baseline"]["value"] > 0 and full["gemm_kernels"] and full["gemm_ms_per_step"] > 0
+    assert full["roofline"]["copy_ceiling_GBps"] > 0
+    assert all(full[k] > 0 for k in ("ms_per_step_bf16x3", "ms_per_step_dense_on_all_rows", "ms_per_step_pruned"))

@@ -115,13 +115,14 @@ def test_bench_shard_mode_steps_one_rank_of_a_job_and_its_shares_add_up(tmp_path
 @pytest.mark.parametrize("layer", ["GATConv", "APPNP"])
 def test_bench_lines_of_the_other_operators(tmp_path, layer):
     """`bench.py --layer GATConv | APPNP` (north_star names GCN / GAT / APPNP): the same line shape as the headline -- the metric, a
-    step-weighted roofline over the operator's own kernels with per-kind entries, the CPU oracle of the same step beside it."""
+    step-weighted roofline over the operator's own kernels with per-kind entries, and under --full the CPU oracle of the same step
+    beside it."""
     bench = os.path.join(ROOT, "bench.py")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, bench, "--layer", layer, "--workload", "S-cora", "--steps", "8", "--warmup", "2"], env=env, cwd=tmp_path,
-                         check=True, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    res = subprocess.run([sys.executable, bench, "--layer", layer, "--workload", "S-cora", "--steps", "8", "--warmup", "2", "--full"], env=env,
+                         cwd=tmp_path, check=True, timeout=600, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["metric"].startswith("edges aggregated/sec") and line["value"] > 0 and line["config"]["layer"] == layer
     kinds = {l["kind"] for l in line["roofline"]["launches"]}

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The scaling evidence ONE MI355X can give: the heaviest rank's step of an N-rank data-parallel job, for
-N = 1, 2, 4, 8, each timed alone on this GPU by `bench.py --shard heaviest/N` (a fresh child process per N: the shard is built exactly
+N = 1, 2, 4, 8, each timed alone on this GPU by `bench.py --shard heaviest/N --full` (a fresh child process per N: the shard is built exactly
 as `--gpus N` builds it, the gradient all-reduce runs over RCCL in a group of one), and the model of DESIGN.md §5 fitted to it:
 
     step_ms(N) = c + s * nnz'_shard(N) / 1e6            (c: what does not shrink with N; s: ms per million edges of the shard)
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run(n, extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--shard", f"heaviest/{n}", "--no-cpu-baseline", "--no-bf16x3", "--no-all-rows",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--shard", f"heaviest/{n}", "--full", "--no-cpu-baseline", "--no-bf16x3", "--no-all-rows",
            "--no-pruned"] + extra
     res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True)
     return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
