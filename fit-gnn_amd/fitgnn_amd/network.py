@@ -62,20 +62,22 @@ class _Base(nn.Module):
             m.reset_parameters()
         self.lt1.reset_parameters()
 
+    def _mask(self, i):
+        """The dropout mask injected for layer i (tests), else None."""
+        return self._inject_masks[i] if self._inject_masks is not None else None
+
     def _first_layer_dedup(self, x_table, edge_index, x_index, link_out=None, gat_link=None):
         """Layer 0 on a de-duplicated feature table (x_index: ops.RowIndex mapping union rows to table rows).
         gat_link: the link an attention layer records for an aggregate-first attention layer right behind it (FusedGATLastLayerRows)."""
-        conv = self.conv[0]
+        conv, mask = self.conv[0], self._mask(0)
         if isinstance(conv, fnn.GATConv) and x_table.is_cuda and link_out is None:
-            mask = self._inject_masks[0] if self._inject_masks is not None else None
             return conv.forward_elu_dropout(x_table, edge_index, p=self.dropout_p, training=self.training, mask=mask, x_index=x_index,
                                             link_out=gat_link)
         if not (isinstance(conv, fnn.GCNConv) and x_table.is_cuda):
             return None
-        mask = self._inject_masks[0] if self._inject_masks is not None else None
         g = conv.graph(edge_index, int(x_index.index.numel()))
         cfg = self.op_config
-        seed = ops.next_seed(cfg) if (self.training and self.dropout_p > 0 and mask is None) else 0
+        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
         return ops.FusedGCNLayerDedup.apply(x_table.float(), conv.lin.weight, conv.bias, g, x_index, float(self.dropout_p),
                                             bool(self.training), seed, mask, link_out, cfg)
 
@@ -101,13 +103,13 @@ class _Base(nn.Module):
         for i in range(first, self.num_layers if last is None else last):
             conv = self.conv[i]
             if isinstance(conv, fnn.GCNConv) and x.is_cuda:
-                mask = self._inject_masks[i] if self._inject_masks is not None else None
+                mask = self._mask(i)
                 nxt = ops.EpilogueLink() if i + 1 < self.num_layers else None   # the last output goes to lt1: plain gradient
                 if i == 0 and link is None and ops.narrow_input_supported(x, conv.lin.weight, self.op_config):
                     # a narrow static input (QM9's 11 atom features): aggregate first, A_hat x formed once per (graph, input)
                     cfg = self.op_config
                     ax = ops.aggregated_input(conv.graph(edge_index, x.shape[0]), x, cfg)
-                    seed = ops.next_seed(cfg) if (self.training and self.dropout_p > 0 and mask is None) else 0
+                    seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
                     x = ops.FusedGCNLayerAggregatedInput.apply(ax, conv.lin.weight, conv.bias, float(self.dropout_p), bool(self.training),
                                                                seed, mask, nxt, cfg)
                 else:
@@ -115,7 +117,7 @@ class _Base(nn.Module):
                                                  link_out=nxt)
                 link = nxt
             elif isinstance(conv, fnn.GATConv) and x.is_cuda:
-                mask = self._inject_masks[i] if self._inject_masks is not None else None
+                mask = self._mask(i)
                 is_tail = i + 1 == (self.num_layers if last is None else last)
                 x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask,
                                              link_out=tail_link if is_tail else None)
@@ -142,9 +144,9 @@ class _Base(nn.Module):
             h, link = x.float(), None
         if h.shape[1] % 4 != 0 and link is not None:
             link = None
-        mask = self._inject_masks[L - 1] if self._inject_masks is not None else None
+        mask = self._mask(L - 1)
         g = last.graph(edge_index, h.shape[0])
-        seed = ops.next_seed(cfg) if (self.training and self.dropout_p > 0 and mask is None) else 0
+        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
         return ops.FusedGCNLayerRows.apply(h, last.lin.weight, last.bias, g, float(self.dropout_p), bool(self.training), seed, mask, rows, cfg,
                                            link)
 
@@ -196,9 +198,9 @@ class _Base(nn.Module):
                     and (first == L - 1 or isinstance(self.conv[L - 2], (fnn.GATConv, fnn.GCNConv)))):
                 # the last attention layer aggregate-first: its dense part on the loss rows only (ops.FusedGATLastLayerRows)
                 x = self.embed(x, edge_index, first=first, link=link, last=L - 1, tail_link=glink)
-                mask = self._inject_masks[L - 1] if self._inject_masks is not None else None
+                mask = self._mask(L - 1)
                 g = fnn.csr_for(edge_index, x.shape[0], "gat")
-                seed = ops.next_seed(cfg) if (self.training and self.dropout_p > 0 and mask is None) else 0
+                seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
                 used = glink if (glink is not None and glink.epi != 0) else None   # (recorded by the layer below: it is an attention layer with act)
                 return ops.FusedGATLastLayerRows.apply(x, last.lin.weight, last.att_src.view(-1), last.att_dst.view(-1), last.bias,
                                                        self.lt1.weight, self.lt1.bias, g, last.negative_slope, float(self.dropout_p),
@@ -208,7 +210,7 @@ class _Base(nn.Module):
         for i in range(first, L - 1):
             conv = self.conv[i]
             if isinstance(conv, fnn.GCNConv):
-                mask = self._inject_masks[i] if self._inject_masks is not None else None
+                mask = self._mask(i)
                 nxt = ops.EpilogueLink()
                 x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask, link_in=link,
                                              link_out=nxt)
@@ -216,10 +218,10 @@ class _Base(nn.Module):
             else:
                 x = F.dropout(F.elu(conv(x, edge_index)), p=self.dropout_p, training=self.training)
                 link = None
-        mask = self._inject_masks[L - 1] if self._inject_masks is not None else None
+        mask = self._mask(L - 1)
         g = last.graph(edge_index, x.shape[0])
         cfg = self.op_config
-        seed = ops.next_seed(cfg) if (self.training and self.dropout_p > 0 and mask is None) else 0
+        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
         if (loss_rows is not None and cfg.last_layer_on_loss_rows and loss_rows.numel() > 0 and x.shape[1] % 4 == 0
                 and last.lin.weight.shape[0] % 4 == 0 and ops.head_rows_supported(x.new_empty((1, last.lin.weight.shape[0])), self.lt1.weight)):
             # aggregate first, then the dense part on the loss rows only; the previous layer's epilogue backward rides on the
@@ -253,14 +255,14 @@ class _Base(nn.Module):
         x = x.float()
         for i in range(first, L - 1):
             conv = self.conv[i]
-            mask = self._inject_masks[i] if self._inject_masks is not None else None
+            mask = self._mask(i)
             x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask) \
                 if isinstance(conv, fnn.GCNConv) else F.dropout(F.elu(conv(x, edge_index)), p=self.dropout_p, training=self.training)
         agg = ops.SpMMRows.apply(x, sub, self.op_config)                   # [m, H_in]
         z = ops.Linear.apply(agg, last.lin.weight, self.op_config)
         if last.bias is not None:
             z = z + last.bias
-        mask = self._inject_masks[L - 1] if self._inject_masks is not None else None
+        mask = self._mask(L - 1)
         z = F.elu(z)
         if mask is not None and self.training:
             z = z * mask.index_select(0, sub.rows).to(z.dtype) / (1.0 - self.dropout_p)

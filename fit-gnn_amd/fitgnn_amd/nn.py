@@ -57,7 +57,7 @@ class GCNConv(_OpConfigured, nn.Module):
         exactly one next fused layer (sequential stacks only, see ops.EpilogueLink)."""
         g = graph if graph is not None else self.graph(edge_index, x.shape[0])
         cfg = self.op_config
-        seed = ops.next_seed(cfg) if (training and p > 0 and mask is None) else 0
+        seed = ops.dropout_seed(cfg, training, p, mask)
         return ops.FusedGCNLayer.apply(x, self.lin.weight, self.bias, g, float(p), bool(training), seed, mask, link_in, link_out, cfg)
 
     def extra_repr(self):
@@ -167,7 +167,7 @@ class GATConv(_OpConfigured, nn.Module):
         g = csr_for(edge_index, n, "gat")
         cfg = self.op_config
         h = ops.Linear.apply(x.float(), self.lin.weight, cfg)
-        seed = ops.next_seed(cfg) if (training and p > 0 and mask is None) else 0
+        seed = ops.dropout_seed(cfg, training, p, mask)
         return ops.GATAggregate.apply(h, self.att_src.view(-1), self.att_dst.view(-1), self.bias, g, self.negative_slope,
                                       True, float(p), bool(training), seed, mask, cfg, x_index, link_out)
 

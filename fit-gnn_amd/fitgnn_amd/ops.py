@@ -78,10 +78,7 @@ class OpConfig:
     fused_pool_head  lt1(global_mean_pool(x[rows])) of the graph-level regression models as one launch each way (MeanPoolHead) instead
                      of pool, scale, library product and bias add (A/B switch).
     grad_sink        None, or an object with `.view(data_ptr)` -> the slice of a "fresh gradients" buffer that belongs to the parameter stored at
-                     that address (train.FlatGrads with fresh=True).  Backward nodes that know it write a weight / bias gradient THERE
-                     (the product's own output buffer) and return None for it, so autograd issues no `grad += new` launch per tensor; the
-                     optimiser kernel folds the buffer into the accumulated gradients (fitgnn_adam_step_acc_f32).  A parameter must
-                     feed ONE such node per backward (a second write would replace the first, not add to it).
+                     that address (train.FlatGrads with fresh=True): backward nodes write weight / bias gradients there (_GradSink).
     pad_table_min_k  static feature tables at least this wide whose width is not a multiple of 32 run layer 0's
                      products on a copy zero-padded once (real feature widths: 100, 500, 1 433, 8 415).
     profile / profile_gemm / profile_fused   None, or a list that collects HIP-event pairs around the SpMM / hand-written
@@ -118,11 +115,41 @@ class OpConfig:
 DEFAULT = OpConfig()   # what ops run under when their caller names no config; never modified by this package
 
 
-def _sink(cfg, t):
-    """The fresh-gradient slice of parameter tensor `t` (or of the parameter stored at address `t`) under cfg.grad_sink, else None."""
-    if cfg.grad_sink is None or t is None:
-        return None
-    return cfg.grad_sink.view(t if isinstance(t, int) else t.data_ptr())
+def _addresses(*params):
+    """data_ptr() of each parameter (None for an absent one): how a forward records its parameters for _GradSink."""
+    return tuple(None if t is None else t.data_ptr() for t in params)
+
+
+class _GradSink:
+    """Where one backward node's weight / bias gradients go under OpConfig.grad_sink, and what it returns to autograd for them.
+
+    A gradient whose parameter has a slice in the sink (the trainer's "fresh gradients" buffer, train.FlatGrads) is written THERE
+    -- the product's own output buffer -- and autograd receives None for it, so it issues no `grad += new` launch per tensor; the
+    optimiser kernel folds the buffer into the accumulated gradients (fitgnn_adam_step_acc_f32).  The contract: one write per
+    parameter per backward; the write replaces.  A parameter must therefore feed ONE sink-writing node per backward (a second write
+    would replace the first, not add to it).  Built per backward from cfg.grad_sink (None: every gradient goes to autograd)."""
+    __slots__ = ("_sink", "_slices")
+
+    def __init__(self, grad_sink):
+        self._sink, self._slices = grad_sink, []
+
+    def slice(self, ptr):
+        """The sink's slice of the parameter stored at address `ptr` (an output buffer for its gradient), else None."""
+        if self._sink is None or ptr is None:
+            return None
+        s = self._sink.view(ptr)
+        if s is not None:
+            self._slices.append(s)
+        return s
+
+    def buffer(self, ptr, shape, device):
+        """An output buffer for the gradient of the parameter at `ptr`: its sink slice, else a fresh tensor."""
+        s = self.slice(ptr)
+        return s if s is not None else torch.empty(shape, dtype=torch.float32, device=device)
+
+    def result(self, grad):
+        """What autograd receives for a computed gradient: None when it is a sink slice (already where it belongs)."""
+        return None if any(grad is s for s in self._slices) else grad
 
 
 def mm(a, b):
@@ -1264,8 +1291,8 @@ class MeanPoolHead(torch.autograd.Function):
                                           _lib.dptr(pi.inv_cnt), _lib.dptr(W), _lib.dptr(bl), C, _lib.dptr(pooled), _lib.dptr(y),
                                           _lib.stream_ptr(x.device)), "fitgnn_pool_head_f32")
         ctx.save_for_backward(pooled, W)
-        ctx.pi, ctx.shape, ctx.cfg = pi, (n, F_), cfg
-        ctx.W_ptr, ctx.b_ptr = Wl.data_ptr(), (bl.data_ptr() if bl is not None else None)
+        ctx.pi, ctx.shape, ctx.cfg, ctx.has_bl = pi, (n, F_), cfg, bl is not None
+        ctx.ptrs = _addresses(Wl, bl)
         return y
 
     @staticmethod
@@ -1277,14 +1304,13 @@ class MeanPoolHead(torch.autograd.Function):
         dy = _f32c(dy)
         dev = dy.device
         dx = torch.empty((n, F_), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        sW = _sink(cfg, ctx.W_ptr) if ctx.needs_input_grad[2] else None
-        sb = _sink(cfg, ctx.b_ptr) if (ctx.b_ptr is not None and ctx.needs_input_grad[3]) else None
-        dW = (sW if sW is not None else torch.empty((C, F_), dtype=torch.float32, device=dev)) if ctx.needs_input_grad[2] else None
-        db = (sb if sb is not None else torch.empty(C, dtype=torch.float32, device=dev)) if (ctx.b_ptr is not None and ctx.needs_input_grad[3]) else None
+        sink, (pW, pb) = _GradSink(cfg.grad_sink), ctx.ptrs
+        dW = sink.buffer(pW, (C, F_), dev) if ctx.needs_input_grad[2] else None
+        db = sink.buffer(pb, C, dev) if (ctx.has_bl and ctx.needs_input_grad[3]) else None
         _lib.check(L.fitgnn_pool_head_bwd_f32(_lib.dptr(dy), _lib.dptr(W), C, _lib.dptr(pooled), _lib.dptr(pi.seg_of_row), _lib.dptr(pi.inv_cnt),
                                               n if dx is not None else 0, pi.n_seg, F_, _lib.dptr(dx), _lib.dptr(dW), _lib.dptr(db),
                                               _lib.stream_ptr(dev)), "fitgnn_pool_head_bwd_f32")
-        return dx, None, (None if sW is not None else dW), (None if sb is not None else db), None
+        return dx, None, sink.result(dW), sink.result(db), None
 
 
 def pool_supported(x):
@@ -1399,6 +1425,21 @@ class SpMMRows(torch.autograd.Function):
         return spmm_raw(t.rowptr, t.col, t.val, t.tiles, _f32c(dY), ctx.sub.n, window_rows=ctx.sub.window_rows, cfg=ctx.cfg), None, None
 
 
+class _Epilogue:
+    """The activation epilogue of one fused layer: out = dropout(ELU(z + b)), the dropout only while training with p > 0.
+    fwd / bwd: the flags of the forward kernel (bias included) / of the epilogue's derivative; p, mask: what the kernels get (0 and
+    None without dropout); seed as given.  act=False: the bias alone (GATConv without its ELU / dropout)."""
+    __slots__ = ("fwd", "bwd", "drop", "p", "seed", "mask")
+
+    def __init__(self, has_bias, p, training, seed, mask, act=True):
+        self.drop = bool(act) and bool(training) and p > 0.0
+        epi = EPI_ELU if act else 0
+        if self.drop:
+            epi |= EPI_DROPOUT
+        self.bwd, self.fwd = epi, epi | (EPI_BIAS if has_bias else 0)
+        self.p, self.seed, self.mask = (p if self.drop else 0.0), seed, (mask if self.drop else None)
+
+
 class EpilogueLink:
     """Connects a fused layer (producer of out = dropout(ELU(z))) with the ONE layer that consumes `out` as its input.
     The producer's forward records its epilogue here; the consumer's backward (which runs first) may then return
@@ -1418,6 +1459,19 @@ class EpilogueLink:
         self.p, self.seed, self.mask, self.want_db = (p if drop else 0.0), seed, (mask if drop else None), bool(want_db)
         self.fused, self.db, self.g, self.aggregated = False, None, g, False
 
+    def hand_back(self, db, aggregated=False):
+        """Consumer side: the gradient it returns on this edge is the producer's dZ (aggregated: A_hat^T dZ), db its bias gradient."""
+        self.fused, self.db, self.aggregated = True, db, aggregated
+
+    def take(self):
+        """Producer side: (db, aggregated) as handed back by the consumer, or None when it handed back the plain gradient.  Resets
+        the link."""
+        if not self.fused:
+            return None
+        got = (self.db, self.aggregated)
+        self.fused, self.db, self.aggregated = False, None, False
+        return got
+
 
 def _dx_through_link(cfg, link, dH, W, X):
     """dX = dH @ W for the consumer of a linked layer (tensor to return as the input gradient): with cfg.fuse_dx_epilogue
@@ -1430,22 +1484,22 @@ def _dx_through_link(cfg, link, dH, W, X):
         if _nt_ok(dH, Wt, cfg):
             dZ, db = gemm_nt_epilogue_bwd(dH, Wt, X, link.epi, p=link.p, seed=link.seed, mask=link.mask, want_db=link.want_db,
                                           cfg=cfg)
-            link.fused, link.db = True, db
+            link.hand_back(db)
             return dZ
     return mm_by_transposed(dH, W, cfg)
 
 
-def _producer_backward(cfg, link, g, out, epi, p, seed, mask, has_bias, dOut, db_out=None):
-    """(dH, db) of a fused layer: through the link when its consumer already applied the epilogue's derivative.  db_out: a buffer the
-    bias gradient may be written to (it is then the returned db itself -- check identity)."""
-    if link is not None and link.fused:
-        db, aggregated = link.db, link.aggregated
-        link.fused, link.db, link.aggregated = False, None, False
+def _producer_backward(cfg, link, g, out, ep, mask, has_bias, dOut, db_out=None):
+    """(dH, db) of a fused layer with epilogue ep: through the link when its consumer already applied the epilogue's derivative.
+    db_out: a buffer the bias gradient may be written to (it is then the returned db itself -- check identity)."""
+    taken = link.take() if link is not None else None
+    if taken is not None:
+        db, aggregated = taken
         if aggregated:   # the consumer's backward already ran this layer's SpMM over dZ (two-hop)
             return _f32c(dOut), db
         return spmm_graph(g, _f32c(dOut), transposed=True, cfg=cfg), db
     plain = not (cfg.fold_backward and getattr(g, "fold_ok", False))
-    dH, db, _ = layer_backward(g, out, epi, p, seed, mask, has_bias, dOut=dOut, cfg=cfg, db_out=db_out if plain else None)
+    dH, db, _ = layer_backward(g, out, ep.bwd, ep.p, ep.seed, mask, has_bias, dOut=dOut, cfg=cfg, db_out=db_out if plain else None)
     return dH, db
 
 
@@ -1457,38 +1511,26 @@ class FusedGCNLayer(torch.autograd.Function):
     def forward(ctx, X, W, b, g, p, training, seed, mask, link_in, link_out, cfg):
         X = _f32c(X)
         Hm = mm_xwt(X, W, cfg)
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
-        out = spmm_graph(g, Hm, bias=b, epilogue=epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None, cfg=cfg)
-        ctx.save_for_backward(X, W, out, mask if drop else None)
-        ctx.g, ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.cfg = g, p, drop, seed, b is not None, cfg
+        ep = _Epilogue(b is not None, p, training, seed, mask)
+        out = spmm_graph(g, Hm, bias=b, epilogue=ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg)
+        ctx.save_for_backward(X, W, out, ep.mask)
+        ctx.g, ctx.ep, ctx.has_bias, ctx.cfg = g, ep, b is not None, cfg
         ctx.link_in, ctx.link_out = link_in, link_out
-        ctx.b_ptr = b.data_ptr() if b is not None else None
+        ctx.ptrs = _addresses(W, b)
         if link_out is not None:
-            link_out.record(drop, p, seed, mask, b is not None, g=g)
+            link_out.record(ep.drop, ep.p, ep.seed, ep.mask, b is not None, g=g)
         return out
 
     @staticmethod
     def backward(ctx, dOut):
         X, W, out, mask = ctx.saved_tensors
-        g = ctx.g
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
         cfg = ctx.cfg
-        sb = _sink(cfg, ctx.b_ptr) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        dH, db = _producer_backward(cfg, ctx.link_out, g, out, epi, ctx.p if ctx.drop else 0.0, ctx.seed, mask, ctx.has_bias, dOut, db_out=sb)
-        if sb is not None and db is sb:
-            db = None   # written to the gradient sink
-        dW = None
-        if ctx.needs_input_grad[1]:
-            sW = _sink(cfg, W)
-            if sW is not None:
-                mm_at_b(dH, X, cfg, out=sW)
-            else:
-                dW = mm_at_b(dH, X, cfg)
+        sink, (pW, pb) = _GradSink(cfg.grad_sink), ctx.ptrs
+        sb = sink.slice(pb) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        dH, db = _producer_backward(cfg, ctx.link_out, ctx.g, out, ctx.ep, mask, ctx.has_bias, dOut, db_out=sb)
+        dW = sink.result(mm_at_b(dH, X, cfg, out=sink.slice(pW))) if ctx.needs_input_grad[1] else None
         dX = _dx_through_link(cfg, ctx.link_in, dH, W, X) if ctx.needs_input_grad[0] else None
-        return dX, dW, (db if ctx.has_bias else None), None, None, None, None, None, None, None, None
+        return dX, dW, (sink.result(db) if ctx.has_bias else None), None, None, None, None, None, None, None, None
 
 
 def narrow_input_supported(x, W, cfg=DEFAULT):
@@ -1525,22 +1567,18 @@ class FusedGCNLayerAggregatedInput(torch.autograd.Function):
         n, K = AX.shape
         H = int(W.shape[0])
         Wc = _f32c(W)
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
+        ep = _Epilogue(b is not None, p, training, seed, mask)
         out = torch.empty((n, H), dtype=torch.float32, device=AX.device)
-        seed_v, epi_v = _seed_arg(seed, epi)
-        m = mask if drop else None
+        seed_v, epi_v = _seed_arg(ep.seed, ep.fwd)
         rc = L.fitgnn_dense_narrow_k_f32(_lib.dptr(AX), AX.stride(0), _lib.dptr(Wc), Wc.stride(0), n, K, H, _lib.dptr(b), epi_v,
-                                         float(p if drop else 0.0), seed_v, _lib.dptr(m), _lib.dptr(out), out.stride(0),
+                                         float(ep.p), seed_v, _lib.dptr(ep.mask), _lib.dptr(out), out.stride(0),
                                          _lib.stream_ptr(AX.device))
         _lib.check(rc, "fitgnn_dense_narrow_k_f32")
-        ctx.save_for_backward(AX, out, m)
-        ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.cfg, ctx.link_out, ctx.H = p, drop, seed, b is not None, cfg, link_out, H
-        ctx.W_ptr, ctx.b_ptr = W.data_ptr(), (b.data_ptr() if b is not None else None)
+        ctx.save_for_backward(AX, out, ep.mask)
+        ctx.ep, ctx.has_bias, ctx.cfg, ctx.link_out, ctx.H = ep, b is not None, cfg, link_out, H
+        ctx.ptrs = _addresses(W, b)
         if link_out is not None:   # g=None: the consumer may hand back dZ, never A_hat^T dZ (this layer has no backward SpMM)
-            link_out.record(drop, p, seed, mask, b is not None, g=None)
+            link_out.record(ep.drop, ep.p, ep.seed, ep.mask, b is not None, g=None)
         return out
 
     @staticmethod
@@ -1550,26 +1588,22 @@ class FusedGCNLayerAggregatedInput(torch.autograd.Function):
         n, K = AX.shape
         H = ctx.H
         dOut = _f32c(dOut)
-        link = ctx.link_out
-        prev, epi = out, EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
-        if link is not None and link.fused:   # the consumer already applied this layer's ELU' / dropout': dOut is dZ
-            link.fused, link.db, link.aggregated = False, None, False
-            prev, epi = None, 0
-        seed_v, epi_v = _seed_arg(ctx.seed, epi)
-        cfg = ctx.cfg
-        sW = _sink(cfg, ctx.W_ptr) if ctx.needs_input_grad[1] else None
-        sb = _sink(cfg, ctx.b_ptr) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        dW = sW if sW is not None else torch.empty((H, K), dtype=torch.float32, device=dOut.device)
-        db = sb if sb is not None else torch.empty(H, dtype=torch.float32, device=dOut.device)
+        ep, link = ctx.ep, ctx.link_out
+        prev, epi = out, ep.bwd
+        if link is not None and link.take() is not None:   # the consumer already applied this layer's ELU' / dropout': dOut is dZ
+            prev, epi = None, 0                            # (and the kernel below forms db from it itself)
+        seed_v, epi_v = _seed_arg(ep.seed, epi)
+        sink, (pW, pb) = _GradSink(ctx.cfg.grad_sink), ctx.ptrs
+        want_dW, want_db = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dW = sink.buffer(pW if want_dW else None, (H, K), dOut.device)
+        db = sink.buffer(pb if want_db else None, H, dOut.device)
         wb = int(L.fitgnn_narrow_atb_workspace_bytes(n, K, H))
         work = torch.empty(wb // 4, dtype=torch.float32, device=dOut.device)
-        rc = L.fitgnn_narrow_atb_f32(_lib.dptr(dOut), dOut.stride(0), _lib.dptr(prev), epi_v, float(ctx.p if ctx.drop else 0.0), seed_v,
+        rc = L.fitgnn_narrow_atb_f32(_lib.dptr(dOut), dOut.stride(0), _lib.dptr(prev), epi_v, float(ep.p), seed_v,
                                      _lib.dptr(mask), _lib.dptr(AX), AX.stride(0), n, K, H, _lib.dptr(dW), _lib.dptr(db), _lib.dptr(work), wb,
                                      _lib.stream_ptr(dOut.device))
         _lib.check(rc, "fitgnn_narrow_atb_f32")
-        dW = dW if (ctx.needs_input_grad[1] and sW is None) else None
-        db = db if (ctx.has_bias and ctx.needs_input_grad[2] and sb is None) else None
-        return None, dW, db, None, None, None, None, None, None
+        return None, (sink.result(dW) if want_dW else None), (sink.result(db) if want_db else None), None, None, None, None, None, None
 
 
 class FusedGCNLayerHead(torch.autograd.Function):
@@ -1587,11 +1621,8 @@ class FusedGCNLayerHead(torch.autograd.Function):
         X = _f32c(X)
         ctx.link_in, ctx.cfg, ctx.loss_rows = link_in, cfg, loss_rows
         Hm = mm_xwt(X, W, cfg)
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
-        out = spmm_graph(g, Hm, bias=b, epilogue=epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None, cfg=cfg)
+        ep = _Epilogue(b is not None, p, training, seed, mask)
+        out = spmm_graph(g, Hm, bias=b, epilogue=ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg)
         if loss_rows is not None and head_rows_supported(out, Wl):
             # rows that never reach the loss are not evaluated (they read as zero): one pass over the kept rows
             y = head_rows(out, loss_rows, Wl, bl)
@@ -1599,19 +1630,17 @@ class FusedGCNLayerHead(torch.autograd.Function):
             y = torch.mm(out, Wl.t())
             if bl is not None:
                 y = y + bl
-        ctx.save_for_backward(X, W, Wl, out, mask if drop else None)
-        ctx.g, ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.has_bl = g, p, drop, seed, b is not None, bl is not None
+        ctx.save_for_backward(X, W, Wl, out, ep.mask)
+        ctx.g, ctx.ep, ctx.has_bias, ctx.has_bl = g, ep, b is not None, bl is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         X, W, Wl, out, mask = ctx.saved_tensors
-        g = ctx.g
         dy = _f32c(dy)
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
-        cfg = ctx.cfg
-        dH, db, dWl = layer_backward(g, out, epi, ctx.p if ctx.drop else 0.0, ctx.seed, mask, ctx.has_bias, dy=dy, Wl=Wl,
-                                     want_dWl=ctx.needs_input_grad[3], cfg=cfg, loss_rows=ctx.loss_rows)
+        cfg, ep = ctx.cfg, ctx.ep
+        dH, db, dWl = layer_backward(ctx.g, out, ep.bwd, ep.p, ep.seed, mask, ctx.has_bias, dy=dy, Wl=Wl, want_dWl=ctx.needs_input_grad[3],
+                                     cfg=cfg, loss_rows=ctx.loss_rows)
         # [R, C] column sums: torch's dim-0 reduction of a tall 3-column matrix takes 50 us, a transposed copy + dim-1
         # reduction 23, the two-pass kernel 9
         dy_l = dy if ctx.loss_rows is None else dy.index_select(0, ctx.loss_rows)
@@ -1628,6 +1657,73 @@ def _arange_rows(g, n, device):
         cache = torch.arange(n, dtype=torch.int64, device=device)
         g._arange_rows = cache
     return cache
+
+
+def _dense_rows(AHc, W, b, rows, ep, cfg):
+    """The dense part of an aggregate-first layer on its kept rows: dropout(ELU(AHc W^T + b)) [n, H], row i with the dropout pattern of
+    original row rows[i]."""
+    outc = mm_xwt(AHc, W, cfg)                                       # [n, H]
+    if not outc.is_contiguous():
+        outc = outc.contiguous()
+    return epilogue_fwd_rows_(outc, rows, b, ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask)
+
+
+def _head_rows_fwd(outc, Wl, bl, rows, n_total, compact_out, g, cfg):
+    """The head y = out Wl^T + bl on the kept rows: [len(rows), C] in the order of `rows` (compact_out), else [n_total, C], zero on every
+    other row."""
+    if _exact(cfg, outc, Wl) and Wl.shape[0] >= 16:
+        # (a head of a few classes stays on head_rows_kernel: a 128-column MFMA tile for 3 columns is slower than its LDS-resident weights)
+        # the head on the kept rows as one more exact-fp32 product: [n, H] @ [C, H]^T on the fp32 MFMA (a 256 x 128 tile of which C
+        # columns are stored: 0.2 ms at S-products against 0.68 ms for head_rows_kernel's LDS-resident weights), bias added after;
+        # the [R, C] form is the same values scattered into zeros
+        y = gemm_exact(outc, Wl, "nt", cfg)
+        if bl is not None:
+            y = y + bl
+        if not compact_out:
+            y = torch.zeros((n_total, y.shape[1]), dtype=torch.float32, device=y.device).index_copy_(0, rows, y)
+        return y
+    if compact_out:
+        return head_rows(outc, _arange_rows(g, rows.numel(), rows.device), Wl, bl, n_total=rows.numel())
+    return head_rows(outc, rows, Wl, bl, n_total=n_total)
+
+
+def _head_rows_bwd(dy, rows, compact_out, outc, Wl, ep, mask, has_bias, want_dWl, want_dbl, cfg, sink, pb=None, pWl=None, pbl=None):
+    """Backward of the epilogue and the head on the kept rows: (dZc [n, H], db, dWl, dbl).  The head's weight gradient in the
+    epilogue-backward kernel where it takes the head, else its own product.  pb / pWl / pbl: addresses of the parameters whose
+    gradients may go to `sink` (None: to autograd)."""
+    H, C = outc.shape[1], Wl.shape[0]
+    dy_c = _f32c(dy) if compact_out else _f32c(dy).index_select(0, rows)   # [n, C]
+    inside = want_dWl and bool(_lib.lib().fitgnn_epilogue_bwd_head_supported(H, C, 1))
+    dZc, db, dWl = epilogue_bwd_head_rows_raw(dy_c, Wl, outc, rows, ep.bwd, p=ep.p, seed=ep.seed, mask=mask, want_db=has_bias,
+                                              want_dWl=inside, inputs_compact=True, zero_rows=0, db_out=sink.slice(pb),
+                                              dWl_out=sink.slice(pWl) if inside else None)
+    if want_dWl and not inside:
+        dWl = head_weight_grad_rows(dy_c, outc, cfg)
+    dbl = colsum_narrow(dy_c, out=sink.slice(pbl)) if want_dbl else None
+    return dZc, sink.result(db), sink.result(dWl), sink.result(dbl)
+
+
+def _rows_adjoint(g, dZc, W, rows, link, Xprev, cfg, zero_tail, two_hop=False):
+    """dX = A_hat^T dAH of an aggregate-first layer, dAH = dZ W on the kept rows, read in compact form [n + ZERO_ROWS, K] through a row
+    indirection (every edge aggregated).  Xprev (the input, kept when link's producer has its ELU' / dropout' applied here): that is
+    done as the rows are stored and handed back on link.  zero_tail: fill dAH's zero rows; two_hop: the two-hop pass may run."""
+    n, K = dZc.shape[0], W.shape[1]
+    dAH = torch.empty((n + ZERO_ROWS, K), dtype=torch.float32, device=dZc.device)
+    if zero_tail:
+        dAH[n:].zero_()
+    mm_by_transposed(dZc, W, cfg, out=dAH[:n])                       # dZ @ W on the kept rows, stored in place
+    if two_hop and Xprev is not None and two_hop_supported(g, link, dAH, Xprev, cfg):
+        # ... and the producing layer's own backward SpMM over that dZ in the same pass: what travels back is A_hat^T dZ
+        dX, db_prev = spmm_two_hop_blocks(g, dAH, Xprev, rows, _compact_positions(g, rows), link, cfg=cfg)
+        link.hand_back(db_prev, aggregated=True)
+    elif Xprev is not None:
+        # the producing layer's ELU' / dropout' applied as the rows are stored: what travels back on this edge is its dZ
+        dX, db_prev = spmm_graph_dz(g, dAH, Xprev, link.epi, p=link.p, seed=link.seed, mask=link.mask, want_db=link.want_db,
+                                    xrow=_compact_positions(g, rows), cfg=cfg, profile_kind="compact_dz", zero_from=n)
+        link.hand_back(db_prev)
+    else:
+        dX = spmm_graph(g, dAH, transposed=True, cfg=cfg, xrow=_compact_positions(g, rows), profile_kind="compact", zero_from=n)
+    return dX
 
 
 class FusedGCNLastLayerRows(torch.autograd.Function):
@@ -1658,88 +1754,27 @@ class FusedGCNLastLayerRows(torch.autograd.Function):
             AH = spmm_graph(g, X, cfg=cfg)                               # [R, K]
             AHc = AH.index_select(0, rows)                               # [n, K]
             del AH
-        outc = mm_xwt(AHc, W, cfg)                                       # [n, H]
-        if not outc.is_contiguous():
-            outc = outc.contiguous()
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
-        epilogue_fwd_rows_(outc, rows, b, epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None)
-        if _exact(cfg, outc, Wl) and Wl.shape[0] >= 16:
-            # (a head of a few classes stays on head_rows_kernel: a 128-column MFMA tile for 3 columns is slower than its LDS-resident weights)
-            # the head on the kept rows as one more exact-fp32 product: [n, H] @ [C, H]^T on the fp32 MFMA (a 256 x 128 tile of which C
-            # columns are stored: 0.2 ms at S-products against 0.68 ms for head_rows_kernel's LDS-resident weights), bias added after;
-            # the [R, C] form is the same values scattered into zeros
-            y = gemm_exact(outc, Wl, "nt", cfg)
-            if bl is not None:
-                y = y + bl
-            if not compact_out:
-                y = torch.zeros((g.n, y.shape[1]), dtype=torch.float32, device=y.device).index_copy_(0, rows, y)
-        elif compact_out:
-            y = head_rows(outc, _arange_rows(g, rows.numel(), rows.device), Wl, bl, n_total=rows.numel())
-        else:
-            y = head_rows(outc, rows, Wl, bl, n_total=g.n)
+        ep = _Epilogue(b is not None, p, training, seed, mask)
+        outc = _dense_rows(AHc, W, b, rows, ep, cfg)                     # [n, H]
+        y = _head_rows_fwd(outc, Wl, bl, rows, g.n, compact_out, g, cfg)
         # X (the previous layer's output) is kept only when that layer's epilogue backward is applied here, in the SpMM's store
         keep_x = link_in is not None and cfg.fuse_dx_epilogue and X.shape[1] % 4 == 0
-        ctx.save_for_backward(W, Wl, AHc, outc, rows, mask if drop else None, X if keep_x else None)
-        ctx.g, ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.has_bl, ctx.cfg = g, p, drop, seed, b is not None, bl is not None, cfg
-        ctx.ptrs = (W.data_ptr(), b.data_ptr() if b is not None else None, Wl.data_ptr(), bl.data_ptr() if bl is not None else None)
+        ctx.save_for_backward(W, Wl, AHc, outc, rows, ep.mask, X if keep_x else None)
+        ctx.g, ctx.ep, ctx.has_bias, ctx.has_bl, ctx.cfg = g, ep, b is not None, bl is not None, cfg
+        ctx.ptrs = _addresses(W, b, Wl, bl)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         W, Wl, AHc, outc, rows, mask, Xprev = ctx.saved_tensors
-        g, cfg = ctx.g, ctx.cfg
-        L = _lib.lib()
-        H, C = outc.shape[1], Wl.shape[0]
-        dy_c = _f32c(dy) if ctx.compact_out else _f32c(dy).index_select(0, rows)   # [n, C]
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
-        inside = ctx.needs_input_grad[3] and bool(L.fitgnn_epilogue_bwd_head_supported(H, C, 1))
+        cfg = ctx.cfg
         # weight / bias gradients go straight to the trainer's gradient sink where there is one (OpConfig.grad_sink): no `grad += new`
-        pW, pb, pWl, pbl = ctx.ptrs
-        sW = _sink(cfg, pW) if ctx.needs_input_grad[1] else None
-        sb = _sink(cfg, pb) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        sWl = _sink(cfg, pWl) if inside else None
-        sbl = _sink(cfg, pbl) if (ctx.has_bl and ctx.needs_input_grad[4]) else None
-        dZc, db, dWl = epilogue_bwd_head_rows_raw(dy_c, Wl, outc, rows, epi, p=ctx.p if ctx.drop else 0.0, seed=ctx.seed, mask=mask,
-                                                  want_db=ctx.has_bias, want_dWl=inside, inputs_compact=True, zero_rows=0, db_out=sb,
-                                                  dWl_out=sWl)
-        if sb is not None:
-            db = None
-        if sWl is not None:
-            dWl = None
-        if ctx.needs_input_grad[3] and not inside:
-            dWl = head_weight_grad_rows(dy_c, outc, cfg)
-        dbl = None
-        if ctx.has_bl and ctx.needs_input_grad[4]:
-            dbl = colsum_narrow(dy_c, out=sbl)
-            if sbl is not None and dbl is sbl:
-                dbl = None
-        dW = None
-        if ctx.needs_input_grad[1]:   # [H, K]
-            if sW is not None:
-                mm_at_b(dZc, AHc, cfg, out=sW)
-            else:
-                dW = mm_at_b(dZc, AHc, cfg)
-        dX = None
-        if ctx.needs_input_grad[0]:
-            n, K = AHc.shape
-            dAH = torch.empty((n + ZERO_ROWS, K), dtype=torch.float32, device=dZc.device)
-            dAH[n:].zero_()
-            mm_by_transposed(dZc, W, cfg, out=dAH[:n])                   # dZ @ W on the loss rows, stored in place
-            link = ctx.link_in
-            if Xprev is not None and two_hop_supported(g, link, dAH, Xprev, cfg):
-                # ... and the producing layer's own backward SpMM over that dZ in the same pass: what travels back is A_hat^T dZ
-                dX, db_prev = spmm_two_hop_blocks(g, dAH, Xprev, rows, _compact_positions(g, rows), link, cfg=cfg)
-                link.fused, link.db, link.aggregated = True, db_prev, True
-            elif Xprev is not None:
-                # the producing layer's ELU' / dropout' applied as the rows are stored: what travels back on this edge is its dZ
-                dX, db_prev = spmm_graph_dz(g, dAH, Xprev, link.epi, p=link.p, seed=link.seed, mask=link.mask, want_db=link.want_db,
-                                            xrow=_compact_positions(g, rows), cfg=cfg, profile_kind="compact_dz", zero_from=n)
-                link.fused, link.db = True, db_prev
-            else:
-                dX = spmm_graph(g, dAH, transposed=True, cfg=cfg, xrow=_compact_positions(g, rows), profile_kind="compact", zero_from=n)
+        sink, (pW, pb, pWl, pbl) = _GradSink(cfg.grad_sink), ctx.ptrs
+        dZc, db, dWl, dbl = _head_rows_bwd(dy, rows, ctx.compact_out, outc, Wl, ctx.ep, mask, ctx.has_bias, ctx.needs_input_grad[3],
+                                           ctx.has_bl and ctx.needs_input_grad[4], cfg, sink, pb=pb if ctx.needs_input_grad[2] else None,
+                                           pWl=pWl, pbl=pbl)
+        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW))) if ctx.needs_input_grad[1] else None   # [H, K]
+        dX = _rows_adjoint(ctx.g, dZc, W, rows, ctx.link_in, Xprev, cfg, zero_tail=True, two_hop=True) if ctx.needs_input_grad[0] else None
         return dX, dW, (db if ctx.has_bias else None), dWl, dbl, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1758,54 +1793,26 @@ class FusedGCNLayerRows(torch.autograd.Function):
         X = _f32c(X)
         rows = rows if rows.dtype == torch.int64 else rows.long()
         AHc = spmm_graph(g, X, cfg=cfg).index_select(0, rows)          # [n, K]
-        outc = mm_xwt(AHc, W, cfg)
-        if not outc.is_contiguous():
-            outc = outc.contiguous()
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
-        epilogue_fwd_rows_(outc, rows, b, epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None)
+        ep = _Epilogue(b is not None, p, training, seed, mask)
+        outc = _dense_rows(AHc, W, b, rows, ep, cfg)
         keep_x = link_in is not None and cfg.fuse_dx_epilogue and X.shape[1] % 4 == 0
-        ctx.save_for_backward(W, AHc, outc, rows, mask if drop else None, X if keep_x else None)
-        ctx.g, ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.cfg, ctx.link_in = g, p, drop, seed, b is not None, cfg, link_in
-        ctx.ptrs = (W.data_ptr(), b.data_ptr() if b is not None else None)
+        ctx.save_for_backward(W, AHc, outc, rows, ep.mask, X if keep_x else None)
+        ctx.g, ctx.ep, ctx.has_bias, ctx.cfg, ctx.link_in = g, ep, b is not None, cfg, link_in
+        ctx.ptrs = _addresses(W, b)
         return outc
 
     @staticmethod
     def backward(ctx, dOutc):
         W, AHc, outc, rows, mask, Xprev = ctx.saved_tensors
-        g, cfg = ctx.g, ctx.cfg
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
-        pW, pb = ctx.ptrs
-        sW = _sink(cfg, pW) if ctx.needs_input_grad[1] else None
-        sb = _sink(cfg, pb) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        dZc, db = epilogue_bwd_rows_raw(dOutc, outc, rows, epi, p=ctx.p if ctx.drop else 0.0, seed=ctx.seed, mask=mask, want_db=ctx.has_bias,
-                                        db_out=sb)
-        if sb is not None:
-            db = None
-        dW = None
-        if ctx.needs_input_grad[1]:
-            if sW is not None:
-                mm_at_b(dZc, AHc, cfg, out=sW)
-            else:
-                dW = mm_at_b(dZc, AHc, cfg)
-        dX = None
-        if ctx.needs_input_grad[0]:
-            n, K = AHc.shape
-            # rows [n, n + ZERO_ROWS) stand for the rows outside the selection: every kernel that takes zero_from treats them as zeros
-            # WITHOUT loading them (staged as zeros / read from a row of zeros in LDS / multiplied from registers), so they are not filled
-            dAH = torch.empty((n + ZERO_ROWS, K), dtype=torch.float32, device=dZc.device)
-            mm_by_transposed(dZc, W, cfg, out=dAH[:n])
-            link = ctx.link_in
-            pos = _compact_positions(g, rows)
-            if Xprev is not None:
-                dX, db_prev = spmm_graph_dz(g, dAH, Xprev, link.epi, p=link.p, seed=link.seed, mask=link.mask, want_db=link.want_db, xrow=pos,
-                                            cfg=cfg, profile_kind="compact_dz", zero_from=n)
-                link.fused, link.db = True, db_prev
-            else:
-                dX = spmm_graph(g, dAH, transposed=True, cfg=cfg, xrow=pos, profile_kind="compact", zero_from=n)
-        return dX, dW, (db if ctx.has_bias else None), None, None, None, None, None, None, None, None
+        cfg, ep = ctx.cfg, ctx.ep
+        sink, (pW, pb) = _GradSink(cfg.grad_sink), ctx.ptrs
+        sb = sink.slice(pb) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        dZc, db = epilogue_bwd_rows_raw(dOutc, outc, rows, ep.bwd, p=ep.p, seed=ep.seed, mask=mask, want_db=ctx.has_bias, db_out=sb)
+        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW))) if ctx.needs_input_grad[1] else None
+        # rows [n, n + ZERO_ROWS) of dAH stand for the rows outside the selection: every kernel that takes zero_from treats them as zeros
+        # WITHOUT loading them (staged as zeros / read from a row of zeros in LDS / multiplied from registers), so they are not filled
+        dX = _rows_adjoint(ctx.g, dZc, W, rows, ctx.link_in, Xprev, cfg, zero_tail=False) if ctx.needs_input_grad[0] else None
+        return dX, dW, (sink.result(db) if ctx.has_bias else None), None, None, None, None, None, None, None, None
 
 
 class FusedGCNLayerDedup(torch.autograd.Function):
@@ -1828,39 +1835,32 @@ class FusedGCNLayerDedup(torch.autograd.Function):
             Ht = gemm_exact(Xp, padded_weight(W, Xp.shape[1]), "nt", cfg)
         else:
             Ht = gemm_nt_padded_k(padded_table(Xt), W, cfg) if ctx.wide else mm_xwt(Xt, W, cfg)  # [N0, H]
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
+        ep = _Epilogue(b is not None, p, training, seed, mask)
         # the direct-gather SpMM variant: its operand table stays in L2 / MALL (5-12 us per S-pubmed step over the LDS-window
         # kernel, same bits)
-        out = spmm_graph(g, Ht, bias=b, epilogue=epi | (_lib.SPMM_GATHER if cfg.dedup_gather else 0), p=p if drop else 0.0, seed=seed,
-                         mask=mask if drop else None, xrow=ridx.index, cfg=cfg)
-        ctx.save_for_backward(Xt, W, out, mask if drop else None)
-        ctx.g, ctx.ridx, ctx.p, ctx.drop, ctx.seed, ctx.has_bias = g, ridx, p, drop, seed, b is not None
+        out = spmm_graph(g, Ht, bias=b, epilogue=ep.fwd | (_lib.SPMM_GATHER if cfg.dedup_gather else 0), p=ep.p, seed=ep.seed, mask=ep.mask,
+                         xrow=ridx.index, cfg=cfg)
+        ctx.save_for_backward(Xt, W, out, ep.mask)
+        ctx.g, ctx.ridx, ctx.ep, ctx.has_bias = g, ridx, ep, b is not None
+        ctx.ptrs = _addresses(W)
         if link_out is not None:
-            link_out.record(drop, p, seed, mask, b is not None, g=g)
+            link_out.record(ep.drop, ep.p, ep.seed, ep.mask, b is not None, g=g)
         return out
 
     @staticmethod
     def backward(ctx, dOut):
         Xt, W, out, mask = ctx.saved_tensors
         g, ridx = ctx.g, ctx.ridx
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
         cfg = ctx.cfg
-        dH, db = _producer_backward(cfg, ctx.link_out, g, out, epi, ctx.p if ctx.drop else 0.0, ctx.seed, mask, ctx.has_bias, dOut)  # [R, H]
+        dH, db = _producer_backward(cfg, ctx.link_out, g, out, ctx.ep, mask, ctx.has_bias, dOut)  # [R, H]
         dHt = segment_sum(ridx.seg_off, ridx.members, dH, ridx.n_table)  # [N0, H] per original node
         if ctx.exact_pad and ctx.needs_input_grad[1]:
             dW = gemm_exact(_f32c(dHt), padded_table(Xt), "tn", cfg)[:, : Xt.shape[1]]
         elif ctx.wide and ctx.needs_input_grad[1]:
             dW = gemm_atb(_f32c(dHt), padded_table(Xt), cfg)[:, : Xt.shape[1]]   # [H, F'] on the padded table, F' - F zero columns dropped
         elif ctx.needs_input_grad[1]:
-            sW = _sink(cfg, W)
-            if sW is not None:
-                mm_at_b(dHt, Xt, cfg, out=sW)
-                dW = None
-            else:
-                dW = mm_at_b(dHt, Xt, cfg)
+            sink, (pW,) = _GradSink(cfg.grad_sink), ctx.ptrs
+            dW = sink.result(mm_at_b(dHt, Xt, cfg, out=sink.slice(pW)))
         else:
             dW = None
         dXt = mm(dHt, W) if ctx.needs_input_grad[0] else None
@@ -1898,19 +1898,16 @@ class GATAggregate(torch.autograd.Function):
         with _timed(cfg, "gat_edge_softmax"):
             _lib.check(L.fitgnn_gat_edge_softmax_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(a_src), _lib.dptr(a_dst),
                                                      float(slope), n, _lib.dptr(alpha), st), "gat_edge_softmax")
-        epi = EPI_BIAS if bias is not None else 0
-        drop = bool(act) and bool(training) and p > 0.0
-        if act:
-            epi |= EPI_ELU | (EPI_DROPOUT if drop else 0)
+        ep = _Epilogue(bias is not None, p, training, seed, mask, act=act)
         # (a union whose runs go to the whole-subgraph kernel takes it here too: the attention weights are the launch's CSR values)
-        out = spmm_graph(g, h, val=alpha, bias=bias, epilogue=epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None, cfg=cfg,
+        out = spmm_graph(g, h, val=alpha, bias=bias, epilogue=ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg,
                          profile_kind="gat_aggregate", xrow=None if ridx is None else ridx.index)
-        ctx.save_for_backward(h, att_src, att_dst, a_src, a_dst, alpha, out if act else None, mask if drop else None)
+        ctx.save_for_backward(h, att_src, att_dst, a_src, a_dst, alpha, out if act else None, ep.mask)
         ctx.g, ctx.slope, ctx.has_bias, ctx.cfg, ctx.ridx = g, slope, bias is not None, cfg, ridx
-        ctx.act, ctx.drop, ctx.p, ctx.seed = bool(act), drop, p, seed
+        ctx.act, ctx.ep = bool(act), ep
         ctx.link_out = link_out if act else None
         if ctx.link_out is not None:   # g=None: the consumer may hand back dZ, never an aggregated form of it
-            link_out.record(drop, p, seed, mask, bias is not None, g=None)
+            link_out.record(ep.drop, ep.p, ep.seed, ep.mask, bias is not None, g=None)
         return out
 
     @staticmethod
@@ -1919,15 +1916,13 @@ class GATAggregate(torch.autograd.Function):
         g, L = ctx.g, _lib.lib()
         dOut = _f32c(dOut)
         db_fused = None
-        cfg = ctx.cfg
-        link = ctx.link_out
-        if ctx.act and link is not None and link.fused:   # the consumer already applied this layer's ELU' / dropout': dOut is dZ
-            db_fused = link.db
-            link.fused, link.db, link.aggregated = False, None, False
+        cfg, ep = ctx.cfg, ctx.ep
+        taken = ctx.link_out.take() if ctx.link_out is not None else None   # (a link only with act)
+        if taken is not None:   # the consumer already applied this layer's ELU' / dropout': dOut is dZ
+            db_fused = taken[0]
         elif ctx.act:   # through ELU / dropout first: dOut becomes the gradient of the pre-activation, db its column sums
             with _timed(cfg, "gat_epilogue_bwd"):
-                dOut, db_fused = epilogue_bwd_raw(dOut, out, EPI_ELU | (EPI_DROPOUT if ctx.drop else 0), p=ctx.p if ctx.drop else 0.0,
-                                                  seed=ctx.seed, mask=mask, want_db=ctx.has_bias)
+                dOut, db_fused = epilogue_bwd_raw(dOut, out, ep.bwd, p=ep.p, seed=ep.seed, mask=mask, want_db=ctx.has_bias)
         C = h.shape[1]
         n = g.n
         ridx = ctx.ridx
@@ -2031,27 +2026,12 @@ class FusedGATLastLayerRows(torch.autograd.Function):
         AX = spmm_graph(g, X, val=alpha, cfg=cfg, profile_kind="gat_aggregate")                   # [R, K]: every row, every edge
         AXc = AX.index_select(0, rows)
         del AX
-        outc = mm_xwt(AXc, W, cfg)
-        if not outc.is_contiguous():
-            outc = outc.contiguous()
-        epi = EPI_ELU | (EPI_BIAS if b is not None else 0)
-        drop = bool(training) and p > 0.0
-        if drop:
-            epi |= EPI_DROPOUT
-        epilogue_fwd_rows_(outc, rows, b, epi, p=p if drop else 0.0, seed=seed, mask=mask if drop else None)
-        if _exact(cfg, outc, Wl) and Wl.shape[0] >= 16:
-            y = gemm_exact(outc, Wl, "nt", cfg)
-            if bl is not None:
-                y = y + bl
-            if not compact_out:
-                y = torch.zeros((R, y.shape[1]), dtype=torch.float32, device=dev).index_copy_(0, rows, y)
-        elif compact_out:
-            y = head_rows(outc, _arange_rows(g, rows.numel(), dev), Wl, bl, n_total=rows.numel())
-        else:
-            y = head_rows(outc, rows, Wl, bl, n_total=R)
-        ctx.save_for_backward(X, W, att2, Wl, AXc, outc, rows, mask if drop else None, alpha, a_src, a_dst, u)
-        ctx.g, ctx.slope, ctx.p, ctx.drop, ctx.seed, ctx.has_bias, ctx.has_bl, ctx.cfg, ctx.compact_out = (
-            g, slope, p, drop, seed, b is not None, bl is not None, cfg, bool(compact_out))
+        ep = _Epilogue(b is not None, p, training, seed, mask)
+        outc = _dense_rows(AXc, W, b, rows, ep, cfg)
+        y = _head_rows_fwd(outc, Wl, bl, rows, R, compact_out, g, cfg)
+        ctx.save_for_backward(X, W, att2, Wl, AXc, outc, rows, ep.mask, alpha, a_src, a_dst, u)
+        ctx.g, ctx.slope, ctx.ep, ctx.has_bias, ctx.has_bl, ctx.cfg, ctx.compact_out = (
+            g, slope, ep, b is not None, bl is not None, cfg, bool(compact_out))
         ctx.link_in = link_in   # X is the un-shared output of a fused layer: its ELU' / dropout' may go into the adjoint aggregation's store
         return y
 
@@ -2061,16 +2041,10 @@ class FusedGATLastLayerRows(torch.autograd.Function):
         g, cfg, L = ctx.g, ctx.cfg, _lib.lib()
         dev, st = X.device, _lib.stream_ptr(X.device)
         R, K = X.shape
-        H, C = outc.shape[1], Wl.shape[0]
         n = int(rows.numel())
-        dy_c = _f32c(dy) if ctx.compact_out else _f32c(dy).index_select(0, rows)
-        epi = EPI_ELU | (EPI_DROPOUT if ctx.drop else 0)
-        inside = ctx.needs_input_grad[5] and bool(L.fitgnn_epilogue_bwd_head_supported(H, C, 1))
-        dZc, db, dWl = epilogue_bwd_head_rows_raw(dy_c, Wl, outc, rows, epi, p=ctx.p if ctx.drop else 0.0, seed=ctx.seed, mask=mask,
-                                                  want_db=ctx.has_bias, want_dWl=inside, inputs_compact=True, zero_rows=0)
-        if ctx.needs_input_grad[5] and not inside:
-            dWl = head_weight_grad_rows(dy_c, outc, cfg)
-        dbl = colsum_narrow(dy_c) if ctx.has_bl and ctx.needs_input_grad[6] else None
+        # (no gradient sink here: every gradient goes to autograd)
+        dZc, db, dWl, dbl = _head_rows_bwd(dy, rows, ctx.compact_out, outc, Wl, ctx.ep, mask, ctx.has_bias, ctx.needs_input_grad[5],
+                                           ctx.has_bl and ctx.needs_input_grad[6], cfg, _GradSink(None))
         dW = mm_at_b(dZc, AXc, cfg)                                                               # [H, K]
         # the compact gradient of the aggregation's output: rows 0..n-1 = dZ W on the loss rows; with the rank-2 term folded into the
         # adjoint aggregation (below) rows n, n + 1 carry u = W^T att, and the zero rows follow
@@ -2127,7 +2101,7 @@ class FusedGATLastLayerRows(torch.autograd.Function):
                     if link.want_db:
                         db_prev = torch.empty(K, dtype=torch.float32, device=dev)
                         _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part), n_part, K, _lib.dptr(db_prev), st), "fitgnn_colsum_partials_f32")
-                    link.fused, link.db = True, db_prev
+                    link.hand_back(db_prev)
                 else:
                     _lib.check(L.fitgnn_spmm_rows_compact_f32(_lib.dptr(rp_aug), _lib.dptr(xcol_aug), _lib.dptr(val_aug), int(xcol_aug.numel()),
                                                               _lib.dptr(op), op.stride(0), n + 2, _lib.dptr(dX), dX.stride(0), R, K, st),
@@ -2508,6 +2482,12 @@ def next_seed(cfg=DEFAULT):
     if cfg.seed_bank is not None:
         return cfg.seed_bank.take()
     return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def dropout_seed(cfg, training, p, mask):
+    """The seed of one layer's dropout: next_seed(cfg) when it drops at random (training, p > 0, no injected mask), else 0 and no
+    draw -- the order and number of draws decide the dropout patterns and the SeedBank cursor of a captured step."""
+    return next_seed(cfg) if (training and p > 0 and mask is None) else 0
 
 
 def _seed_arg(seed, epilogue):

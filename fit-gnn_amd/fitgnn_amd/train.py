@@ -220,13 +220,13 @@ class GDTrainer:
         self.model, self.batch, self.task = model, batch, task
         if op_config is not None:
             model.set_op_config(op_config)
+        _drop_stale_sink(model)   # (before the config is read: self.cfg is the one the model runs under)
         from . import ops as _ops
         self.cfg = getattr(model, "op_config", _ops.DEFAULT)
         self.sub = None
         # first layer on the de-duplicated feature table when the batch carries one (same arithmetic, fewer FLOPs)
         self.dedup = dedup and getattr(batch, "row_index", None) is not None
         self.flat = FlatGrads(model.parameters())
-        _drop_stale_sink(model)
         if next(model.parameters()).is_cuda:   # one kernel over the flat buffers (same arithmetic as torch.optim.Adam)
             self.opt = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay)
         else:                                  # host-side logic tests (gloo): the reference's optimiser itself

@@ -1282,6 +1282,23 @@ def test_a_stale_autograd_graph_makes_the_trainers_step_eagerly_instead_of_captu
     assert float(tr2.step()) == want and tr2.capture and tr2._graph is not None
 
 
+def test_a_trainer_after_a_lean_one_runs_under_the_models_config_without_its_sink(mods):
+    """A lean GDTrainer leaves its gradient sink on the model's config (ops.OpConfig.grad_sink); a non-lean trainer built on that model
+    afterwards drops it and keeps the very config the model then runs under (profiling hooks set on tr.cfg record the model's launches)."""
+    from fitgnn_amd import train
+
+    network, fnn, gorc = mods
+    batch, _ = _subgraph_batches(seed=6)
+    args = argparse.Namespace(num_layers1=2, layer_name="GCNConv", num_features=24, hidden=32, num_classes=4)
+    torch.manual_seed(5)
+    model = network.Classify_node(args).cuda()
+    tr1 = train.GDTrainer(model, batch, lr=0.01, weight_decay=5e-4)
+    assert tr1.lean and model.op_config.grad_sink is tr1.flat
+    tr2 = train.GDTrainer(model, batch, lr=0.01, weight_decay=5e-4, lean_step=False)
+    assert tr2.cfg is model.op_config
+    assert tr2.cfg.grad_sink is None
+
+
 @pytest.mark.parametrize("cls_name,layers", [("Regress_graph_gs", 2), ("Regress_graph_gs", 1), ("Regress_graph_gs", 3), ("Classify_graph_gs", 2)])
 @pytest.mark.parametrize("mode", ["eval", "masks", "hashed"])
 def test_last_layer_on_the_pooled_rows_changes_nothing_the_pool_sees(mods, cls_name, layers, mode):
