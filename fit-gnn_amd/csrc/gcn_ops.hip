@@ -314,6 +314,13 @@ __global__ __launch_bounds__(256) void narrow_colsum_kernel(const float *__restr
     }
 }
 
+// step_size = lr / (1 - b1^t) and sqrt(1 - b2^t), formed in double as torch forms them: in fp32, 1 - powf(0.999f, t) cancels most
+// of its bits at small t (sqrt(bc2) off by 3e-6 relative at t = 2, fifty times the update's own rounding).
+__device__ __forceinline__ void adam_bias_corrections(float lr, float b1, float b2, float t, float &step_size, float &bc2s) {
+    step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)t)));
+    bc2s = (float)sqrt(1.0 - pow((double)b2, (double)t));
+}
+
 // torch.optim.Adam (amsgrad=False, maximize=False) over one flat parameter buffer: g += wd * p (L2, as torch's
 // weight_decay), m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps).
 // `step` is a device counter (float, as torch keeps it) advanced by thread 0: the update can sit in a captured graph.
@@ -321,8 +328,8 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float4 *__restrict__ p, 
                                                         float4 *__restrict__ v, int64_t n4, float lr, float b1, float b2, float eps,
                                                         float wd, float *__restrict__ step) {
     const float t = *step + 1.0f;
-    const float bc1 = 1.0f - powf(b1, t), bc2s = sqrtf(1.0f - powf(b2, t));
-    const float step_size = lr / bc1;
+    float step_size, bc2s;
+    adam_bias_corrections(lr, b1, b2, t, step_size, bc2s);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n4) {
         float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
@@ -351,8 +358,8 @@ __global__ __launch_bounds__(256) void adam_flat_acc_kernel(float4 *__restrict__
                                                             unsigned long long *__restrict__ seeds, int32_t n_seeds,
                                                             unsigned long long seed_stride) {
     const float t = state[0] + 1.0f;
-    const float bc1 = 1.0f - powf(b1, t), bc2s = sqrtf(1.0f - powf(b2, t));
-    const float step_size = lr / bc1;
+    float step_size, bc2s;
+    adam_bias_corrections(lr, b1, b2, t, step_size, bc2s);
     // four float4 per thread: a quarter of the workgroups, i.e. of the tickets taken below (the atomics of ~260 workgroups were most
     // of the launch on a 270 k-float model)
 #pragma unroll
@@ -930,10 +937,10 @@ extern "C" size_t fitgnn_epilogue_bwd_workspace_bytes(int32_t n_rows, int32_t H)
 
 namespace {
 // Class c's dy value is fetched by lane c of every wave, and only the lanes that own columns of the wave's slab are active:
-// the head must not have more classes than the narrowest (= last) slab has active lanes.
-bool head_supported(int32_t H, int32_t C, bool with_dWl) {
+// the head must not have more classes than the narrowest (= last) slab has active lanes.  vec: the float4 form (256-column
+// slabs, H % 4 == 0 and 16-byte aligned operands), else one column per lane (64-column slabs).
+bool head_supported(int32_t H, int32_t C, bool with_dWl, bool vec) {
     if (H < 1 || C < 1 || C > (with_dWl ? kMaxHeadC : kMaxHeadWide)) return false;
-    const bool vec = (H % 4) == 0;
     const int slab = vec ? 256 : 64, per_lane = vec ? 4 : 1;
     const int last_cols = (H - 1) % slab + 1;
     return C <= last_cols / per_lane;
@@ -947,7 +954,10 @@ int epilogue_bwd_launch(const float *dOut, const float *dy, const float *Wl, int
     if (n_rows == 0 || H == 0) return 0;
     const bool head = dOut == nullptr;
     if (!out || !dZ) return FITGNN_E_BADARG;
-    if (head && (!dy || !Wl || !head_supported(H, C, dWl != nullptr))) return FITGNN_E_BADARG;
+    const bool vec = (H % 4 == 0) && ((((uintptr_t)dOut | (uintptr_t)out | (uintptr_t)dZ) % 16) == 0);
+    if (head && (!dy || !Wl || !head_supported(H, C, dWl != nullptr, H % 4 == 0))) return FITGNN_E_BADARG;
+    // H % 4 == 0 on operands that are not 16-byte aligned takes the one-column form, whose last slab may have fewer lanes
+    if (head && !head_supported(H, C, dWl != nullptr, vec)) return FITGNN_E_ALIGN;
     if (!head && dWl) return FITGNN_E_BADARG;
     if ((epilogue & FITGNN_EPI_DROPOUT) && !(p_drop >= 0.f && p_drop < 1.f)) return FITGNN_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
@@ -957,7 +967,6 @@ int epilogue_bwd_launch(const float *dOut, const float *dy, const float *Wl, int
     if (need && (!work || work_bytes < need)) return FITGNN_E_WORKSPACE;
     float *partial = db ? (float *)work : nullptr;
     float *partialW = dWl ? (float *)work + (db ? (size_t)chunks * H : 0) : nullptr;
-    const bool vec = (H % 4 == 0) && ((((uintptr_t)dOut | (uintptr_t)out | (uintptr_t)dZ) % 16) == 0);
     // x (fastest) = column slab: both halves of every row are in flight together; y = row chunk
     const dim3 grid(vec ? (H + 255) / 256 : (H + 63) / 64, chunks);
 #define FITGNN_LAUNCH_EB(V, HD, CWV)                                                                                     \
@@ -990,7 +999,9 @@ extern "C" int fitgnn_epilogue_bwd_f32(const float *dOut, const float *out, floa
 
 extern "C" int fitgnn_head_max_classes(void) { return kMaxHeadC; }
 extern "C" int fitgnn_head_max_classes_wide(void) { return kMaxHeadWide; }
-extern "C" int fitgnn_epilogue_bwd_head_supported(int32_t H, int32_t C, int32_t with_dWl) { return head_supported(H, C, with_dWl != 0) ? 1 : 0; }
+extern "C" int fitgnn_epilogue_bwd_head_supported(int32_t H, int32_t C, int32_t with_dWl) {
+    return head_supported(H, C, with_dWl != 0, H % 4 == 0) ? 1 : 0;
+}
 
 extern "C" size_t fitgnn_epilogue_bwd_head_workspace_bytes(int32_t n_rows, int32_t H, int32_t C) {
     if (n_rows <= 0 || H <= 0 || C < 0) return 0;

@@ -541,7 +541,9 @@ def softmax_nll_raw(z, idx, labels, scale):
     """(loss, dz): loss = scale * sum_t NLL(log_softmax(z[idx[t]]), labels[t]) as a one-element tensor and dz = d loss / d z, from ONE
     launch (fitgnn_softmax_nll_f32).  z may be a [rows x C] view with a row stride (the padded signal APPNPPropagate returns): it is
     read in place and dz comes back as the same view of an equally strided buffer.  A trainer that owns the step calls
-    z.backward(dz) instead of loss.backward(): the same gradient without the multiplication by autograd's ones."""
+    z.backward(dz) instead of loss.backward(): the same gradient without the multiplication by autograd's ones.  The rows of idx must
+    be distinct (not checked): the kernel writes each selected row's gradient, so a row listed twice would get one term of dz, not
+    their sum."""
     _lib.require_cuda(z, idx, labels)
     L = _lib.lib()
     if z.dtype != torch.float32 or z.stride(1) != 1 or z.stride(0) < z.shape[1]:

@@ -381,7 +381,9 @@ int fitgnn_colsum_partials_f32(const float *partial, int32_t n_chunks, int32_t H
 /* loss[0] = scale * sum_t NLL(log_softmax(z[idx[t]]), labels[t]) over n selected rows (Classify_node's log_softmax,
  * network.py:35, followed by NLLLoss, run.py:341; scale = 1/n for reduction='mean', 1/global count under data
  * parallelism), and dz [n_rows x ldz] = its gradient w.r.t. the logits z (zero on rows that are not selected).
- * One pass over the selected rows instead of log_softmax + gather + nll_loss and their three backward kernels. */
+ * One pass over the selected rows instead of log_softmax + gather + nll_loss and their three backward kernels.
+ * The rows of idx must be distinct (not checked): each selected row's gradient is written, not added, so a row listed twice
+ * would get one term of dz, not the sum of both. */
 /* loss[0] = scale * sum_i |out[i] - tgt[i]| and grad[i] = scale * sign(out[i] - tgt[i]) over n contiguous values: L1Loss of the
  * regression tasks (run.py:518,716; scale = 1/n for reduction='mean') with its gradient, one launch (a fixed-order sum). */
 int fitgnn_l1_loss_f32(const float *out, const float *tgt, int32_t n, float scale, float *loss, float *grad, void *stream);
@@ -426,7 +428,10 @@ int fitgnn_epilogue_bwd_f32(const float *dOut, const float *out, float *dZ, int3
 int fitgnn_head_max_classes(void);
 int fitgnn_head_max_classes_wide(void);
 /* 1 when fitgnn_epilogue_bwd_head_f32 takes a head of C classes on H hidden columns (with / without dWl): besides the two
- * limits above, C may not exceed the number of lanes that own columns of the last 256-column slab (H = 16 -> 4 classes). */
+ * limits above, C may not exceed the number of lanes that own columns of the last 256-column slab (H = 16 -> 4 classes).
+ * That holds for 16-byte aligned dy-side operands (out, dZ); with H % 4 == 0 but an operand that is not 16-byte aligned the kernel
+ * takes 64-column slabs, one column per lane, and the launchers return FITGNN_E_ALIGN when the last such slab has fewer than C
+ * columns (H = 68 -> 4 classes). */
 int fitgnn_epilogue_bwd_head_supported(int32_t H, int32_t C, int32_t with_dWl);
 size_t fitgnn_epilogue_bwd_head_workspace_bytes(int32_t n_rows, int32_t H, int32_t C);
 int fitgnn_epilogue_bwd_head_f32(const float *dy, const float *Wl, int32_t C, const float *out, float *dZ,
