@@ -407,7 +407,10 @@ extern "C" int fitgnn_pool_rows_f32(const int32_t *assign, const double *cval, i
 
 // ---- graph-level pooling on sorted segments (global_mean_pool / global_max_pool of network.py:93,131,164,202) ----------------------
 // out[s][c] = max over the segment's member rows of X[member][c], arg[s][c] = the member row that holds it (the first one on a tie;
-// an empty segment gives -inf / -1).  One wave per (segment, 256-column slab), 16-byte row accesses, members broadcast from registers.
+// an empty segment gives -inf / -1; a column whose members are all -inf gives -inf and the first member).  A NaN member makes the
+// output NaN from ANY position, as torch's amax does, and arg is the first NaN row: a member replaces the held value when it is NaN or
+// larger (`!(v <= best)`), and a held NaN is never replaced.  (`v > best` alone dropped every NaN but one in first place: found by
+// tests/test_gpu_pool_kernels.py::test_segment_max_nan_position.)  One wave per (segment, 256-column slab), 16-byte row accesses.
 __global__ __launch_bounds__(256) void segment_max_kernel(const int32_t *__restrict__ off, const int32_t *__restrict__ members, int32_t n_seg,
                                                           const float *__restrict__ X, int64_t ldx, int32_t F, float *__restrict__ out,
                                                           int32_t *__restrict__ arg, int32_t n_slabs) {
@@ -428,7 +431,7 @@ __global__ __launch_bounds__(256) void segment_max_kernel(const int32_t *__restr
         else { for (int i = 0; i < 4; ++i) v[i] = f0 + i < F ? src[i] : -INFINITY; }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if (v[i] > best[i] || who[i] < 0) { best[i] = v[i]; who[i] = node; }
+            if (who[i] < 0 || (best[i] == best[i] && !(v[i] <= best[i]))) { best[i] = v[i]; who[i] = node; }
     }
     for (int i = 0; i < 4 && f0 + i < F; ++i) {
         out[(int64_t)sgm * F + f0 + i] = best[i];
@@ -634,7 +637,9 @@ extern "C" int fitgnn_segment_sum_f32(const int32_t *seg_off, const int32_t *mem
                                       int64_t ldx, int32_t F, float *out, int64_t ldo, void *stream) {
     if (n_seg < 0 || F < 0 || ldx < F || ldo < F) return FITGNN_E_BADARG;
     if (n_seg == 0 || F == 0) return 0;
-    if (!seg_off || !X || !out) return FITGNN_E_BADARG;
+    // members is read unconditionally (only the max pool takes NULL as the identity): a NULL one is refused, not dereferenced
+    // (tests/test_gpu_pool_kernels.py::test_segment_refusals)
+    if (!seg_off || !members || !X || !out) return FITGNN_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (ldo % 4 == 0) && ((((uintptr_t)X | (uintptr_t)out) % 16) == 0);
     if (vec) {

@@ -1245,7 +1245,9 @@ class SegmentMeanPool(torch.autograd.Function):
 
 class SegmentMaxPool(torch.autograd.Function):
     """global_max_pool over sorted segments (fitgnn_segment_max_f32) with the arg-max rows kept for the backward scatter (the first row
-    on a tie takes the whole gradient; torch's scatter_reduce splits it evenly among tied rows)."""
+    on a tie takes the whole gradient; torch's scatter_reduce splits it evenly among tied rows).  A NaN in any member row makes that
+    segment's column NaN, as the scatter form's amax does; its arg is the first NaN row.  An empty segment gives -inf / no gradient, a
+    column of -inf members gives -inf with the first member as arg."""
 
     @staticmethod
     def forward(ctx, x, pi):

@@ -272,10 +272,11 @@ int fitgnn_segment_sum_f32(const int32_t *seg_off, const int32_t *members, int32
                            int32_t F, float *out, int64_t ldo, void *stream);
 
 /* Graph-level pooling over SORTED segments (torch_geometric.nn.global_mean_pool / global_max_pool as called from network.py:93,131,
- * 164,202; a batch's rows are grouped by graph).  members (int32, may be NULL = the identity) lists the pooled rows -- the row mask
- * x[mask] of the *_gs models (network.py:129,200) is folded into the pool: no gathered copy.
- *   mean / sum: fitgnn_segment_sum_f32 above (+ a per-graph scale);
- *   max: out[s][c] = max_m X[members[m]][c], arg[s][c] = that row (first on a tie; -inf / -1 for an empty segment);
+ * 164,202; a batch's rows are grouped by graph).  members (int32; for the max pool it may be NULL = the identity) lists the pooled rows
+ * -- the row mask x[mask] of the *_gs models (network.py:129,200) is folded into the pool: no gathered copy.
+ *   mean / sum: fitgnn_segment_sum_f32 above (+ a per-graph scale; members required);
+ *   max: out[s][c] = max_m X[members[m]][c], arg[s][c] = that row (first on a tie; -inf / -1 for an empty segment; a NaN member
+ *     gives NaN from any position, arg = the first NaN row; ldx % 4 == 0 and X 16-byte aligned, else FITGNN_E_ALIGN);
  *   backward of mean / sum: fitgnn_segment_expand_f32 writes EVERY row of dst [n_rows x F]: scale[seg] * src[seg] for seg =
  *     seg_of_row[r] >= 0 and zeros otherwise (F % 4 == 0);
  *   backward of max: fitgnn_segment_max_bwd_f32 stores g[s][c] at dst[arg[s][c]][c] (dst zeroed by the caller; segments disjoint). */

@@ -192,6 +192,10 @@ def test_segment_pools_equal_the_scatter_pools(mods, F_, with_rows):
         (out * torch.where(finite, w, torch.zeros(())).cuda()).nan_to_num(0.0, 0.0, 0.0).sum().backward()
         (torch.where(finite, ref, torch.zeros(())) * w).sum().backward()
         assert rel(xg.grad.cpu(), xr.grad) < 1e-6
+    # NaN rows at any position of their graph: the segment path and the scatter path (the same rows, unsorted) give the same NaN pattern
+    xn, perm, r = x.index_fill(0, torch.arange(1, n, 7), float("nan")), torch.randperm(batch.numel()), (lambda t: t if rows is None else t[rows])
+    assert torch.equal(torch.isnan(fnn.global_max_pool(xn.cuda(), batch.cuda(), G, rows=None if rows is None else rows.cuda())),
+                       torch.isnan(fnn.global_max_pool(r(xn)[perm].cuda(), batch[perm].cuda(), G)))
 
 
 def test_graph_level_models(mods):

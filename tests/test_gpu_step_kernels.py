@@ -32,6 +32,12 @@ Launcher -> branch -> tests that reach it:
 | fitgnn_epilogue_fwd_rows_f32 | rows NULL / given, ldz > H, mask / hash, ELU with __expf | test_epilogue_fwd_rows |
 | fitgnn_dense_narrow_k_f32 | K = 1, 8, 11, 31, 32; H = 4, 16, 36 (item loop: H / 4 does not divide 256), 512; K = 32 at H = 512 refused; n = 1, 7, 4 096, 4 097, 60 000 (rows_per_block 8 / 9 / 118); lda, ldw > K, ldo > H; every flag combination | test_dense_narrow_k_shapes, test_dense_narrow_k_epilogues, test_dense_narrow_k_lds_refusal |
 | fitgnn_narrow_atb_f32 | KT = 8 (K = 1, 8), 16 (K = 9, 16), 32 (K = 17, 32); H = 16, 64, 512, 1 024; H = 96 refused; n = 1, 15, 16, 17, 50 000; prev NULL / given with ELU, dropout (mask / hash) | test_narrow_atb_shapes, test_narrow_atb_epilogues, test_narrow_atb_refusal |
+| fitgnn_gemm_nt_epilogue_bwd_f32 (csrc/gemm_nt.hip, <4, true, PRE>) | operand forms: plain b with ldb > K (PRE = false: waves 0-3 stage a, 4-7 stage b) and the pre-split image made by fitgnn_gemm_nt_presplit_f32 from a transposed view (ldb == 0, PRE = true: LDS-DMA); K = 32 (one stage: every prefetch re-reads it), 96 (three) | test_gemm_nt_epilogue_bwd_exact[plain-* / image-*] |
+| | row tiles: R = 1, 5 (rows clamped to R - 1, one live row group), 255, 256, 257 (a second tile of one row), 2049 (9 tiles: the second group of eight, tm = 8 on XCD slot 0, the slots of tm = 9 ... 15 return); bias-gradient partials of a partial tile | test_gemm_nt_epilogue_bwd_exact[*-R*] |
+| | column tiles: N = 4 (one live lane per half wave, nc clamped to N - 4 = 0), 128 (wn = 1 dead), 260 (second column tile with one live lane: its dropout group and its `out` reads at nc = N - 4) | test_gemm_nt_epilogue_bwd_exact[*-N*] |
+| | epilogue: flags 0, ELU, DROPOUT, both; mask, hash seed by value, by pointer; db given / NULL (no fitgnn_colsum_partials_f32 launch) | test_gemm_nt_epilogue_bwd_exact, test_gemm_nt_epilogue_bwd_without_db |
+| | RANDOM operands against float64; two launches give the same bits | test_gemm_nt_epilogue_bwd_random |
+| | N = 6, p = 1, `out` one float into its buffer (FITGNN_E_ALIGN), workspace one byte short (FITGNN_E_WORKSPACE), K = 48, lda % 4 != 0 | test_gemm_nt_epilogue_bwd_refusals |
 | all fixed-order sums | two launches on RANDOM inputs give the same bits | test_repeat_launches_give_the_same_bits |
 
 Bounds that are not bit-exact:
@@ -47,6 +53,11 @@ Bounds that are not bit-exact:
 * ELU through __expf (forward epilogue, dense_narrow_k): for y = z + b <= 0, |elu - expm1(y)| <= u (exp(y)(4 + 2|y| + e_y / u) +
   |expm1(y)|) with e_y the bound on y itself (the exp2 argument y log2(e) rounds twice, v_exp_f32 is within 1 ulp, the
   subtraction of 1 rounds once); times 2 as margin, and the dropout scale.
+* gemm_nt_epilogue_bwd on RANDOM operands: |dZ - ref| <= 2e-5 max|a b^T| |factor| + 2u |ref| per entry: 2e-5 of the largest product
+  entry is what test_linear_gemm_matches_f64 holds the three-product bf16 split to (the dropped lo.lo terms are 2^-16 relative per
+  product, fp32 accumulation over K adds K u); at p = 0.5 the scale 2 and o = out / 2 are exact, so the epilogue rounds twice
+  (o + 1, then the product).  db: the sum of its column's dZ bounds plus (R + 8) u sum |dZ| for the additions (256 rows per tile in
+  8 fixed levels, then the tiles).  Worst observed error / bound on one MI355X run: dZ 0.33, db 0.12.
 """
 import zlib
 
@@ -829,3 +840,119 @@ def test_repeat_launches_give_the_same_bits(L, kernel):
     for x, y in zip(first, second):
         assert np.array_equal(x, y, equal_nan=True), f"{kernel}: two launches on the same input differ"
     del rng
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the dX GEMM with the previous layer's epilogue backward (csrc/gemm_nt.hip)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _presplit(L, b):
+    """The pre-split image of b [N x K], read through the strides of a transposed view (b^T [K x N + 4] is what is in memory)."""
+    N, K = b.shape
+    bT = _strided(np.ascontiguousarray(b.T), N + 4)            # element (n, k) at bT[k * (N + 4) + n]
+    nbytes = int(L.lib().fitgnn_gemm_nt_presplit_bytes(N, K))
+    assert nbytes == -(-N // 256) * (K // 32) * 32768
+    img = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    _run(L, "fitgnn_gemm_nt_presplit_f32", _p(L, bT), 1, N + 4, N, K, K, _p(L, img))
+    return img
+
+
+def _gemm_epi_bwd(L, a, b, out, form, epi, p, seed, mask, with_db=True, out_offset=0, short=0, lda=None):
+    R, K = a.shape
+    N = b.shape[0]
+    lda = K + 4 if lda is None else lda
+    ad = _strided(a, lda)
+    if form == "image":
+        bd, ldb = _presplit(L, b), 0
+    else:
+        bd, ldb = _strided(b, K + 4), K + 4
+    od = _offset_copy(out, out_offset)
+    dbuf = torch.full((R * N + 4,), float("nan"), device="cuda")
+    dZ = dbuf[:R * N].view(R, N)
+    db = torch.full((N + 1,), float("nan"), device="cuda") if with_db else None
+    wb = int(L.lib().fitgnn_gemm_nt_epilogue_bwd_workspace_bytes(R, N))
+    assert wb == -(-R // 256) * N * 4
+    work = torch.empty(max(wb, 4), dtype=torch.uint8, device="cuda")
+    rc = _call(L, "fitgnn_gemm_nt_epilogue_bwd_f32", _p(L, ad), lda, _p(L, bd), ldb, R, N, K, _p(L, od), _p(L, dZ), epi, p, seed, _p(L, mask),
+               _p(L, db), _p(L, work), wb - short)
+    assert torch.isnan(dbuf[-4:]).all().item(), "wrote past the end of dZ"
+    return rc, dZ, db
+
+
+GEMM_SHAPES = [(R, N, K) for R in (1, 5, 255, 256, 257, 2049) for N in (4, 128, 260) for K in (32, 96)]
+GEMM_EPI = [(False, "none"), (True, "none"), (False, "mask"), (False, "hash"), (True, "hash_ptr"), (True, "mask"), (True, "hash")]
+
+
+@pytest.mark.parametrize("elu,drop", GEMM_EPI, ids=lambda v: str(v))
+@pytest.mark.parametrize("R,N,K", GEMM_SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("form", ["plain", "image"])
+def test_gemm_nt_epilogue_bwd_exact(L, form, R, N, K, elu, drop):
+    """a, b = integers in [-8, 8] over 64 (four significant bits: the bf16 high part is the value, the low part zero), `out` integers
+    over 8, p = 0.5: every product, every fp32 partial sum and the epilogue's factor are exact, so dZ and db must equal the float64
+    result bit for bit at every row and column -- tile edges, the clamped rows and the ragged column tile's dropout group included."""
+    rng = _rng("gemm_epi", R, N, K, elu, drop)
+    a, b = _exact(rng, (R, K)), _exact(rng, (N, K))
+    out = _out_exact(rng, (R, N), den=8)
+    epi, seed, mask, word, keep = _epi_case(rng, R, N, elu, drop)
+    ref = (a.astype(np.float64) @ b.astype(np.float64).T) * sr.epilogue_bwd_factor(out, epi, 0.5, keep(np.arange(R)))
+    # the premise of exactness: every dZ is a multiple of 2^-15 (2^-12 products, the scale 2, o + 1 a multiple of 2^-4) and a column's
+    # absolute sum stays below 2^24 of them
+    assert np.all(ref * 2.0 ** 15 == np.round(ref * 2.0 ** 15)) and np.abs(ref).sum(0).max() < 2.0 ** 9
+    rc, dZ, db = _gemm_epi_bwd(L, a, b, out, form, epi, 0.5, seed, mask)
+    L.check(rc, "fitgnn_gemm_nt_epilogue_bwd_f32")
+    _same(_np(dZ), ref, "dZ")
+    _same(_np(db[:N]), sr.colsum(ref)[0], "db")
+    assert np.isnan(db[N].item()), "wrote past column N of db"
+    del word
+
+
+@pytest.mark.parametrize("form", ["plain", "image"])
+def test_gemm_nt_epilogue_bwd_without_db(L, form):
+    rng = _rng("gemm_epi_nodb", form)
+    R, N, K = 257, 260, 32
+    a, b, out = _exact(rng, (R, K)), _exact(rng, (N, K)), _out_exact(rng, (R, N), den=8)
+    epi, seed, mask, word, keep = _epi_case(rng, R, N, True, "hash")
+    rc, dZ, db = _gemm_epi_bwd(L, a, b, out, form, epi, 0.5, seed, mask, with_db=False)
+    L.check(rc, "fitgnn_gemm_nt_epilogue_bwd_f32")
+    _same(_np(dZ), (a.astype(np.float64) @ b.astype(np.float64).T) * sr.epilogue_bwd_factor(out, epi, 0.5, keep(np.arange(R))), "dZ")
+
+
+@pytest.mark.parametrize("elu,drop", [(True, "hash"), (True, "none"), (False, "mask")], ids=lambda v: str(v))
+@pytest.mark.parametrize("R,N,K", [(5, 4, 32), (257, 260, 96), (2049, 128, 32)], ids=lambda v: str(v))
+@pytest.mark.parametrize("form", ["plain", "image"])
+def test_gemm_nt_epilogue_bwd_random(L, form, R, N, K, elu, drop):
+    rng = _rng("gemm_epi_random", R, N, K, elu, drop)
+    a, b = rng.normal(size=(R, K)).astype(np.float32), rng.normal(size=(N, K)).astype(np.float32)
+    out = rng.normal(size=(R, N)).astype(np.float32)
+    epi, seed, mask, word, keep = _epi_case(rng, R, N, elu, drop)
+    rc, dZ, db = _gemm_epi_bwd(L, a, b, out, form, epi, 0.5, seed, mask)
+    L.check(rc, "fitgnn_gemm_nt_epilogue_bwd_f32")
+    prod = a.astype(np.float64) @ b.astype(np.float64).T
+    factor = sr.epilogue_bwd_factor(out, epi, 0.5, keep(np.arange(R)))
+    ref = prod * factor
+    bound = 2e-5 * np.abs(prod).max() * np.abs(factor) + 2 * U * np.abs(ref)
+    got, gdb = _np(dZ), _np(db[:N])
+    bdb = bound.sum(0) + (R + 8) * U * np.abs(ref).sum(0)
+    live = bound > 0
+    print(f"[ratio] gemm_nt_epilogue_bwd dZ: {(np.abs(got - ref)[live] / bound[live]).max():.3g}, db: {(np.abs(gdb - ref.sum(0)) / bdb).max():.3g}")
+    _within(got, ref, bound, "dZ")
+    _within(gdb, ref.sum(0), bdb, "db")
+    rc, dZ2, db2 = _gemm_epi_bwd(L, a, b, out, form, epi, 0.5, seed, mask)
+    assert torch.equal(dZ, dZ2) and torch.equal(db[:N], db2[:N]), "two launches on the same input differ"
+    del word
+
+
+def test_gemm_nt_epilogue_bwd_refusals(L):
+    rng = _rng("gemm_epi_refusals")
+    R, K = 8, 32
+
+    def launch(N=8, K=K, epi=0, p=0.0, **kw):
+        return _gemm_epi_bwd(L, _exact(rng, (R, K)), _exact(rng, (N, K)), _out_exact(rng, (R, N), den=8), "plain", epi, p, 0, None, **kw)[0]
+
+    assert launch() == 0
+    assert launch(N=6) == E_BADARG                  # a dropout group of four columns would straddle two rows
+    assert launch(epi=sr.EPI_DROPOUT, p=1.0) == E_BADARG
+    assert launch(epi=sr.EPI_DROPOUT, p=0.5) == 0
+    assert launch(out_offset=1) == E_ALIGN
+    assert launch(short=1) == E_WORKSPACE
+    assert launch(K=48) == E_BADARG                 # K % 32 != 0
+    assert launch(lda=K + 1) == E_BADARG            # rows of a not 16-byte aligned
