@@ -1,0 +1,251 @@
+// query.hip -- node queries on the two-hop receptive field (inference.py:668-688 of the reference: the model on the ONE subgraph
+// that holds the queried node, of whose output one row is kept).
+//
+// For the reference's default model (two GCNConv layers, ELU, lt1, eval mode) row q of the block-diagonal union needs only
+//     T     = X W0^T                                                       (once per model: fitgnn_gemm_exact_f32)
+//     h_j   = ELU(sum_{e' in row j} val[e'] T[xrow[col[e']]] + b0)          for j in row q's columns
+//     g_q   = sum_{e in row q} val[e] h_{col[e]}                            fitgnn_gcn_query_gather_f32
+//     z_q   = ELU(W1 g_q + b1);  out_q = Wl z_q + bl  (log_softmax)         fitgnn_gcn_query_tail_f32
+// The union is block-diagonal, so both hops stay inside the query's subgraph: the values are the per-subgraph forward's.
+//
+// Operation order (tests/query_reference.py mirrors it):
+//   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
+//           entry i of row q (CSR order) belongs to wave i % 4, which folds its entries in ascending i: p_w = fmaf(val[e], h, p_w);
+//           g = ((p_0 + p_1) + p_2) + p_3 (a wave without entries holds 0).
+//   tail    z[n] = ELU(fmaf chain over k ascending of G[q][k] W1[n][k], from 0, + b1[n])   (v_mfma_f32_16x16x4_f32: exact fp32,
+//           bit-equal to that chain); logit[c] = (fmaf chain over h ascending of z[h] Wl[c][h], from 0) + bl[c];
+//           log-softmax: m = max_c logit, s = sum_c expf(logit[c] - m) ascending c, out[c] = (logit[c] - m) - logf(s).
+#include <algorithm>
+
+#include "common.h"
+#include "fitgnn_hip.h"
+
+namespace {
+
+constexpr int kGatherWaves = 4;
+
+__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
+
+// One workgroup per (query, 256-column slab), the slab fastest so that all of a table row's slabs are in flight together; 64 lanes x
+// float4 per slab (the columns are independent: the bits do not depend on the split).  The query's entries are dealt round-robin to
+// the four waves; a wave forms its neighbour's layer-0 row from the table -- the neighbour's entries fetched 64 at a time and broadcast by
+// v_readlane, four table rows in flight -- applies + b0 and ELU and folds the row into its partial.  Any degree is served by the
+// loops; the partials meet in LDS in wave order.
+__global__ __launch_bounds__(256) void query_gather_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                           const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
+                                                           const int32_t *__restrict__ xrow, const float *__restrict__ b0,
+                                                           const int64_t *__restrict__ rows, int32_t H, float *__restrict__ G,
+                                                           int64_t ldg, int32_t n_slabs) {
+    __shared__ float4 part[kGatherWaves][64];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = blockIdx.x / n_slabs, c0 = (blockIdx.x % n_slabs) * 256;
+    const int64_t q = rows[qi];
+    const int e0 = __builtin_amdgcn_readfirstlane(rowptr[q]), e1 = __builtin_amdgcn_readfirstlane(rowptr[q + 1]);
+    const int deg = e1 - e0;
+    const int c = c0 + lane * 4;
+    const bool live = c < H;  // H % 4 == 0: a live lane owns four whole columns
+    const float *Tc = T + (live ? c : 0);
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (b0 && live) bias = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = w; i < deg; i += kGatherWaves) {
+        const int j = __builtin_amdgcn_readfirstlane(col[e0 + i]);
+        const float vq = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(val[e0 + i])));
+        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[j]), n1 = __builtin_amdgcn_readfirstlane(rowptr[j + 1]);
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = n0; base < n1; base += 64) {
+            const int cnt = min(64, n1 - base);
+            int my = 0, mv = 0;
+            if (lane < cnt) {
+                const int cc = col[base + lane];
+                my = xrow ? xrow[cc] : cc;
+                mv = __float_as_int(val[base + lane]);
+            }
+            for (int k = 0; k < cnt; k += 4) {
+                float4 t[4];
+                float wv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                    const int idx = k + u < cnt ? k + u : k;
+                    const int node = __builtin_amdgcn_readlane(my, idx);
+                    wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
+                    t[u] = *reinterpret_cast<const float4 *>(Tc + (int64_t)node * ldt);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (k + u < cnt) {
+                        a.x = fmaf(wv[u], t[u].x, a.x);
+                        a.y = fmaf(wv[u], t[u].y, a.y);
+                        a.z = fmaf(wv[u], t[u].z, a.z);
+                        a.w = fmaf(wv[u], t[u].w, a.w);
+                    }
+                }
+            }
+        }
+        p.x = fmaf(vq, elu1(a.x + bias.x), p.x);
+        p.y = fmaf(vq, elu1(a.y + bias.y), p.y);
+        p.z = fmaf(vq, elu1(a.z + bias.z), p.z);
+        p.w = fmaf(vq, elu1(a.w + bias.w), p.w);
+    }
+    part[w][lane] = p;
+    __syncthreads();
+    if (w == 0 && live) {
+        float4 g = part[0][lane];
+#pragma unroll
+        for (int o = 1; o < kGatherWaves; ++o) {
+            const float4 r = part[o][lane];
+            g.x += r.x; g.y += r.y; g.z += r.z; g.w += r.w;
+        }
+        *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + c) = g;
+    }
+}
+
+// ---- tail ----
+constexpr int kTailQ = 16;       // queries per workgroup: one MFMA tile of rows
+constexpr int kTailKS = 32;      // k-stage
+constexpr int kTailLd = kTailKS + 4;  // stage row stride: 16 rows x 36 floats + the four k of a step fall on 64 distinct banks
+constexpr int kTailCols = 256;   // columns of z per pass: 4 waves x 4 accumulators x 16
+constexpr size_t kTailLdsMax = 160 * 1024;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__host__ __device__ constexpr size_t tail_lds_floats(int H2, int C) {
+    return (size_t)kTailQ * (H2 + 4) + (size_t)kTailCols * kTailLd + (size_t)kTailQ * kTailLd + (size_t)kTailQ * C;
+}
+static_assert(tail_lds_floats(512, 48) * sizeof(float) <= kTailLdsMax, "the default model's tail must fit LDS");
+
+// One workgroup per tile of up to 16 queries.  z = ELU(G W1^T + b1) on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4],
+// B: W1[n = l & 15][k = l >> 4], C/D: column l & 15, rows 4 (l >> 4) + r), W1 and the tile's rows of G staged through LDS in
+// k-stages of 32; the tile's z stays in LDS, the head reads it from there.
+__global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1,
+                                                         const float *__restrict__ b1, const float *__restrict__ Wl,
+                                                         const float *__restrict__ bl, int32_t H, int32_t H2, int32_t C,
+                                                         float *__restrict__ out, int64_t ldo, int32_t log_softmax) {
+    extern __shared__ float smem[];
+    const int zld = H2 + 4;
+    float *zs = smem;
+    float *Ws = zs + (size_t)kTailQ * zld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *lg = Gs + kTailQ * kTailLd;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
+    const int q0 = blockIdx.x * kTailQ;
+    const int nq = min(kTailQ, Q - q0);
+
+    for (int n0 = 0; n0 < H2; n0 += kTailCols) {
+        const int ncols = min(kTailCols, H2 - n0);  // a multiple of 16
+        f32x4 acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < H; k0 += kTailKS) {
+            const int k4 = min(kTailKS, H - k0) >> 2;  // float4 per staged row (H % 4 == 0)
+            __syncthreads();                           // the previous stage has been consumed
+            for (int idx = tid; idx < ncols * k4; idx += 256) {
+                const int n = idx / k4, kk = idx - n * k4;
+                *reinterpret_cast<float4 *>(Ws + n * kTailLd + kk * 4) =
+                    *reinterpret_cast<const float4 *>(W1 + (int64_t)(n0 + n) * H + k0 + kk * 4);
+            }
+            for (int idx = tid; idx < kTailQ * k4; idx += 256) {
+                const int r = idx / k4, kk = idx - r * k4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);  // rows past Q: computed as zeros, never stored
+                if (r < nq) v = *reinterpret_cast<const float4 *>(G + (int64_t)(q0 + r) * ldg + k0 + kk * 4);
+                *reinterpret_cast<float4 *>(Gs + r * kTailLd + kk * 4) = v;
+            }
+            __syncthreads();
+            for (int kk = 0; kk < k4; ++kk) {
+                const float a = Gs[r16 * kTailLd + kk * 4 + kq];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int nb = (w * 4 + u) * 16;
+                    if (nb < ncols) {  // wave-uniform
+                        const float b = Ws[(nb + r16) * kTailLd + kk * 4 + kq];
+                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[u], 0, 0, 0);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {
+                const int n = n0 + nb + r16;
+                const float bias = b1 ? b1[n] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zs[(kq * 4 + r) * zld + n] = elu1(acc[u][r] + bias);
+            }
+        }
+    }
+    __syncthreads();
+
+    // the head: 16 consecutive lanes share a class (one broadcast read of Wl) and read 16 rows of z, 4 banks apart
+    for (int o = tid; o < kTailQ * C; o += 256) {
+        const int qi = o & (kTailQ - 1), c = o >> 4;
+        const float *wl = Wl + (int64_t)c * H2;
+        const float *z = zs + qi * zld;
+        float s = 0.f;
+        for (int h = 0; h < H2; h += 4) {
+            const float4 wv = *reinterpret_cast<const float4 *>(wl + h);
+            const float4 zv = *reinterpret_cast<const float4 *>(z + h);
+            s = fmaf(zv.x, wv.x, s);
+            s = fmaf(zv.y, wv.y, s);
+            s = fmaf(zv.z, wv.z, s);
+            s = fmaf(zv.w, wv.w, s);
+        }
+        lg[qi * C + c] = bl ? s + bl[c] : s;
+    }
+    __syncthreads();
+    if (log_softmax) {
+        if (tid < nq) {
+            float *row = lg + tid * C;
+            float m = row[0];
+            for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+            float s = 0.f;
+            for (int c = 0; c < C; ++c) s += expf(row[c] - m);
+            const float l = logf(s);
+            for (int c = 0; c < C; ++c) row[c] = (row[c] - m) - l;
+        }
+        __syncthreads();
+    }
+    for (int o = tid; o < nq * C; o += 256) {  // rows of a partial last tile are not stored
+        const int qi = o / C, c = o - qi * C;
+        out[(int64_t)(q0 + qi) * ldo + c] = lg[o];
+    }
+}
+
+}  // namespace
+
+extern "C" int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                           const int32_t *xrow, const float *b0, const int64_t *rows, int32_t Q, int32_t H, float *G,
+                                           int64_t ldg, void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || ldt < H || ldg < H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !rows || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G) % 16) != 0) return FITGNN_E_ALIGN;
+    const int n_slabs = (H + 255) / 256;
+    if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
+    hipLaunchKernelGGL(query_gather_kernel, dim3((unsigned)(Q * n_slabs)), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, T, ldt, xrow,
+                       b0, rows, H, G, ldg, n_slabs);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t fitgnn_gcn_query_tail_lds_bytes(int32_t H2, int32_t C) {
+    if (H2 <= 0 || C <= 0) return 0;
+    return tail_lds_floats(H2, C) * sizeof(float);
+}
+
+extern "C" int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl,
+                                         const float *bl, int32_t H, int32_t H2, int32_t C, float *out, int64_t ldo, int32_t log_softmax,
+                                         void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || H2 < 16 || (H2 % 16) != 0 || C < 1 || ldg < H || ldo < C) return FITGNN_E_BADARG;
+    if ((ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gcn_query_tail_lds_bytes(H2, C);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // z of the tile does not fit LDS
+    if (Q == 0) return 0;
+    if (!G || !W1 || !Wl || !out) return FITGNN_E_BADARG;
+    if ((((uintptr_t)G | (uintptr_t)W1 | (uintptr_t)Wl | (uintptr_t)out) % 16) != 0) return FITGNN_E_ALIGN;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(query_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1, b1,
+                       Wl, bl, H, H2, C, out, ldo, log_softmax);
+    return (int)hipGetLastError();
+}

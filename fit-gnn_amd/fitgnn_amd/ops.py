@@ -1168,6 +1168,47 @@ def head_rows(out, rows, Wl, bl, n_total=None):
     return y
 
 
+def gcn_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
+    """G [Q, H]: row i = the layer-1 aggregation of union row rows[i] over layer-0 rows made from T = X W0^T on the fly
+    (fitgnn_gcn_query_gather_f32).  rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
+    _lib.require_cuda(rowptr, col, val, T, rows, xrow, b0)
+    Q, H = int(rows.numel()), int(T.shape[1])
+    G = out if out is not None else torch.empty((Q, H), dtype=torch.float32, device=T.device)
+    _lib.check(_lib.lib().fitgnn_gcn_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                      _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
+                                                      _lib.stream_ptr(T.device)), "fitgnn_gcn_query_gather_f32")
+    return G
+
+
+def gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=False, out=None):
+    """[Q, C] = Wl ELU(W1 G^T + b1) + bl per row, log-softmax on request (fitgnn_gcn_query_tail_f32).  W1 [H2, H], Wl [C, H2] contiguous."""
+    _lib.require_cuda(G, W1, b1, Wl, bl)
+    Q, H = int(G.shape[0]), int(G.shape[1])
+    H2, C = int(W1.shape[0]), int(Wl.shape[0])
+    y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
+    _lib.check(_lib.lib().fitgnn_gcn_query_tail_f32(_lib.dptr(G), G.stride(0), Q, _lib.dptr(W1), _lib.dptr(b1), _lib.dptr(Wl), _lib.dptr(bl),
+                                                    H, H2, C, _lib.dptr(y), y.stride(0), 1 if log_softmax else 0,
+                                                    _lib.stream_ptr(G.device)), "fitgnn_gcn_query_tail_f32")
+    return y
+
+
+def query_supported(model):
+    """The two query kernels answer for `model`: exactly two GCNConv layers, hidden size a multiple of 16, a head the tail's LDS
+    holds, contiguous float32 parameters on the GPU."""
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GCNConv for c in convs):
+        return False
+    W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
+    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias]
+    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        return False
+    H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
+    return (H % 16 == 0 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+
+
 def segment_sum(seg_off, members, X, n_seg):
     """out[s] = sum of X[members[seg_off[s]:seg_off[s+1]]] (fitgnn_segment_sum_f32)."""
     _lib.require_cuda(seg_off, members, X)

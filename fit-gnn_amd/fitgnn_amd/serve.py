@@ -1,0 +1,184 @@
+"""QueryEngine: predictions for node ids, computed on each node's two-hop receptive field inside its own subgraph.
+
+FIT-GNN answers a node query by running the model on the ONE subgraph that holds the node (inference.py:668-688 of the reference)
+and keeping one row.  For the reference's default model -- two GCNConv layers, ELU, lt1, eval mode -- row q of the block-diagonal
+union needs only
+
+    T     = X W0^T                                                     once per model, every table row (ops.Linear)
+    h_j   = ELU(sum_{e' in row j} val[e'] T[xrow[col[e']]] + b0)        j in row q's columns
+    g_q   = sum_{e in row q} val[e] h_{col[e]}                          ops.gcn_query_gather: one launch for any number of queries
+    out_q = Wl ELU(W1 g_q + b1) + bl   (+ log_softmax)                  ops.gcn_query_tail:   one launch
+
+The union is block-diagonal, so both hops stay inside the query's subgraph and the values are the per-subgraph forward's.  Any other
+model (GAT / SAGE / GIN layers, one or three layers, hidden sizes the kernels do not take) is answered by that per-subgraph forward
+itself, each subgraph cut out of the union once and kept.
+"""
+import numpy as np
+import torch
+
+from . import ops
+from .csr import csr_for
+
+
+def core_row_table(node_id, core, n_nodes=None):
+    """Host function.  int64 [n_nodes]: the union row at which original node v is a core (own-cluster) row, -1 where the batch holds
+    no such row (a shard holds only some clusters).  node_id / core: per union row, the original node and whether the row is its
+    cluster's own copy (every node is core in exactly one subgraph of the full union)."""
+    node_id = np.asarray(node_id, dtype=np.int64)
+    core = np.asarray(core, dtype=bool)
+    rows = np.nonzero(core)[0]
+    ids = node_id[rows]
+    n = int(n_nodes) if n_nodes is not None else (int(node_id.max()) + 1 if node_id.size else 0)
+    table = np.full(n, -1, dtype=np.int64)
+    table[ids[::-1]] = rows[::-1]   # a node listed twice keeps its first core row
+    return table
+
+
+def first_missing(table, node_ids):
+    """Host function.  The first of node_ids that has no core row in `table` (outside it, or -1 there); None when all have one."""
+    ids = np.asarray(node_ids, dtype=np.int64).reshape(-1)
+    inside = (ids >= 0) & (ids < len(table))
+    ok = inside.copy()
+    ok[inside] = table[ids[inside]] >= 0
+    bad = np.nonzero(~ok)[0]
+    return None if bad.size == 0 else int(ids[bad[0]])
+
+
+class QueryEngine:
+    """predict(node_ids) -> [Q, C] for a trained network.Classify_node (log-probabilities) or network.Regress_node (raw values) over a
+    data.SubgraphBatch, extra-node or cluster-node layout, with or without the de-duplicated feature table."""
+
+    def __init__(self, model, batch):
+        self.model, self.batch = model, batch
+        self.log_softmax = not isinstance(model, _regressors())
+        g = batch.graph
+        if g is None:
+            raise ValueError("QueryEngine needs a SubgraphBatch on the GPU")
+        self.graph = g
+        self.n_rows = int(batch.n_rows)
+        dev = batch.x.device
+        n_nodes = int(batch.x_table.shape[0]) if batch.x_table is not None else None
+        table = core_row_table(batch.node_id.cpu().numpy(), batch.core.cpu().numpy(), n_nodes)
+        self._core_host = table
+        self._core_row = torch.from_numpy(table).to(dev)
+        self._T = None          # (W0, W0._version, T)
+        self._subgraphs = {}    # the per-subgraph forward's inputs: s -> (x, edge_index, first row)
+        self._fused = None      # (key of the model's layers and parameters, ops.query_supported(model))
+
+    # -- the table T = X W0^T --
+    @property
+    def fused(self):
+        """ops.query_supported(model), re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
+        m = self.model
+        params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
+        params += [m.lt1.weight, m.lt1.bias]
+        key = tuple(type(c) for c in m.conv) + tuple(None if p is None else (p.data_ptr(), p.dtype, p.shape) for p in params)
+        if self._fused is None or self._fused[0] != key:
+            self._fused = (key, ops.query_supported(m))
+        return self._fused[1]
+
+    def _operand(self):
+        b = self.batch
+        if b.x_table is not None and b.row_index is not None:
+            return b.x_table, b.row_index.index
+        return b.x, None
+
+    def refresh(self):
+        """Remake T from the model's current weights (done automatically when conv[0].lin.weight changes)."""
+        W0 = self.model.conv[0].lin.weight
+        X, _ = self._operand()
+        with torch.no_grad():
+            T = ops.Linear.apply(X.float(), W0, self.model.op_config).contiguous()
+        self._T = (W0, W0._version, T)
+        return self
+
+    def _table(self):
+        W0 = self.model.conv[0].lin.weight
+        if not ops._same_index(self._T, W0):
+            self.refresh()
+        return self._T[2]
+
+    @property
+    def table_bytes(self):
+        """Bytes of T (0 on the per-subgraph path, which keeps none)."""
+        if not self.fused:
+            return 0
+        T = self._table()
+        return int(T.numel()) * T.element_size()
+
+    # -- queries --
+    def predict(self, node_ids):
+        """[Q, C] for original node ids (any order, repeats allowed).  ValueError names the first id that has no core row here."""
+        ids = torch.as_tensor(node_ids, dtype=torch.int64).reshape(-1)
+        miss = first_missing(self._core_host, ids.cpu().numpy())
+        if miss is not None:
+            raise ValueError(f"node {miss} has no core row in this batch")
+        return self.predict_rows(self._core_row.index_select(0, ids.to(self._core_row.device)))
+
+    def predict_rows(self, rows):
+        """[Q, C] for union rows."""
+        if self.model.training:
+            raise RuntimeError("QueryEngine answers in eval mode only: call model.eval() (dropout has no place in a query)")
+        dev = self.batch.x.device
+        if torch.is_tensor(rows) and rows.is_cuda:
+            rows = rows.to(torch.int64).reshape(-1).contiguous()
+            bad = bool(rows.numel()) and (int(rows.min()) < 0 or int(rows.max()) >= self.n_rows)
+        else:   # host ids: checked on the host, no device round trip before the launches
+            host = np.asarray(rows.numpy() if torch.is_tensor(rows) else rows, dtype=np.int64).reshape(-1)
+            bad = bool(host.size) and (int(host.min()) < 0 or int(host.max()) >= self.n_rows)
+            rows = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+        if bad:
+            raise ValueError(f"union rows must lie in [0, {self.n_rows})")
+        with torch.no_grad():
+            if self.fused:
+                return self._predict_fused(rows)
+            return self._predict_subgraphs(rows)
+
+    def _predict_fused(self, rows):
+        m, f = self.model, self.graph.f
+        _, xrow = self._operand()
+        G = ops.gcn_query_gather(f.rowptr, f.col, f.val, self._table(), rows, xrow=xrow, b0=m.conv[0].bias)
+        return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
+
+    def subgraph(self, s):
+        """(x, edge_index, first union row) of subgraph s as its own small graph, cut out once and kept; its CSR is built here too."""
+        hit = self._subgraphs.get(s)
+        if hit is None:
+            b = self.batch
+            r0, r1 = int(b.ptr[s]), int(b.ptr[s + 1])
+            ei = b.edge_index
+            m = (ei[0] >= r0) & (ei[0] < r1)
+            hit = (b.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
+            mode = _layer_mode(self.model)
+            if mode is not None:
+                csr_for(hit[1], r1 - r0, mode)
+            self._subgraphs[s] = hit
+        return hit
+
+    def _predict_subgraphs(self, rows):
+        host = rows.cpu().numpy()
+        subs = np.searchsorted(self.batch.ptr, host, side="right") - 1
+        C = int(self.model.lt1.weight.shape[0])
+        out = torch.empty((len(host), C), dtype=torch.float32, device=rows.device)
+        for s in np.unique(subs):
+            x, ei, r0 = self.subgraph(int(s))
+            y = self.model(x, ei)
+            pick = torch.from_numpy(np.nonzero(subs == s)[0]).to(rows.device)
+            out[pick] = y.index_select(0, rows[pick] - r0).float()
+        return out
+
+
+def _regressors():
+    from . import network
+    return (network.Regress_node,)
+
+
+def _layer_mode(model):
+    """The CSR mode the model's layers look up (pre-built per subgraph so that a timed forward finds it)."""
+    from . import nn as fnn
+    conv = model.conv[0] if len(model.conv) else None
+    if isinstance(conv, fnn.GCNConv):
+        return "gcn"
+    if isinstance(conv, fnn.GATConv):
+        return "gat"
+    return None

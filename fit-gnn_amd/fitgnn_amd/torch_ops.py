@@ -10,6 +10,9 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::lift_adjacency(rowptr, col, w, assign, cval, n) -> (rowptr_c, col_c, w_c)
     fitgnn::gemm_nt(a, b) -> a @ b^T          fitgnn::gemm_atb(a, b) -> a^T @ b      (3 x bf16 MFMA kernels, fp32 in/out)
     fitgnn::linear(x, W) -> x @ W^T           differentiable: dX = gemm_nt(dY, W^T), dW = gemm_atb(dY, x)
+    fitgnn::gcn_query_gather(rowptr, col, val, T, rows, xrow?, b0?) -> G      the two node-query launches (fitgnn_amd.serve)
+    fitgnn::gcn_query_tail(G, W1, b1?, Wl, bl?, log_softmax) -> out
+                                              (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
 (meta) kernels for shape inference and an autograd formula for spmm_csr over a pair of forward / transposed
@@ -32,6 +35,8 @@ _LIB.define("lift_adjacency(Tensor rowptr, Tensor col, Tensor w, Tensor assign, 
 _LIB.define("gemm_nt(Tensor a, Tensor b) -> Tensor")
 _LIB.define("gemm_atb(Tensor a, Tensor b) -> Tensor")
 _LIB.define("linear(Tensor x, Tensor W) -> Tensor")
+_LIB.define("gcn_query_gather(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor rows, Tensor? xrow, Tensor? b0) -> Tensor")
+_LIB.define("gcn_query_tail(Tensor G, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
 
 
 def _spmm_csr(rowptr, col, val, X, tiles, window_rows, bias, epilogue, p, seed, mask):
@@ -93,7 +98,15 @@ def _gemm_atb(a, b):
     return ops.gemm_atb(a.contiguous(), b.contiguous())
 
 
-for _name, _fn in (("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
+def _gcn_query_gather(rowptr, col, val, T, rows, xrow, b0):
+    return ops.gcn_query_gather(rowptr, col, val, T, rows, xrow=xrow, b0=b0)
+
+
+def _gcn_query_tail(G, W1, b1, Wl, bl, log_softmax):
+    return ops.gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=log_softmax)
+
+
+for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
                    ("lift_adjacency", _lift_adjacency)):
     _LIB.impl(_name, _fn, "CUDA")
@@ -143,6 +156,16 @@ def _(a, b):
 @torch.library.register_fake("fitgnn::linear")
 def _(x, W):
     return x.new_empty((x.shape[0], W.shape[0]))
+
+
+@torch.library.register_fake("fitgnn::gcn_query_gather")
+def _(rowptr, col, val, T, rows, xrow, b0):
+    return T.new_empty((rows.shape[0], T.shape[1]))
+
+
+@torch.library.register_fake("fitgnn::gcn_query_tail")
+def _(G, W1, b1, Wl, bl, log_softmax):
+    return G.new_empty((G.shape[0], Wl.shape[0]))
 
 
 def _linear_setup(ctx, inputs, output):

@@ -8,7 +8,8 @@ subgraph set or coarsened graph).  For every sampled test node the model runs on
 the ONE subgraph that contains it (inference.py:668-688) -- that is the "inference that FITs in memory" claim --
 and, with --baseline, on the full graph (inference.py:651-666).  Unlike the reference, the timed region is
 bracketed by a device synchronisation (the reference's time() around an asynchronous launch measures launch time).
-Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50).
+Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50), --query_engine
+(opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows inside the same timing bracket; same CSV row).
 """
 import argparse
 import os
@@ -67,6 +68,9 @@ def build_parser():
     p.add_argument('--layer_name', type=str, default='GCNConv')
     p.add_argument('--n_graphs', type=int, default=2000)
     p.add_argument('--community_nodes', type=int, default=165000)
+    p.add_argument('--query_engine', action='store_true',
+                   help="node_cls / node_reg: answer each query with fitgnn_amd.serve.QueryEngine (two launches on the query's two-hop "
+                        "receptive field) instead of a forward over its whole subgraph")
     return p
 
 
@@ -200,8 +204,27 @@ def main(argv=None):
     ei = batch.edge_index
     cache = {}
     times, losses, hits = [], [], 0
+    engine = None
+    if args.query_engine:   # built outside the timed region, as the per-subgraph CSR is below; T = X W0^T is made here too
+        from fitgnn_amd.serve import QueryEngine
+        engine = QueryEngine(model, batch)
+        if engine.fused:
+            engine.refresh()
+        else:
+            for _, s in queries:
+                engine.subgraph(s)
     with torch.no_grad():
         for row, s in queries:
+            if engine is not None:
+                torch.cuda.synchronize(dev)
+                t0 = time.time()
+                out = engine.predict_rows([row])
+                torch.cuda.synchronize(dev)
+                times.append(time.time() - t0)
+                l, h = query_loss(out[0], batch.y[row])
+                losses.append(l)
+                hits += h
+                continue
             if s not in cache:  # the subgraph as its own tiny graph: rows ptr[s]:ptr[s+1] of the union
                 r0, r1 = int(ptr[s]), int(ptr[s + 1])
                 m = (ei[0] >= r0) & (ei[0] < r1)

@@ -590,6 +590,36 @@ int fitgnn_appnp_lds_f32(const int32_t *rowptr, const int32_t *col, const float 
                          int32_t slice, void *stream);
 
 /* =====================================================================================
+ * Inference half: node queries on the two-hop receptive field
+ * replaces: inference.py:668-688 (model_gs(x, edge_index) on the query's whole subgraph, of which out_gs[j] is kept), for the
+ *           two-layer GCN of inference.py:22-50 in eval mode
+ * ===================================================================================== */
+
+/* G[i][:] = g_{rows[i]} for i < Q, the layer-1 aggregation of union row q = rows[i] over layer-0 rows made on the fly from
+ * T = X W0^T [n_table x H] (row stride ldt):
+ *   h_j = ELU(sum_{e' in row j} val[e'] * T[xrow ? xrow[col[e']] : col[e']] + b0),   g_q = sum_{e in row q} val[e] * h_{col[e]}
+ * over the GCN-normalised CSR (rowptr, col, val) of a block-diagonal union (xrow, b0 may be NULL).  One workgroup per query and
+ * 256-column slab (the columns are independent: a row of H = 512 is two workgroups, each walking the query's CSR entries), its
+ * entries dealt round-robin to four waves whose partial rows are added in wave order; every sum runs in CSR order with fmaf, so two
+ * launches give the same bits (operation order: csrc/query.hip).  Any degree is served.  A query row without entries gives zeros, a
+ * neighbour row without entries ELU(b0).  rows (int64, values in [0, n_rows)) may repeat and need no order.  Writes
+ * G[0..Q) x [0..H) only.  Requires H % 4 == 0, ldt, ldg >= H (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G 16-byte aligned
+ * (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                const int32_t *xrow, const float *b0, const int64_t *rows, int32_t Q, int32_t H, float *G, int64_t ldg,
+                                void *stream);
+
+/* out[i][:] = Wl ELU(W1 G[i] + b1) + bl for i < Q (network.py:31-34 on the aggregated rows: A (h W1^T) = (A h) W1^T), followed by a
+ * max-subtracted log-softmax per row when log_softmax != 0 (network.py:35).  W1 [H2 x H], Wl [C x H2] contiguous; b1, bl may be
+ * NULL.  One workgroup per tile of 16 queries: the product on the exact-fp32 MFMA (an ascending-k fmaf chain), the tile's z in LDS,
+ * the head accumulated in ascending h.  Rows of a partial last tile are not stored.  Requires H % 4 == 0, H2 % 16 == 0, C >= 1,
+ * ldg >= H, ldo >= C and fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 KiB (FITGNN_E_BADARG); ldg a multiple of 4 and G, W1, Wl,
+ * out 16-byte aligned (FITGNN_E_ALIGN). */
+size_t fitgnn_gcn_query_tail_lds_bytes(int32_t H2, int32_t C);
+int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl, const float *bl,
+                              int32_t H, int32_t H2, int32_t C, float *out, int64_t ldo, int32_t log_softmax, void *stream);
+
+/* =====================================================================================
  * Coarsen half: one contraction level of variation_neighborhoods
  * replaces: graph_coarsening/coarsening_utils.py contract_variation_linear :530-650,
  *           get_coarsening_matrix :212-254, coarsen_matrix :201-205 (+ graph_utils.zero_diag :82-90),

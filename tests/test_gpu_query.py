@@ -1,0 +1,222 @@
+"""GPU tier: fitgnn_amd.serve.QueryEngine -- node ids in, predictions out -- against the float64 oracle's whole-union forward, on
+small unions of cluster subgraphs with shared extra nodes (extra-node layout) and with cluster nodes; its per-subgraph path for the
+models the two kernels do not take; the torch.ops bindings; inference.py --query_engine."""
+import argparse
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, N_CLUSTERS = 60, 4
+SHAPES = [(12, 64), (33, 512)]   # (F, hidden); C = 7
+
+
+def rel(a, b):   # tests/test_gpu_gnn.py's measure: the project's tolerance on logits is 1e-4 of the largest
+    return float((a - b).abs().max() / b.abs().max().clamp(min=1e-20))
+
+
+@pytest.fixture(scope="module")
+def mods():
+    assert torch.cuda.is_available()
+    from fitgnn_amd import data as fdata, network, ops, serve
+    from oracle import gnn_oracle as gorc
+    return fdata, network, ops, serve, gorc
+
+
+def _union(fdata, layout, F, dedup=True):
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(5)
+    ei = fdata.synthetic_graph(N, 150, seed=2)
+    assign = rng.integers(0, N_CLUSTERS, size=N)
+    assign[:N_CLUSTERS] = np.arange(N_CLUSTERS)
+    X = rng.normal(size=(N, F)).astype(np.float32)
+    y = rng.integers(0, 7, size=N)
+    if layout == "cluster":
+        cu, cv = assign[ei[0]], assign[ei[1]]
+        k = cu != cv
+        adj = sp.csr_matrix((np.ones(int(k.sum())), (cu[k], cv[k])), shape=(N_CLUSTERS, N_CLUSTERS))
+        sub = fdata.assemble_subgraphs_cluster(ei, N, assign, N_CLUSTERS, adj)
+        X = np.concatenate([X, rng.normal(size=(N_CLUSTERS, F)).astype(np.float32)])   # stand-ins for the pooled rows C.X
+        y = np.concatenate([y, np.zeros(N_CLUSTERS, dtype=y.dtype)])
+    else:
+        sub = fdata.assemble_subgraphs(ei, N, assign, N_CLUSTERS, extra_node=True)
+        extra = sub["node_id"][~sub["core"]]
+        assert len(np.unique(extra)) < len(extra), "no extra node is shared between subgraphs"
+    assert len(sub["ptr"]) - 1 >= 3
+    return fdata.SubgraphBatch(sub, X, y, np.zeros(len(X), dtype=bool), device="cuda", dedup=dedup)
+
+
+def _model(network, F, hidden, cls="Classify_node", layer="GCNConv", layers=2, seed=0):
+    args = argparse.Namespace(num_layers1=layers, layer_name=layer, num_features=F, hidden=hidden, num_classes=7)
+    torch.manual_seed(seed)
+    m = getattr(network, cls)(args).cuda()
+    with torch.no_grad():
+        for name, p in m.named_parameters():
+            if name.endswith("bias"):
+                p.normal_(0, 0.3)   # the default zero biases would hide a dropped bias
+    return m.eval()
+
+
+def _oracle(gorc, model, batch, rows, classify=True):
+    sd = {k: v.detach().cpu().double() for k, v in model.state_dict().items()}
+    out = gorc.classify_node_forward(sd, batch.x.cpu().double(), batch.edge_index.cpu(), 2)
+    if not classify:   # Regress_node: the same stack without the log_softmax
+        x = batch.x.cpu().double()
+        for i in range(2):
+            x = torch.nn.functional.elu(gorc.gcn_conv(x, batch.edge_index.cpu(), sd[f"conv.{i}.lin.weight"], sd[f"conv.{i}.bias"]))
+        out = x @ sd["lt1.weight"].t() + sd["lt1.bias"]
+    return out[rows.cpu()]
+
+
+@pytest.mark.parametrize("dedup", [True, False], ids=["table", "rows"])
+@pytest.mark.parametrize("F,hidden", SHAPES, ids=str)
+@pytest.mark.parametrize("layout", ["extra", "cluster"])
+def test_predict_every_core_node(mods, layout, F, hidden, dedup):
+    fdata, network, ops, serve, gorc = mods
+    batch = _union(fdata, layout, F, dedup=dedup)
+    model = _model(network, F, hidden)
+    eng = serve.QueryEngine(model, batch)
+    assert eng.fused is True and ops.query_supported(model)
+    rows = torch.nonzero(batch.core).flatten()
+    ids = batch.node_id[rows]
+    perm = torch.randperm(len(ids), generator=torch.Generator().manual_seed(1)).cuda()
+    ids, rows = ids[perm], rows[perm]     # unsorted
+    out = eng.predict(ids)
+    assert out.shape == (len(ids), 7) and out.dtype == torch.float32
+    ref = _oracle(gorc, model, batch, rows)
+    assert rel(out.cpu().double(), ref) <= 1e-4
+    with torch.no_grad():
+        full = model(batch.x, batch.edge_index)[rows]
+    assert rel(out.cpu().double(), full.cpu().double()) <= 1e-4
+    assert torch.equal(eng.predict_rows(rows), out) and torch.equal(eng.predict(ids.cpu().tolist()), out)
+    n_table = batch.x_table.shape[0] if dedup else batch.n_rows
+    assert eng.table_bytes == n_table * hidden * 4
+
+
+def test_regress_node_values(mods):
+    fdata, network, ops, serve, gorc = mods
+    batch = _union(fdata, "extra", 12)
+    model = _model(network, 12, 64, cls="Regress_node")
+    eng = serve.QueryEngine(model, batch)
+    rows = torch.nonzero(batch.core).flatten()
+    out = eng.predict(batch.node_id[rows])
+    assert out.shape == (len(rows), 1) and eng.fused
+    assert rel(out.cpu().double(), _oracle(gorc, model, batch, rows, classify=False)) <= 1e-4
+
+
+def test_weight_update_is_picked_up(mods):
+    fdata, network, ops, serve, gorc = mods
+    batch = _union(fdata, "extra", 12)
+    model = _model(network, 12, 64)
+    eng = serve.QueryEngine(model, batch)
+    rows = torch.nonzero(batch.core).flatten()
+    ids = batch.node_id[rows]
+    before = eng.predict(ids).clone()
+    with torch.no_grad():
+        model.conv[0].lin.weight.mul_(0.5).add_(0.01)     # in place: same storage, new version
+        model.lt1.bias.add_(0.25)
+    after = eng.predict(ids)
+    assert rel(after.cpu().double(), _oracle(gorc, model, batch, rows)) <= 1e-4
+    assert not torch.allclose(after, before, atol=1e-3)
+    assert torch.equal(eng.refresh().predict(ids), after)
+
+
+@pytest.mark.parametrize("layer,layers,hidden", [("GATConv", 2, 64), ("GCNConv", 1, 64), ("GCNConv", 2, 40)], ids=str)
+def test_other_models_take_the_per_subgraph_forward(mods, layer, layers, hidden):
+    fdata, network, ops, serve, gorc = mods
+    batch = _union(fdata, "extra", 12)
+    model = _model(network, 12, hidden, layer=layer, layers=layers)
+    eng = serve.QueryEngine(model, batch)
+    assert eng.fused is False and eng.table_bytes == 0
+    rows = torch.nonzero(batch.core).flatten().flip(0)
+    out = eng.predict(batch.node_id[rows])
+    ptr = batch.ptr
+    ref = torch.empty_like(out)
+    with torch.no_grad():
+        for s in range(len(ptr) - 1):   # the per-subgraph forward of inference.py
+            r0, r1 = int(ptr[s]), int(ptr[s + 1])
+            ei = batch.edge_index
+            m = (ei[0] >= r0) & (ei[0] < r1)
+            y = model(batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous())
+            pick = (rows >= r0) & (rows < r1)
+            ref[pick] = y[rows[pick] - r0]
+    assert rel(out.cpu().double(), ref.cpu().double()) <= 1e-4
+    if layer == "GCNConv" and layers == 2:   # hidden 40: not a multiple of 16, but the oracle still applies
+        assert rel(out.cpu().double(), _oracle(gorc, model, batch, rows)) <= 1e-4
+
+
+def test_refusals(mods):
+    fdata, network, ops, serve, gorc = mods
+    batch = _union(fdata, "extra", 12)
+    model = _model(network, 12, 64)
+    eng = serve.QueryEngine(model, batch)
+    with pytest.raises(ValueError, match=r"node 60\b"):
+        eng.predict([3, 60, 61])
+    with pytest.raises(ValueError):
+        eng.predict_rows([batch.n_rows])
+    # a shard: the clusters 1 and 2 alone -- a node of cluster 0 has no core row there
+    sub = fdata.assemble_subgraphs(fdata.synthetic_graph(N, 150, seed=2), N, np.arange(N) % N_CLUSTERS, N_CLUSTERS, extra_node=True)
+    shard = fdata.select_clusters(sub, np.array([1, 2]))
+    sb = fdata.SubgraphBatch(shard, np.zeros((N, 12), dtype=np.float32), np.zeros(N, dtype=np.int64), np.zeros(N, dtype=bool), device="cuda")
+    se = serve.QueryEngine(model, sb)
+    assert se.predict([1, 2, 5]).shape == (3, 7)
+    with pytest.raises(ValueError, match=r"node 4\b"):
+        se.predict([1, 4, 0])
+    model.train()
+    with pytest.raises(RuntimeError):
+        eng.predict([3])
+    model.eval()
+
+
+def test_torch_ops_hold_the_two_launchers(mods):
+    fdata, network, ops, serve, gorc = mods
+    from fitgnn_amd import torch_ops  # noqa: F401  (registers torch.ops.fitgnn)
+    batch = _union(fdata, "extra", 12)
+    model = _model(network, 12, 64)
+    eng = serve.QueryEngine(model, batch)
+    f, T = batch.graph.f, eng._table()
+    rows = torch.nonzero(batch.core).flatten()
+    xrow, b0 = batch.row_index.index, model.conv[0].bias
+    G = torch.ops.fitgnn.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, xrow, b0)
+    assert torch.equal(G, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, xrow=xrow, b0=b0))
+    W1, b1, Wl, bl = model.conv[1].lin.weight, model.conv[1].bias, model.lt1.weight, model.lt1.bias
+    y = torch.ops.fitgnn.gcn_query_tail(G, W1, b1, Wl, bl, True)
+    assert torch.equal(y, ops.gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=True)) and torch.equal(y, eng.predict_rows(rows))
+    assert torch.equal(torch.ops.fitgnn.gcn_query_tail(G, W1, None, Wl, None, False), ops.gcn_query_tail(G, W1, None, Wl, None))
+    m = torch.ops.fitgnn.gcn_query_gather(f.rowptr.to("meta"), f.col.to("meta"), f.val.to("meta"), T.to("meta"), rows.to("meta"), None, None)
+    assert m.shape == G.shape and torch.ops.fitgnn.gcn_query_tail(m, W1.to("meta"), None, Wl.to("meta"), None, False).shape == y.shape
+
+
+def test_inference_cli_with_and_without_the_engine(tmp_path, monkeypatch):
+    """inference.py on synthetic-cora with a checkpoint trained for a handful of epochs here: --query_engine gives the same hit
+    count, the mean loss within 1e-4 relative, and the same CSV header and column count.  Each inference run is a process of its
+    own, as a user starts it: the coarsening's eigensolver (ARPACK) draws its start vector from a generator whose state lives as long
+    as the process, so two calls of inference.main in ONE process sample different queries -- with or without the flag."""
+    import subprocess
+    import sys
+
+    monkeypatch.chdir(tmp_path)
+    import main as cli
+
+    common = ["--dataset", "synthetic-cora", "--hidden", "64", "--seed", "0", "--normalize_features", "--extra_node"]
+    cli.main(common + ["--runs", "1", "--output_dir", "f", "--train_fitgnn", "--exp_setup", "Gs_train_2_Gs_infer", "--coarsening_ratio", "0.5",
+                       "--epochs1", "5", "--epochs2", "5"])
+    inf = [sys.executable, os.path.join(ROOT, "fit-gnn_amd", "inference.py")] + common + ["--num_test_samples", "30", "--path_gs", "save/node_cls/f/"]
+    outs = []
+    for extra in ([], ["--query_engine"]):
+        r = subprocess.run(inf + extra, cwd=tmp_path, check=True, timeout=300, stdout=subprocess.PIPE, text=True)
+        outs.append(r.stdout)
+    hits = [ln for o in outs for ln in o.splitlines() if ln.startswith("Accuracy (FIT-GNN):")]
+    assert len(hits) == 2 and hits[0] == hits[1], hits
+    lines = open(os.path.join("inference_results", "node_cls.csv")).read().strip().split("\n")
+    assert len(lines) == 3 and lines[0].startswith("dataset,baseline,experiment,exp_setup")
+    head, a, b = (ln.split(",") for ln in lines)
+    assert len(a) == len(b) == len(head)
+    la, lb = float(a[head.index("avg_loss")]), float(b[head.index("avg_loss")])
+    assert abs(la - lb) <= 1e-4 * abs(la), (la, lb)
+    assert a[:head.index("avg_inf_time")] == b[:head.index("avg_inf_time")] and a[-1] == b[-1]

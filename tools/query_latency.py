@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Latency of one node query through fitgnn_amd.serve.QueryEngine against the per-subgraph forward inference.py times without
+--query_engine, on a workloads.py union (GPU only).
+
+    python tools/query_latency.py --workload S-pubmed [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
+
+Writes profiles/query_latency_<workload>.json (or --out):
+  (a) engine_single      median / p90 seconds of predict_rows([row]) per sampled core row, bracketed by device synchronisations as
+                         inference.py brackets its forward;
+  (b) subgraph_forward   the same rows through inference.timed_forward on the cached subgraph with its CSR pre-built -- measured TWICE
+                         per row (b1 before the engine's turn, b2 after it) so that its own run-to-run spread is known;
+                         (a), (b1), (b2) alternate row by row inside one process, after one untimed pass over every row;
+  (c) engine_batch       queries per second at Q = --batch, and the gather kernel alone: sum_q sum_{j in row q} deg(j) * H * 4 bytes over
+                         its HIP-event time, next to fitgnn_stream_copy_f32's rate in the same process.
+The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fit-gnn_amd")
+for p in (ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def _stats(t):
+    import numpy as np
+    t = np.asarray(t)
+    return dict(median_us=round(float(np.median(t)) * 1e6, 2), p90_us=round(float(np.percentile(t, 90)) * 1e6, 2),
+                mean_us=round(float(t.mean()) * 1e6, 2), n=int(t.size))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="S-pubmed")
+    ap.add_argument("--hidden", type=int, default=512)
+    ap.add_argument("--samples", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import time
+
+    import numpy as np
+    import torch
+
+    import inference
+    from fitgnn_amd import _lib, network, ops, serve, workloads
+    from fitgnn_amd.csr import csr_for
+
+    assert torch.cuda.is_available(), "query_latency.py measures on the GPU only"
+    dev = torch.device("cuda", 0)
+    N, E, F, C, r = workloads.SHAPES[a.workload]
+    wl = workloads.coarsen_workload(a.workload, dev)
+    sub, _ = workloads.assemble(a.workload, torch.from_numpy(np.ascontiguousarray(wl["ei"])).to(dev),
+                                torch.from_numpy(np.ascontiguousarray(wl["assign"])).to(dev), wl["n_clusters"])
+    batch = workloads.batch_from_subgraphs(a.workload, sub, dev)
+    del sub, wl
+    margs = argparse.Namespace(num_layers1=2, layer_name="GCNConv", num_features=F, hidden=a.hidden, num_classes=C)
+    torch.manual_seed(2)
+    model = network.Classify_node(margs).to(dev).eval()
+    engine = serve.QueryEngine(model, batch)
+    assert engine.fused
+    t0 = time.time()
+    engine.refresh()
+    torch.cuda.synchronize()
+    t_table = time.time() - t0
+
+    rng = np.random.default_rng(0)
+    core_rows = torch.nonzero(batch.core).flatten().cpu().numpy()
+    rows = core_rows[rng.permutation(len(core_rows))[: a.samples]]
+    ptr, ei = batch.ptr, batch.edge_index
+    subs = np.searchsorted(ptr, rows, side="right") - 1
+    cache = {}
+    for s in np.unique(subs):   # exactly inference.py's cache: the subgraph as its own graph, its CSR built outside the timed call
+        r0, r1 = int(ptr[s]), int(ptr[s + 1])
+        m = (ei[0] >= r0) & (ei[0] < r1)
+        cache[int(s)] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
+        csr_for(cache[int(s)][1], r1 - r0, "gcn")
+
+    def engine_once(row):
+        torch.cuda.synchronize(dev)
+        t = time.time()
+        out = engine.predict_rows([row])
+        torch.cuda.synchronize(dev)
+        return out, time.time() - t
+
+    def forward_once(row, s):
+        x, e, r0 = cache[s]
+        out, dt = inference.timed_forward(model, x, e, dev)
+        return out[row - r0], dt
+
+    worst = 0.0
+    with torch.no_grad():
+        for row, s in zip(rows.tolist(), subs.tolist()):   # untimed pass: every shape warmed, answers compared
+            oa, _ = engine_once(row)
+            ob, _ = forward_once(row, s)
+            worst = max(worst, float((oa[0] - ob).abs().max() / ob.abs().max().clamp(min=1e-20)))
+        ta, tb1, tb2 = [], [], []
+        per_round = []
+        for _ in range(a.rounds):
+            ra, r1_, r2_ = [], [], []
+            for row, s in zip(rows.tolist(), subs.tolist()):
+                r1_.append(forward_once(row, s)[1])
+                ra.append(engine_once(row)[1])
+                r2_.append(forward_once(row, s)[1])
+            per_round.append(dict(engine_median_us=round(float(np.median(ra)) * 1e6, 2), forward_first_median_us=round(float(np.median(r1_)) * 1e6, 2),
+                                  forward_second_median_us=round(float(np.median(r2_)) * 1e6, 2)))
+            ta += ra; tb1 += r1_; tb2 += r2_
+
+        # (c) a batch of queries: the two launches end to end, and the gather kernel alone by HIP events
+        qrows = torch.from_numpy(core_rows[rng.integers(0, len(core_rows), size=a.batch)]).to(dev)
+        for _ in range(3):
+            engine.predict_rows(qrows)
+        torch.cuda.synchronize()
+        reps = 20
+        t = time.time()
+        for _ in range(reps):
+            engine.predict_rows(qrows)
+        torch.cuda.synchronize()
+        t_batch = (time.time() - t) / reps
+        f = batch.graph.f
+        T = engine._table()
+        xrow = batch.row_index.index if batch.row_index is not None else None
+        G = torch.empty((a.batch, a.hidden), dtype=torch.float32, device=dev)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        for e0, e1 in ev:
+            e0.record()
+            ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
+            e1.record()
+        torch.cuda.synchronize()
+        t_gather = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e-3
+        deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
+        csum = torch.zeros(deg.numel() + 1, dtype=torch.int64, device=dev)
+        csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)     # prefix sums of deg(col[e]) over the entries
+        rp = f.rowptr.long()
+        table_rows = int((csum[rp[qrows + 1]] - csum[rp[qrows]]).sum())
+        gather_bytes = table_rows * a.hidden * 4
+        n = 64 * 1024 * 1024
+        src, dst = torch.empty(n, dtype=torch.float32, device=dev).normal_(), torch.empty(n, dtype=torch.float32, device=dev)
+        cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for e0, e1 in cev:
+            e0.record()
+            _lib.check(_lib.lib().fitgnn_stream_copy_f32(_lib.dptr(src), _lib.dptr(dst), n, _lib.stream_ptr(dev)), "fitgnn_stream_copy_f32")
+            e1.record()
+        torch.cuda.synchronize()
+        t_copy = float(np.median([e0.elapsed_time(e1) for e0, e1 in cev][2:])) * 1e-3
+
+    sa, s1, s2 = _stats(ta), _stats(tb1), _stats(tb2)
+    base = min(s1["median_us"], s2["median_us"])
+    spread = abs(s1["median_us"] - s2["median_us"])
+    res = dict(workload=a.workload, hidden=a.hidden, classes=C, union_rows=int(batch.n_rows), nnz=int(batch.nnz), subgraphs=int(len(ptr) - 1),
+               samples=int(len(rows)), rounds=a.rounds, device=torch.cuda.get_device_name(0),
+               table=dict(rows=int(T.shape[0]), bytes=engine.table_bytes, build_s=round(t_table, 4)),
+               engine_single=sa, subgraph_forward_first=s1, subgraph_forward_second=s2, per_round=per_round,
+               subgraph_forward_spread_us=round(spread, 2), engine_below_forward_by_us=round(base - sa["median_us"], 2),
+               engine_faster_beyond_spread=bool(base - sa["median_us"] > spread),
+               max_rel_diff_engine_vs_forward=worst,
+               engine_batch=dict(Q=a.batch, seconds=round(t_batch, 6), queries_per_s=round(a.batch / t_batch, 1),
+                                 gather_kernel_s=round(t_gather, 6), gather_table_rows=table_rows, gather_bytes=gather_bytes,
+                                 gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
+                                 stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
