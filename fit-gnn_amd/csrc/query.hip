@@ -7,6 +7,7 @@
 //     g_q   = sum_{e in row q} val[e] h_{col[e]}                            fitgnn_gcn_query_gather_f32
 //     z_q   = ELU(W1 g_q + b1);  out_q = Wl z_q + bl  (log_softmax)         fitgnn_gcn_query_tail_f32
 // The union is block-diagonal, so both hops stay inside the query's subgraph: the values are the per-subgraph forward's.
+// Two GATConv layers take the same tail behind fitgnn_gat_query_gather_f32 (attention over both hops: see gat_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -100,8 +101,229 @@ __global__ __launch_bounds__(256) void query_gather_kernel(const int32_t *__rest
     }
 }
 
+// ---- attention over both hops (two GATConv layers, heads = 1) ----
+//   h_r = ELU(sum_k alpha_rk T[t(k)] + b0),  alpha_r. = softmax_k lrelu(a0s[t(k)] + a0d[t(r)], slope0)     k in CSR row r
+//   g_q = sum_j beta_j h_j,                  beta     = softmax_j lrelu(u_s . h_j + u_d . h_q, slope1)      j in CSR row q
+// Operation order (tests/gat_query_reference.py mirrors it).  A wave holds a whole row: lane l owns columns 4 l .. 4 l + 3 and, for
+// H > 256, 256 + 4 l .. 256 + 4 l + 3.
+//   row r    s = a0s[t(k)] + a0d[t(r)]; e = s > 0 ? s : slope0 * s; m = max_k e; p_k = expf(e_k - m); over the entries in CSR order
+//            l = l + p_k, a = fmaf(p_k, T[t(k)][c], a) (both from 0); h = ELU(fmaf(a, 1 / l, b0[c])); a row without entries: ELU(b0).
+//   dot      u . h: per lane d = fmaf(u[c], h[c], d) from 0 over its columns ascending, then d += d of lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.
+//   query q  every wave that has entries forms h_q itself (the same bits in each) and c_q = u_d . h_q.  Entry i of row q (CSR order)
+//            belongs to wave i % 4, which folds its entries in ascending i into (M, L, P) = (-inf, 0, 0):
+//            f = lrelu((u_s . h_j) + c_q, slope1);  f > M: x = expf(M - f), L = fmaf(L, x, 1), P = fmaf(P, x, h_j), M = f;
+//            otherwise x = expf(f - M), L = L + x, P = fmaf(x, h_j, P).
+//   merge    M = max_w M_w; x_w = expf(M_w - M); over w ascending L = fmaf(x_w, L_w, L), P = fmaf(x_w, P_w, P) (from 0);
+//            g = P * (1 / L).  A wave without entries holds (-inf, 0, 0): x_w = 0.  A query without entries gives zeros.
+constexpr int kHopsWaves = 4;
+
+__device__ __forceinline__ float lrelu1(float x, float slope) {
+#pragma clang fp contract(off)  // the product is rounded on its own: the row's maximum minus itself is exactly 0
+    return x > 0.f ? x : slope * x;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+template <int NS>
+__device__ __forceinline__ float row_dot(const float4 (&u)[NS], const float4 (&h)[NS]) {
+    float d = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        d = fmaf(u[s].x, h[s].x, d);
+        d = fmaf(u[s].y, h[s].y, d);
+        d = fmaf(u[s].z, h[s].z, d);
+        d = fmaf(u[s].w, h[s].w, d);
+    }
+    return wave_sum(d);
+}
+
+// One wave: layer-0 row r of the union into h.  Tc[s]: the lane's column of slot s in T (a lane past H reads column 0 and is never
+// stored or counted: its u is 0).  The row's entries are fetched 64 at a time -- the table row and the weight ride on the lanes -- and
+// broadcast by v_readlane, four table rows in flight.
+template <int NS>
+__device__ __forceinline__ void gat_row(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *const (&Tc)[NS],
+                                        int64_t ldt, const int32_t *__restrict__ xrow, const float *__restrict__ a_src0,
+                                        const float *__restrict__ a_dst0, float slope0, const float4 (&bias)[NS], int r, int lane,
+                                        float4 (&h)[NS]) {
+    const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+    const int tr = __builtin_amdgcn_readfirstlane(xrow ? xrow[r] : r);
+    const float ad = a_dst0[tr];
+    float mx = -INFINITY;
+    for (int base = n0 + lane; base < n1; base += 64) {
+        const int cc = col[base];
+        mx = fmaxf(mx, lrelu1(a_src0[xrow ? xrow[cc] : cc] + ad, slope0));
+    }
+    mx = wave_max(mx);
+    float l = 0.f;
+    float4 a[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) a[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = n0; base < n1; base += 64) {
+        const int cnt = min(64, n1 - base);
+        int my = 0, mv = 0;
+        if (lane < cnt) {
+            const int cc = col[base + lane];
+            my = xrow ? xrow[cc] : cc;
+            mv = __float_as_int(expf(lrelu1(a_src0[my] + ad, slope0) - mx));
+        }
+        for (int k = 0; k < cnt; k += 4) {
+            float4 t[4][NS];
+            float wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                const int idx = k + u < cnt ? k + u : k;
+                const int node = __builtin_amdgcn_readlane(my, idx);
+                wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
+#pragma unroll
+                for (int s = 0; s < NS; ++s) t[u][s] = *reinterpret_cast<const float4 *>(Tc[s] + (int64_t)node * ldt);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k + u < cnt) {
+                    l += wv[u];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        a[s].x = fmaf(wv[u], t[u][s].x, a[s].x);
+                        a[s].y = fmaf(wv[u], t[u][s].y, a[s].y);
+                        a[s].z = fmaf(wv[u], t[u][s].z, a[s].z);
+                        a[s].w = fmaf(wv[u], t[u][s].w, a[s].w);
+                    }
+                }
+            }
+        }
+    }
+    const float inv = n1 > n0 ? 1.f / l : 0.f;  // l >= 1: the row's largest score gives expf(0)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        h[s].x = elu1(fmaf(a[s].x, inv, bias[s].x));
+        h[s].y = elu1(fmaf(a[s].y, inv, bias[s].y));
+        h[s].z = elu1(fmaf(a[s].z, inv, bias[s].z));
+        h[s].w = elu1(fmaf(a[s].w, inv, bias[s].w));
+    }
+}
+
+// One workgroup of four waves per query, every wave on whole rows of H <= 256 NS columns (the layer-1 score is a dot over the whole
+// row of h_j).  The four online-softmax states meet in LDS in wave order.
+template <int NS>
+__global__ __launch_bounds__(256) void gat_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                             const float *__restrict__ T, int64_t ldt, const int32_t *__restrict__ xrow,
+                                                             const float *__restrict__ a_src0, const float *__restrict__ a_dst0,
+                                                             const float *__restrict__ b0, float slope0, const float *__restrict__ u_src,
+                                                             const float *__restrict__ u_dst, float slope1,
+                                                             const int64_t *__restrict__ rows, int32_t H, float *__restrict__ G, int64_t ldg) {
+    __shared__ float4 part[kHopsWaves][NS][64];
+    __shared__ float ml[kHopsWaves][2];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = blockIdx.x;
+    const int q = (int)rows[qi];
+    const int e0 = __builtin_amdgcn_readfirstlane(rowptr[q]), e1 = __builtin_amdgcn_readfirstlane(rowptr[q + 1]);
+    const int deg = e1 - e0;
+    const float *Tc[NS];
+    float4 bias[NS], us[NS], P[NS];
+    bool live[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int c = s * 256 + lane * 4;
+        live[s] = c < H;  // H % 4 == 0: a live lane owns four whole columns
+        Tc[s] = T + (live[s] ? c : 0);
+        bias[s] = us[s] = P[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live[s]) {
+            if (b0) bias[s] = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+            us[s] = *reinterpret_cast<const float4 *>(u_src + c);
+        }
+    }
+    float M = -INFINITY, Lw = 0.f;
+    if (w < deg) {
+        float4 h[NS];
+        float cq;
+        {
+            float4 ud[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                ud[s] = live[s] ? *reinterpret_cast<const float4 *>(u_dst + s * 256 + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            gat_row<NS>(rowptr, col, Tc, ldt, xrow, a_src0, a_dst0, slope0, bias, q, lane, h);
+            cq = row_dot<NS>(ud, h);
+        }
+        for (int i = w; i < deg; i += kHopsWaves) {
+            const int j = __builtin_amdgcn_readfirstlane(col[e0 + i]);
+            gat_row<NS>(rowptr, col, Tc, ldt, xrow, a_src0, a_dst0, slope0, bias, j, lane, h);
+            const float f = lrelu1(row_dot<NS>(us, h) + cq, slope1);
+            if (f > M) {  // wave-uniform: every lane holds the butterfly's bits
+                const float x = expf(M - f);
+                Lw = fmaf(Lw, x, 1.f);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    P[s].x = fmaf(P[s].x, x, h[s].x);
+                    P[s].y = fmaf(P[s].y, x, h[s].y);
+                    P[s].z = fmaf(P[s].z, x, h[s].z);
+                    P[s].w = fmaf(P[s].w, x, h[s].w);
+                }
+                M = f;
+            } else {
+                const float x = expf(f - M);
+                Lw += x;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    P[s].x = fmaf(x, h[s].x, P[s].x);
+                    P[s].y = fmaf(x, h[s].y, P[s].y);
+                    P[s].z = fmaf(x, h[s].z, P[s].z);
+                    P[s].w = fmaf(x, h[s].w, P[s].w);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) part[w][s][lane] = P[s];
+    if (lane == 0) {
+        ml[w][0] = M;
+        ml[w][1] = Lw;
+    }
+    __syncthreads();
+    if (w != 0) return;
+    float4 g[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) g[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (deg > 0) {
+        float Mx = ml[0][0];
+#pragma unroll
+        for (int o = 1; o < kHopsWaves; ++o) Mx = fmaxf(Mx, ml[o][0]);
+        float Ls = 0.f;
+#pragma unroll
+        for (int o = 0; o < kHopsWaves; ++o) {
+            const float x = expf(ml[o][0] - Mx);  // a wave without entries: expf(-inf) = 0
+            Ls = fmaf(x, ml[o][1], Ls);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float4 r = part[o][s][lane];
+                g[s].x = fmaf(x, r.x, g[s].x);
+                g[s].y = fmaf(x, r.y, g[s].y);
+                g[s].z = fmaf(x, r.z, g[s].z);
+                g[s].w = fmaf(x, r.w, g[s].w);
+            }
+        }
+        const float inv = 1.f / Ls;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            g[s].x *= inv; g[s].y *= inv; g[s].z *= inv; g[s].w *= inv;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if (live[s]) *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + s * 256 + lane * 4) = g[s];
+}
+
 // ---- tail ----
-constexpr int kTailQ = 16;       // queries per workgroup: one MFMA tile of rows
+constexpr int kTailQ = 16;      // queries per workgroup: one MFMA tile of rows
 constexpr int kTailKS = 32;      // k-stage
 constexpr int kTailLd = kTailKS + 4;  // stage row stride: 16 rows x 36 floats + the four k of a step fall on 64 distinct banks
 constexpr int kTailCols = 256;   // columns of z per pass: 4 waves x 4 accumulators x 16
@@ -225,6 +447,24 @@ extern "C" int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t 
     if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
     hipLaunchKernelGGL(query_gather_kernel, dim3((unsigned)(Q * n_slabs)), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, T, ldt, xrow,
                        b0, rows, H, G, ldg, n_slabs);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_gat_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                           const float *a_src0, const float *a_dst0, const float *b0, float slope0, const float *u_src,
+                                           const float *u_dst, float slope1, const int64_t *rows, int32_t Q, int32_t H, float *G,
+                                           int64_t ldg, void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || H > 512 || ldt < H || ldg < H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !T || !a_src0 || !a_dst0 || !u_src || !u_dst || !rows || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G | (uintptr_t)u_src | (uintptr_t)u_dst) % 16) != 0) return FITGNN_E_ALIGN;
+    if (H <= 256)
+        hipLaunchKernelGGL(gat_query_hops_kernel<1>, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, rowptr, col, T, ldt, xrow, a_src0,
+                           a_dst0, b0, slope0, u_src, u_dst, slope1, rows, H, G, ldg);
+    else
+        hipLaunchKernelGGL(gat_query_hops_kernel<2>, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, rowptr, col, T, ldt, xrow, a_src0,
+                           a_dst0, b0, slope0, u_src, u_dst, slope1, rows, H, G, ldg);
     return (int)hipGetLastError();
 }
 

@@ -1209,6 +1209,40 @@ def query_supported(model):
             and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
 
 
+def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=None, b0=None, slope0=0.2, slope1=0.2, out=None):
+    """G [Q, H]: row i = the layer-1 attention aggregation (before its Linear) of union row rows[i] over layer-0 GAT rows made from
+    T = X W0^T on the fly (fitgnn_gat_query_gather_f32).  a_src0 / a_dst0: the layer-0 score dots per TABLE row; u_src / u_dst [H]:
+    W1^T att_src1, W1^T att_dst1.  rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
+    _lib.require_cuda(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow, b0)
+    Q, H = int(rows.numel()), int(T.shape[1])
+    G = out if out is not None else torch.empty((Q, H), dtype=torch.float32, device=T.device)
+    _lib.check(_lib.lib().fitgnn_gat_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(T), T.stride(0), _lib.dptr(xrow),
+                                                      _lib.dptr(a_src0), _lib.dptr(a_dst0), _lib.dptr(b0), float(slope0), _lib.dptr(u_src),
+                                                      _lib.dptr(u_dst), float(slope1), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
+                                                      _lib.stream_ptr(T.device)), "fitgnn_gat_query_gather_f32")
+    return G
+
+
+def gat_query_supported(model):
+    """fitgnn_gat_query_gather_f32 and the tail answer for `model`: exactly two GATConv layers and a head, hidden sizes multiples of
+    16 with the first at most 512 (a wave holds a whole layer-0 row), a head the tail's LDS holds, contiguous float32 parameters on
+    the GPU."""
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GATConv for c in convs):
+        return False
+    W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
+    att = [convs[0].att_src, convs[0].att_dst, convs[1].att_src, convs[1].att_dst]
+    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias] + att
+    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        return False
+    H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
+    return (H % 16 == 0 and H <= 512 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+            and att[0].numel() == H and att[1].numel() == H and att[2].numel() == H2 and att[3].numel() == H2
+            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+
+
 def segment_sum(seg_off, members, X, n_seg):
     """out[s] = sum of X[members[seg_off[s]:seg_off[s+1]]] (fitgnn_segment_sum_f32)."""
     _lib.require_cuda(seg_off, members, X)

@@ -9,9 +9,18 @@ union needs only
     g_q   = sum_{e in row q} val[e] h_{col[e]}                          ops.gcn_query_gather: one launch for any number of queries
     out_q = Wl ELU(W1 g_q + b1) + bl   (+ log_softmax)                  ops.gcn_query_tail:   one launch
 
-The union is block-diagonal, so both hops stay inside the query's subgraph and the values are the per-subgraph forward's.  Any other
-model (GAT / SAGE / GIN layers, one or three layers, hidden sizes the kernels do not take) is answered by that per-subgraph forward
-itself, each subgraph cut out of the union once and kept.
+The union is block-diagonal, so both hops stay inside the query's subgraph and the values are the per-subgraph forward's.
+
+With gat_kernels=True a model of two GATConv layers (heads = 1) takes the same two launches, attention over both hops
+(ops.gat_query_gather, then the same tail: sum beta = 1, so W1 (sum_j beta_j h_j) + b1 is conv1's output):
+
+    T, a0s = T att_src0, a0d = T att_dst0                               once per set of weights, per table row
+    u_s = W1^T att_src1, u_d = W1^T att_dst1                            (att . (W1 h) = (W1^T att) . h)
+    h_r   = ELU(sum_k alpha_rk T[t(k)] + b0)                            alpha_r. = softmax_k lrelu(a0s[t(k)] + a0d[t(r)], slope0)
+    g_q   = sum_j beta_j h_j                                            beta = softmax_j lrelu(u_s . h_j + u_d . h_q, slope1)
+
+Any other model (a GAT model without the flag, SAGE / GIN layers, one or three layers, hidden sizes the kernels do not take) is
+answered by that per-subgraph forward itself, each subgraph cut out of the union once and kept.
 """
 import numpy as np
 import torch
@@ -46,10 +55,13 @@ def first_missing(table, node_ids):
 
 class QueryEngine:
     """predict(node_ids) -> [Q, C] for a trained network.Classify_node (log-probabilities) or network.Regress_node (raw values) over a
-    data.SubgraphBatch, extra-node or cluster-node layout, with or without the de-duplicated feature table."""
+    data.SubgraphBatch, extra-node or cluster-node layout, with or without the de-duplicated feature table.  gat_kernels: a model of
+    two GATConv layers is answered by the attention query kernel (off by default: its speed against the per-subgraph forward is
+    not measured yet); it changes nothing for any other model."""
 
-    def __init__(self, model, batch):
+    def __init__(self, model, batch, gat_kernels=False):
         self.model, self.batch = model, batch
+        self.gat_kernels = bool(gat_kernels)
         self.log_softmax = not isinstance(model, _regressors())
         g = batch.graph
         if g is None:
@@ -63,19 +75,28 @@ class QueryEngine:
         self._core_row = torch.from_numpy(table).to(dev)
         self._T = None          # (W0, W0._version, T)
         self._subgraphs = {}    # the per-subgraph forward's inputs: s -> (x, edge_index, first row)
-        self._fused = None      # (key of the model's layers and parameters, ops.query_supported(model))
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | None: the kernels that answer)
+        self._gat = None        # the GAT path's prepared state: ([(tensor, version)] of the six weights it is made from, a0s, a0d, u_s, u_d)
 
     # -- the table T = X W0^T --
-    @property
-    def fused(self):
-        """ops.query_supported(model), re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
+    def _kind(self):
+        """"gcn" (ops.query_supported), "gat" (gat_kernels and ops.gat_query_supported) or None, re-evaluated only when a layer or a
+        parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
+        if self.gat_kernels:
+            params += [getattr(c, a, None) for c in m.conv for a in ("att_src", "att_dst")]
         key = tuple(type(c) for c in m.conv) + tuple(None if p is None else (p.data_ptr(), p.dtype, p.shape) for p in params)
         if self._fused is None or self._fused[0] != key:
-            self._fused = (key, ops.query_supported(m))
+            kind = "gcn" if ops.query_supported(m) else ("gat" if self.gat_kernels and ops.gat_query_supported(m) else None)
+            self._fused = (key, kind)
         return self._fused[1]
+
+    @property
+    def fused(self):
+        """The query kernels answer for the model (otherwise the per-subgraph forward does)."""
+        return self._kind() is not None
 
     def _operand(self):
         b = self.batch
@@ -84,13 +105,43 @@ class QueryEngine:
         return b.x, None
 
     def refresh(self):
-        """Remake T from the model's current weights (done automatically when conv[0].lin.weight changes)."""
+        """Remake T -- and, on the GAT path, the score vectors and W1^T att -- from the model's current weights (done automatically
+        when one of the weights they are made from changes)."""
         W0 = self.model.conv[0].lin.weight
         X, _ = self._operand()
         with torch.no_grad():
             T = ops.Linear.apply(X.float(), W0, self.model.op_config).contiguous()
         self._T = (W0, W0._version, T)
+        if self._kind() == "gat":
+            self._refresh_gat(T)
         return self
+
+    def _gat_weights(self):
+        c0, c1 = self.model.conv
+        return [c0.lin.weight, c0.att_src, c0.att_dst, c1.lin.weight, c1.att_src, c1.att_dst]
+
+    def _refresh_gat(self, T):
+        """a0s / a0d = T att0 per table row (fitgnn_gat_scores_f32); u = W1^T att1, formed in float64 and rounded once."""
+        from . import _lib
+        W0, as0, ad0, W1, as1, ad1 = ws = self._gat_weights()
+        n, H = T.shape
+        with torch.no_grad():
+            a0s = torch.empty(n, dtype=torch.float32, device=T.device)
+            a0d = torch.empty(n, dtype=torch.float32, device=T.device)
+            as0, ad0 = as0.detach().reshape(-1).contiguous(), ad0.detach().reshape(-1).contiguous()
+            _lib.check(_lib.lib().fitgnn_gat_scores_f32(_lib.dptr(T), T.stride(0), n, H, _lib.dptr(as0), _lib.dptr(ad0), _lib.dptr(a0s),
+                                                        _lib.dptr(a0d), _lib.stream_ptr(T.device)), "fitgnn_gat_scores_f32")
+            W1d = W1.detach().double()
+            u_s = (as1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
+            u_d = (ad1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
+        self._gat = ([(w, w._version) for w in ws], a0s, a0d, u_s, u_d)
+
+    def _gat_state(self):
+        """(T, a0s, a0d, u_s, u_d), remade when the storage or version of any of the six weights has changed."""
+        ws = self._gat_weights()
+        if self._gat is None or not all(ops._same_index(e, w) for e, w in zip(self._gat[0], ws)) or not ops._same_index(self._T, ws[0]):
+            self.refresh()
+        return (self._T[2],) + tuple(self._gat[1:])
 
     def _table(self):
         W0 = self.model.conv[0].lin.weight
@@ -100,9 +151,13 @@ class QueryEngine:
 
     @property
     def table_bytes(self):
-        """Bytes of T (0 on the per-subgraph path, which keeps none)."""
-        if not self.fused:
+        """Bytes of T -- and of the two score vectors on the GAT path (0 on the per-subgraph path, which keeps none)."""
+        kind = self._kind()
+        if kind is None:
             return 0
+        if kind == "gat":
+            T, a0s, a0d = self._gat_state()[:3]
+            return int(T.numel()) * T.element_size() + int(a0s.numel() + a0d.numel()) * a0s.element_size()
         T = self._table()
         return int(T.numel()) * T.element_size()
 
@@ -137,6 +192,11 @@ class QueryEngine:
     def _predict_fused(self, rows):
         m, f = self.model, self.graph.f
         _, xrow = self._operand()
+        if self._kind() == "gat":   # the same pattern in both CSR modes: existing self loops removed, one added per node
+            T, a0s, a0d, u_s, u_d = self._gat_state()
+            G = ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, rows, xrow=xrow, b0=m.conv[0].bias,
+                                     slope0=m.conv[0].negative_slope, slope1=m.conv[1].negative_slope)
+            return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
         G = ops.gcn_query_gather(f.rowptr, f.col, f.val, self._table(), rows, xrow=xrow, b0=m.conv[0].bias)
         return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
 

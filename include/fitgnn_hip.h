@@ -609,6 +609,22 @@ int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const
                                 const int32_t *xrow, const float *b0, const int64_t *rows, int32_t Q, int32_t H, float *G, int64_t ldg,
                                 void *stream);
 
+/* The same for two GATConv layers (heads = 1): G[i][:] = g_q for q = rows[i], attention over both hops, the second layer's Linear
+ * left to the tail (sum beta = 1, so W1 (sum beta h) + b1 is conv1's output):
+ *   h_r = ELU(sum_k alpha_rk T[t(k)] + b0),  alpha_r. = softmax over CSR row r of LeakyReLU(a_src0[t(k)] + a_dst0[t(r)], slope0)
+ *   g_q = sum_j beta_j h_j,                  beta     = softmax over CSR row q of LeakyReLU(u_src . h_j + u_dst . h_q, slope1)
+ * with t(r) = xrow ? xrow[r] : r, a_src0 / a_dst0 the layer-0 score dots per TABLE row (fitgnn_gat_scores_f32 on T) and
+ * u_src = W1^T att_src1, u_dst = W1^T att_dst1 [H].  The pattern (rowptr, col) is the union's CSR with one self loop per node; h_q is
+ * made from row q itself, whether or not q is among its own columns.  One workgroup of four waves per query, a wave on whole rows
+ * (H <= 512), max-subtracted softmaxes with expf, no atomics: two launches give the same bits (operation order: csrc/query.hip).  Any
+ * degree is served.  A row without entries gives h_r = ELU(b0), a query without entries zeros.  xrow, b0 may be NULL.  Writes
+ * G[0..Q) x [0..H) only.  Requires 4 <= H <= 512, H % 4 == 0, ldt, ldg >= H (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G,
+ * u_src, u_dst 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+int fitgnn_gat_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                const float *a_src0, const float *a_dst0, const float *b0, float slope0, const float *u_src,
+                                const float *u_dst, float slope1, const int64_t *rows, int32_t Q, int32_t H, float *G, int64_t ldg,
+                                void *stream);
+
 /* out[i][:] = Wl ELU(W1 G[i] + b1) + bl for i < Q (network.py:31-34 on the aggregated rows: A (h W1^T) = (A h) W1^T), followed by a
  * max-subtracted log-softmax per row when log_softmax != 0 (network.py:35).  W1 [H2 x H], Wl [C x H2] contiguous; b1, bl may be
  * NULL.  One workgroup per tile of 16 queries: the product on the exact-fp32 MFMA (an ascending-k fmaf chain), the tile's z in LDS,

@@ -2,16 +2,17 @@
 """Latency of one node query through fitgnn_amd.serve.QueryEngine against the per-subgraph forward inference.py times without
 --query_engine, on a workloads.py union (GPU only).
 
-    python tools/query_latency.py --workload S-pubmed [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
+    python tools/query_latency.py --workload S-pubmed [--layer GATConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
 
-Writes profiles/query_latency_<workload>.json (or --out):
+--layer GATConv: a two-layer GAT model through QueryEngine(gat_kernels=True) (fitgnn_gat_query_gather_f32 and the same tail).
+Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>_GATConv.json with --layer GATConv; or --out):
   (a) engine_single      median / p90 seconds of predict_rows([row]) per sampled core row, bracketed by device synchronisations as
                          inference.py brackets its forward;
   (b) subgraph_forward   the same rows through inference.timed_forward on the cached subgraph with its CSR pre-built -- measured TWICE
                          per row (b1 before the engine's turn, b2 after it) so that its own run-to-run spread is known;
                          (a), (b1), (b2) alternate row by row inside one process, after one untimed pass over every row;
-  (c) engine_batch       queries per second at Q = --batch, and the gather kernel alone: sum_q sum_{j in row q} deg(j) * H * 4 bytes over
-                         its HIP-event time, next to fitgnn_stream_copy_f32's rate in the same process.
+  (c) engine_batch       queries per second at Q = --batch, and the gather kernel alone: sum_q sum_{j in row q} deg(j) * H * 4 bytes
+                         (GATConv: + deg(q) rows for h_q) over its HIP-event time, next to fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded)."""
 import argparse
 import json
@@ -35,6 +36,7 @@ def _stats(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="S-pubmed")
+    ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv"])
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
@@ -59,11 +61,12 @@ def main():
                                 torch.from_numpy(np.ascontiguousarray(wl["assign"])).to(dev), wl["n_clusters"])
     batch = workloads.batch_from_subgraphs(a.workload, sub, dev)
     del sub, wl
-    margs = argparse.Namespace(num_layers1=2, layer_name="GCNConv", num_features=F, hidden=a.hidden, num_classes=C)
+    margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=F, hidden=a.hidden, num_classes=C)
     torch.manual_seed(2)
     model = network.Classify_node(margs).to(dev).eval()
-    engine = serve.QueryEngine(model, batch)
-    assert engine.fused
+    gat = a.layer == "GATConv"
+    engine = serve.QueryEngine(model, batch, gat_kernels=gat)
+    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -79,7 +82,7 @@ def main():
         r0, r1 = int(ptr[s]), int(ptr[s + 1])
         m = (ei[0] >= r0) & (ei[0] < r1)
         cache[int(s)] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
-        csr_for(cache[int(s)][1], r1 - r0, "gcn")
+        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "gcn")
 
     def engine_once(row):
         torch.cuda.synchronize(dev)
@@ -123,13 +126,18 @@ def main():
         torch.cuda.synchronize()
         t_batch = (time.time() - t) / reps
         f = batch.graph.f
-        T = engine._table()
+        T = engine._gat_state()[0] if gat else engine._table()
         xrow = batch.row_index.index if batch.row_index is not None else None
         G = torch.empty((a.batch, a.hidden), dtype=torch.float32, device=dev)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
         for e0, e1 in ev:
             e0.record()
-            ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
+            if gat:
+                _, a0s, a0d, u_s, u_d = engine._gat_state()
+                ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, qrows, xrow=xrow, b0=model.conv[0].bias,
+                                     slope0=model.conv[0].negative_slope, slope1=model.conv[1].negative_slope, out=G)
+            else:
+                ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
             e1.record()
         torch.cuda.synchronize()
         t_gather = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e-3
@@ -138,6 +146,8 @@ def main():
         csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)     # prefix sums of deg(col[e]) over the entries
         rp = f.rowptr.long()
         table_rows = int((csum[rp[qrows + 1]] - csum[rp[qrows]]).sum())
+        if gat:   # every query also forms h_q from its own row
+            table_rows += int(deg[qrows].sum())
         gather_bytes = table_rows * a.hidden * 4
         n = 64 * 1024 * 1024
         src, dst = torch.empty(n, dtype=torch.float32, device=dev).normal_(), torch.empty(n, dtype=torch.float32, device=dev)
@@ -152,7 +162,7 @@ def main():
     sa, s1, s2 = _stats(ta), _stats(tb1), _stats(tb2)
     base = min(s1["median_us"], s2["median_us"])
     spread = abs(s1["median_us"] - s2["median_us"])
-    res = dict(workload=a.workload, hidden=a.hidden, classes=C, union_rows=int(batch.n_rows), nnz=int(batch.nnz), subgraphs=int(len(ptr) - 1),
+    res = dict(workload=a.workload, layer=a.layer, hidden=a.hidden, classes=C, union_rows=int(batch.n_rows), nnz=int(batch.nnz), subgraphs=int(len(ptr) - 1),
                samples=int(len(rows)), rounds=a.rounds, device=torch.cuda.get_device_name(0),
                table=dict(rows=int(T.shape[0]), bytes=engine.table_bytes, build_s=round(t_table, 4)),
                engine_single=sa, subgraph_forward_first=s1, subgraph_forward_second=s2, per_round=per_round,
@@ -163,7 +173,7 @@ def main():
                                  gather_kernel_s=round(t_gather, 6), gather_table_rows=table_rows, gather_bytes=gather_bytes,
                                  gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
                                  stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}.json")
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_GATConv' if gat else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
