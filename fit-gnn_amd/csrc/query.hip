@@ -8,6 +8,7 @@
 //     z_q   = ELU(W1 g_q + b1);  out_q = Wl z_q + bl  (log_softmax)         fitgnn_gcn_query_tail_f32
 // The union is block-diagonal, so both hops stay inside the query's subgraph: the values are the per-subgraph forward's.
 // Two GATConv layers take the same tail behind fitgnn_gat_query_gather_f32 (attention over both hops: see gat_query_hops_kernel).
+// Two SAGEConv layers take it behind fitgnn_sage_query_gather_f32 (a gather plus a root term: see sage_query_gather_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -322,6 +323,116 @@ __global__ __launch_bounds__(256) void gat_query_hops_kernel(const int32_t *__re
         if (live[s]) *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + s * 256 + lane * 4) = g[s];
 }
 
+// ---- mean aggregation plus a root term (two SAGEConv layers) ----
+//   T     = X [W_l0 ; W_r0]^T                                   [n_table x 2H]: columns [0, H) = X W_l0^T, [H, 2H) = X W_r0^T
+//   h_r   = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b_l0)           t(r) = xrow ? xrow[r] : r
+//   g_q   = sum_{j in row q} val[j] h_{col[j]};   G[i] = [g_q | h_q]: the tail with K = 2H, W1 = [W_l1 | W_r1], b1 = b_l1 finishes.
+// Operation order (tests/sage_query_reference.py mirrors it):
+//   row r    a = 0; a = fmaf(val[e'], T[t(col[e'])][c], a) over row r's entries in CSR order; h_r[c] = ELU((a + T[t(r)][H + c]) + b0[c])
+//            (b0 == NULL: the second add is absent), ELU(x) = x > 0 ? x : expm1f(x); a row without entries: ELU(T[t(r)][H + c] + b0[c]).
+//   query q  the work items are q's deg(q) entries in CSR order followed by one more, q itself; item i belongs to wave i % 4, which
+//            takes its items in ascending i.  An entry item folds p_w = fmaf(val[e], h_{col[e]}, p_w); the last item stores h_q straight
+//            to G[i][H + c] and touches no partial.  g = ((p_0 + p_1) + p_2) + p_3 (a wave without entries holds 0).  A query without
+//            entries gives g = 0 and still h_q.
+// Every h is formed by the same code on a whole wave, whichever wave: the bits depend neither on the slab split nor on the wave.
+
+// One wave: columns c .. c + 3 of layer-0 row r.  Tc: the lane's column in T's aggregate half; the root float4 at + H is requested
+// before the entry loads, so that it is in flight with them.  The entries are fetched 64 at a time and broadcast by v_readlane,
+// four table rows in flight (query_gather_kernel's scheme).
+__device__ __forceinline__ float4 sage_row(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                           const float *__restrict__ val, const float *__restrict__ Tc, int64_t ldt, int32_t H,
+                                           const int32_t *__restrict__ xrow, bool has_bias, const float4 &bias, int r, int lane) {
+    const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+    const int tr = __builtin_amdgcn_readfirstlane(xrow ? xrow[r] : r);
+    const float4 root = *reinterpret_cast<const float4 *>(Tc + (int64_t)tr * ldt + H);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = n0; base < n1; base += 64) {
+        const int cnt = min(64, n1 - base);
+        int my = 0, mv = 0;
+        if (lane < cnt) {
+            const int cc = col[base + lane];
+            my = xrow ? xrow[cc] : cc;
+            mv = __float_as_int(val[base + lane]);
+        }
+        for (int k = 0; k < cnt; k += 4) {
+            float4 t[4];
+            float wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                const int idx = k + u < cnt ? k + u : k;
+                const int node = __builtin_amdgcn_readlane(my, idx);
+                wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
+                t[u] = *reinterpret_cast<const float4 *>(Tc + (int64_t)node * ldt);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k + u < cnt) {
+                    a.x = fmaf(wv[u], t[u].x, a.x);
+                    a.y = fmaf(wv[u], t[u].y, a.y);
+                    a.z = fmaf(wv[u], t[u].z, a.z);
+                    a.w = fmaf(wv[u], t[u].w, a.w);
+                }
+            }
+        }
+    }
+    a.x += root.x; a.y += root.y; a.z += root.z; a.w += root.w;
+    if (has_bias) {  // wave-uniform
+        a.x += bias.x; a.y += bias.y; a.z += bias.z; a.w += bias.w;
+    }
+    return make_float4(elu1(a.x), elu1(a.y), elu1(a.z), elu1(a.w));
+}
+
+// One workgroup per (query, 256-column slab), the slab fastest; 64 lanes x float4 per slab.  The query's entries and, after them,
+// the query itself are dealt round-robin to the four waves; the partials meet in LDS in wave order.
+__global__ __launch_bounds__(256) void sage_query_gather_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                                const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
+                                                                const int32_t *__restrict__ xrow, const float *__restrict__ b0,
+                                                                const int64_t *__restrict__ rows, int32_t H, float *__restrict__ G,
+                                                                int64_t ldg, int32_t n_slabs) {
+    __shared__ float4 part[kGatherWaves][64];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = blockIdx.x / n_slabs, c0 = (blockIdx.x % n_slabs) * 256;
+    const int q = __builtin_amdgcn_readfirstlane((int)rows[qi]);
+    const int e0 = __builtin_amdgcn_readfirstlane(rowptr[q]), e1 = __builtin_amdgcn_readfirstlane(rowptr[q + 1]);
+    const int deg = e1 - e0;
+    const int c = c0 + lane * 4;
+    const bool live = c < H;  // H % 4 == 0: a live lane owns four whole columns
+    const float *Tc = T + (live ? c : 0);
+    const bool has_bias = b0 != nullptr;
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has_bias && live) bias = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = w; i <= deg; i += kGatherWaves) {
+        const bool self = i == deg;  // wave-uniform: the item after the last entry is q itself
+        int j = q;
+        float vq = 0.f;
+        if (!self) {
+            j = __builtin_amdgcn_readfirstlane(col[e0 + i]);
+            vq = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(val[e0 + i])));
+        }
+        const float4 h = sage_row(rowptr, col, val, Tc, ldt, H, xrow, has_bias, bias, j, lane);
+        if (self) {
+            if (live) *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + H + c) = h;
+        } else {
+            p.x = fmaf(vq, h.x, p.x);
+            p.y = fmaf(vq, h.y, p.y);
+            p.z = fmaf(vq, h.z, p.z);
+            p.w = fmaf(vq, h.w, p.w);
+        }
+    }
+    part[w][lane] = p;
+    __syncthreads();
+    if (w == 0 && live) {
+        float4 g = part[0][lane];
+#pragma unroll
+        for (int o = 1; o < kGatherWaves; ++o) {
+            const float4 r = part[o][lane];
+            g.x += r.x; g.y += r.y; g.z += r.z; g.w += r.w;
+        }
+        *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + c) = g;
+    }
+}
+
 // ---- tail ----
 constexpr int kTailQ = 16;      // queries per workgroup: one MFMA tile of rows
 constexpr int kTailKS = 32;      // k-stage
@@ -465,6 +576,21 @@ extern "C" int fitgnn_gat_query_gather_f32(const int32_t *rowptr, const int32_t 
     else
         hipLaunchKernelGGL(gat_query_hops_kernel<2>, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, rowptr, col, T, ldt, xrow, a_src0,
                            a_dst0, b0, slope0, u_src, u_dst, slope1, rows, H, G, ldg);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_sage_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                            const int32_t *xrow, const float *b0, const int64_t *rows, int32_t Q, int32_t H, float *G,
+                                            int64_t ldg, void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || ldt < 2 * (int64_t)H || ldg < 2 * (int64_t)H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !rows || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G) % 16) != 0) return FITGNN_E_ALIGN;
+    const int n_slabs = (H + 255) / 256;
+    if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
+    hipLaunchKernelGGL(sage_query_gather_kernel, dim3((unsigned)(Q * n_slabs)), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, T, ldt,
+                       xrow, b0, rows, H, G, ldg, n_slabs);
     return (int)hipGetLastError();
 }
 

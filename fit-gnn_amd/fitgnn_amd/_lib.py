@@ -128,6 +128,7 @@ SIGNATURES = {
     "fitgnn_gather_rows_padded_f32": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, c_i64, ptr, c_i32, ptr]),
     "fitgnn_appnp_units_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i32, c_i32, c_i32, ptr, ptr, c_i32, c_i32, c_f32, c_i32, ptr]),
     "fitgnn_gcn_query_gather_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, c_i32, c_i32, ptr, c_i64, ptr]),
+    "fitgnn_sage_query_gather_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, c_i32, c_i32, ptr, c_i64, ptr]),
     "fitgnn_gat_query_gather_f32": (ctypes.c_int, [ptr, ptr, ptr, c_i64, ptr, ptr, ptr, ptr, c_f32, ptr, ptr, c_f32, ptr, c_i32, c_i32, ptr,
                                                    c_i64, ptr]),
     "fitgnn_gcn_query_tail_lds_bytes": (c_size, [c_i32, c_i32]),

@@ -1243,6 +1243,37 @@ def gat_query_supported(model):
             and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
 
 
+def sage_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
+    """G [Q, 2H]: row i = [g_q | h_q] for union row q = rows[i] -- the layer-1 mean aggregation over layer-0 SAGE rows and q's own
+    layer-0 row, both made on the fly from T = X [W_l0 ; W_r0]^T [n_table, 2H] (fitgnn_sage_query_gather_f32) over the mean CSR.
+    rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
+    _lib.require_cuda(rowptr, col, val, T, rows, xrow, b0)
+    Q, H = int(rows.numel()), int(T.shape[1]) // 2
+    G = out if out is not None else torch.empty((Q, 2 * H), dtype=torch.float32, device=T.device)
+    _lib.check(_lib.lib().fitgnn_sage_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                       _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
+                                                       _lib.stream_ptr(T.device)), "fitgnn_sage_query_gather_f32")
+    return G
+
+
+def sage_query_supported(model):
+    """fitgnn_sage_query_gather_f32 and the tail answer for `model`: exactly two SAGEConv layers and a head, hidden sizes multiples
+    of 16, a head the tail's LDS holds, contiguous float32 parameters on the GPU (lin_l.bias may be None)."""
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.SAGEConv for c in convs):
+        return False
+    Wl0, Wr0, Wl1, Wr1, Wl = convs[0].lin_l.weight, convs[0].lin_r.weight, convs[1].lin_l.weight, convs[1].lin_r.weight, lt1.weight
+    params = [Wl0, Wr0, Wl1, Wr1, Wl, convs[0].lin_l.bias, convs[1].lin_l.bias, lt1.bias]
+    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        return False
+    H, H2, C = int(Wl0.shape[0]), int(Wl1.shape[0]), int(Wl.shape[0])
+    return (H % 16 == 0 and H2 % 16 == 0 and tuple(Wr0.shape) == tuple(Wl0.shape) and tuple(Wl1.shape) == (H2, H)
+            and tuple(Wr1.shape) == (H2, H) and int(Wl.shape[1]) == H2
+            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+
+
 def segment_sum(seg_off, members, X, n_seg):
     """out[s] = sum of X[members[seg_off[s]:seg_off[s+1]]] (fitgnn_segment_sum_f32)."""
     _lib.require_cuda(seg_off, members, X)

@@ -19,7 +19,15 @@ With gat_kernels=True a model of two GATConv layers (heads = 1) takes the same t
     h_r   = ELU(sum_k alpha_rk T[t(k)] + b0)                            alpha_r. = softmax_k lrelu(a0s[t(k)] + a0d[t(r)], slope0)
     g_q   = sum_j beta_j h_j                                            beta = softmax_j lrelu(u_s . h_j + u_d . h_q, slope1)
 
-Any other model (a GAT model without the flag, SAGE / GIN layers, one or three layers, hidden sizes the kernels do not take) is
+With sage_kernels=True a model of two SAGEConv layers takes two launches as well: its layer is a gather plus a root term, over the
+union's mean CSR (no self loops added, val = 1 / max(deg, 1): what nn.SAGEConv.forward looks up), with t(r) the table row of union row r:
+
+    T     = X [W_l0 ; W_r0]^T    [n_table, 2H]                          once per set of weights (one ops.Linear)
+    h_r   = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b_l0)
+    G_q   = [sum_{j in row q} val[j] h_{col[j]} | h_q]                   ops.sage_query_gather
+    out_q = Wl ELU([W_l1 | W_r1] G_q + b_l1) + bl   (+ log_softmax)      ops.gcn_query_tail, unchanged, with K = 2H
+
+Any other model (a GAT or SAGE model without its flag, GIN layers, one or three layers, hidden sizes the kernels do not take) is
 answered by that per-subgraph forward itself, each subgraph cut out of the union once and kept.
 """
 import numpy as np
@@ -57,11 +65,13 @@ class QueryEngine:
     """predict(node_ids) -> [Q, C] for a trained network.Classify_node (log-probabilities) or network.Regress_node (raw values) over a
     data.SubgraphBatch, extra-node or cluster-node layout, with or without the de-duplicated feature table.  gat_kernels: a model of
     two GATConv layers is answered by the attention query kernel (off by default: its speed against the per-subgraph forward is
-    not measured yet); it changes nothing for any other model."""
+    not measured yet); it changes nothing for any other model.  sage_kernels: the same switch for a model of two SAGEConv layers
+    (the mean-aggregation query kernel), off by default for the same reason."""
 
-    def __init__(self, model, batch, gat_kernels=False):
+    def __init__(self, model, batch, gat_kernels=False, sage_kernels=False):
         self.model, self.batch = model, batch
         self.gat_kernels = bool(gat_kernels)
+        self.sage_kernels = bool(sage_kernels)
         self.log_softmax = not isinstance(model, _regressors())
         g = batch.graph
         if g is None:
@@ -75,21 +85,27 @@ class QueryEngine:
         self._core_row = torch.from_numpy(table).to(dev)
         self._T = None          # (W0, W0._version, T)
         self._subgraphs = {}    # the per-subgraph forward's inputs: s -> (x, edge_index, first row)
-        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | None: the kernels that answer)
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "sage" | None: the kernels that answer)
         self._gat = None        # the GAT path's prepared state: ([(tensor, version)] of the six weights it is made from, a0s, a0d, u_s, u_d)
+        self._sage = None       # the SAGE path's prepared state: ([(tensor, version)] of the four weights it is made from, T, W1cat)
+        self._mean = None       # the union's mean CSR (the SAGE path's pattern), looked up once
 
     # -- the table T = X W0^T --
     def _kind(self):
-        """"gcn" (ops.query_supported), "gat" (gat_kernels and ops.gat_query_supported) or None, re-evaluated only when a layer or a
-        parameter's storage, type or shape has changed."""
+        """"gcn" (ops.query_supported), "gat" (gat_kernels and ops.gat_query_supported), "sage" (sage_kernels and
+        ops.sage_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
         if self.gat_kernels:
             params += [getattr(c, a, None) for c in m.conv for a in ("att_src", "att_dst")]
+        if self.sage_kernels:
+            params += [getattr(getattr(c, l, None), a, None) for c in m.conv for l in ("lin_l", "lin_r") for a in ("weight", "bias")]
         key = tuple(type(c) for c in m.conv) + tuple(None if p is None else (p.data_ptr(), p.dtype, p.shape) for p in params)
         if self._fused is None or self._fused[0] != key:
             kind = "gcn" if ops.query_supported(m) else ("gat" if self.gat_kernels and ops.gat_query_supported(m) else None)
+            if kind is None and self.sage_kernels and ops.sage_query_supported(m):
+                kind = "sage"
             self._fused = (key, kind)
         return self._fused[1]
 
@@ -105,8 +121,10 @@ class QueryEngine:
         return b.x, None
 
     def refresh(self):
-        """Remake T -- and, on the GAT path, the score vectors and W1^T att -- from the model's current weights (done automatically
-        when one of the weights they are made from changes)."""
+        """Remake T -- and, on the GAT path, the score vectors and W1^T att; on the SAGE path, [W_l1 | W_r1] -- from the model's
+        current weights (done automatically when one of the weights they are made from changes)."""
+        if self._kind() == "sage":
+            return self._refresh_sage()
         W0 = self.model.conv[0].lin.weight
         X, _ = self._operand()
         with torch.no_grad():
@@ -143,6 +161,33 @@ class QueryEngine:
             self.refresh()
         return (self._T[2],) + tuple(self._gat[1:])
 
+    def _sage_weights(self):
+        c0, c1 = self.model.conv
+        return [c0.lin_l.weight, c0.lin_r.weight, c1.lin_l.weight, c1.lin_r.weight]
+
+    def _refresh_sage(self):
+        """T = X [W_l0 ; W_r0]^T [n_table, 2H] (one product) and W1cat = [W_l1 | W_r1] [H2, 2H]."""
+        Wl0, Wr0, Wl1, Wr1 = ws = self._sage_weights()
+        X, _ = self._operand()
+        with torch.no_grad():
+            T = ops.Linear.apply(X.float(), torch.cat([Wl0.detach(), Wr0.detach()], 0).contiguous(), self.model.op_config).contiguous()
+            W1cat = torch.cat([Wl1.detach(), Wr1.detach()], 1).contiguous()
+        self._sage = ([(w, w._version) for w in ws], T, W1cat)
+        return self
+
+    def _sage_state(self):
+        """(T, W1cat), remade when the storage or version of any of the four weights has changed."""
+        ws = self._sage_weights()
+        if self._sage is None or not all(ops._same_index(e, w) for e, w in zip(self._sage[0], ws)):
+            self._refresh_sage()
+        return self._sage[1], self._sage[2]
+
+    def _mean_csr(self):
+        """The union's mean CSR (rows = targets, no self loops added, val = 1 / max(deg, 1)): nn.SAGEConv.forward's own lookup."""
+        if self._mean is None:
+            self._mean = csr_for(self.batch.edge_index, self.n_rows, "mean")
+        return self._mean
+
     def _table(self):
         W0 = self.model.conv[0].lin.weight
         if not ops._same_index(self._T, W0):
@@ -151,14 +196,15 @@ class QueryEngine:
 
     @property
     def table_bytes(self):
-        """Bytes of T -- and of the two score vectors on the GAT path (0 on the per-subgraph path, which keeps none)."""
+        """Bytes of T -- [n_table, 2H] on the SAGE path -- and of the two score vectors on the GAT path (0 on the per-subgraph path,
+        which keeps none)."""
         kind = self._kind()
         if kind is None:
             return 0
         if kind == "gat":
             T, a0s, a0d = self._gat_state()[:3]
             return int(T.numel()) * T.element_size() + int(a0s.numel() + a0d.numel()) * a0s.element_size()
-        T = self._table()
+        T = self._sage_state()[0] if kind == "sage" else self._table()
         return int(T.numel()) * T.element_size()
 
     # -- queries --
@@ -197,6 +243,11 @@ class QueryEngine:
             G = ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, rows, xrow=xrow, b0=m.conv[0].bias,
                                      slope0=m.conv[0].negative_slope, slope1=m.conv[1].negative_slope)
             return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
+        if self._kind() == "sage":   # G = [g_q | h_q]: the tail's K is 2H
+            T, W1cat = self._sage_state()
+            f = self._mean_csr().f
+            G = ops.sage_query_gather(f.rowptr, f.col, f.val, T, rows, xrow=xrow, b0=m.conv[0].lin_l.bias)
+            return ops.gcn_query_tail(G, W1cat, m.conv[1].lin_l.bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
         G = ops.gcn_query_gather(f.rowptr, f.col, f.val, self._table(), rows, xrow=xrow, b0=m.conv[0].bias)
         return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
 
@@ -241,4 +292,6 @@ def _layer_mode(model):
         return "gcn"
     if isinstance(conv, fnn.GATConv):
         return "gat"
+    if isinstance(conv, fnn.SAGEConv):
+        return "mean"
     return None

@@ -13,6 +13,7 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::gcn_query_gather(rowptr, col, val, T, rows, xrow?, b0?) -> G      the two node-query launches (fitgnn_amd.serve)
     fitgnn::gcn_query_tail(G, W1, b1?, Wl, bl?, log_softmax) -> out
     fitgnn::gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow?, b0?, slope0, slope1) -> G     its GAT counterpart
+    fitgnn::sage_query_gather(rowptr, col, val, T, rows, xrow?, b0?) -> G [Q, 2H] = [g_q | h_q]     its SAGE counterpart (T [n_table, 2H], the mean CSR)
                                               (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
@@ -39,6 +40,7 @@ _LIB.define("linear(Tensor x, Tensor W) -> Tensor")
 _LIB.define("gcn_query_gather(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor rows, Tensor? xrow, Tensor? b0) -> Tensor")
 _LIB.define("gat_query_gather(Tensor rowptr, Tensor col, Tensor T, Tensor a_src0, Tensor a_dst0, Tensor u_src, Tensor u_dst, Tensor rows, "
             "Tensor? xrow, Tensor? b0, float slope0, float slope1) -> Tensor")
+_LIB.define("sage_query_gather(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor rows, Tensor? xrow, Tensor? b0) -> Tensor")
 _LIB.define("gcn_query_tail(Tensor G, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
 
 
@@ -109,11 +111,15 @@ def _gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow, 
     return ops.gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=xrow, b0=b0, slope0=slope0, slope1=slope1)
 
 
+def _sage_query_gather(rowptr, col, val, T, rows, xrow, b0):
+    return ops.sage_query_gather(rowptr, col, val, T, rows, xrow=xrow, b0=b0)
+
+
 def _gcn_query_tail(G, W1, b1, Wl, bl, log_softmax):
     return ops.gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=log_softmax)
 
 
-for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
+for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
                    ("lift_adjacency", _lift_adjacency)):
     _LIB.impl(_name, _fn, "CUDA")
@@ -172,6 +178,11 @@ def _(rowptr, col, val, T, rows, xrow, b0):
 
 @torch.library.register_fake("fitgnn::gat_query_gather")
 def _(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow, b0, slope0, slope1):
+    return T.new_empty((rows.shape[0], T.shape[1]))
+
+
+@torch.library.register_fake("fitgnn::sage_query_gather")
+def _(rowptr, col, val, T, rows, xrow, b0):
     return T.new_empty((rows.shape[0], T.shape[1]))
 
 

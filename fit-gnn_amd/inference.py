@@ -10,7 +10,8 @@ and, with --baseline, on the full graph (inference.py:651-666).  Unlike the refe
 bracketed by a device synchronisation (the reference's time() around an asynchronous launch measures launch time).
 Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50), --query_engine
 (opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows inside the same timing bracket; same CSV row),
---query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel).
+--query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel), --query_sage (with
+--query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel).
 """
 import argparse
 import os
@@ -75,6 +76,9 @@ def build_parser():
     p.add_argument('--query_attention', action='store_true',
                    help="with --query_engine: a --layer_name GATConv model of two layers is answered by the attention query kernel "
                         "(QueryEngine(gat_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
+    p.add_argument('--query_sage', action='store_true',
+                   help="with --query_engine: a --layer_name SAGEConv model of two layers is answered by the mean-aggregation query kernel "
+                        "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
     return p
 
 
@@ -211,7 +215,7 @@ def main(argv=None):
     engine = None
     if args.query_engine:   # built outside the timed region, as the per-subgraph CSR is below; T = X W0^T is made here too
         from fitgnn_amd.serve import QueryEngine
-        engine = QueryEngine(model, batch, gat_kernels=args.query_attention)
+        engine = QueryEngine(model, batch, gat_kernels=args.query_attention, sage_kernels=args.query_sage)
         if engine.fused:
             engine.refresh()
         else:
@@ -234,7 +238,7 @@ def main(argv=None):
                 m = (ei[0] >= r0) & (ei[0] < r1)
                 cache[s] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
                 # static per-subgraph CSR in the mode the model's layers look up, built once outside the timed call
-                csr_for(cache[s][1], r1 - r0, "gat" if args.layer_name == "GATConv" else "gcn")
+                csr_for(cache[s][1], r1 - r0, {"GATConv": "gat", "SAGEConv": "mean"}.get(args.layer_name, "gcn"))
             x, e, r0 = cache[s]
             out, dt = timed_forward(model, x, e, dev)
             j = row - r0

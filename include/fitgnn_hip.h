@@ -625,6 +625,21 @@ int fitgnn_gat_query_gather_f32(const int32_t *rowptr, const int32_t *col, const
                                 const float *u_dst, float slope1, const int64_t *rows, int32_t Q, int32_t H, float *G, int64_t ldg,
                                 void *stream);
 
+/* The same for two SAGEConv layers (aggr = mean, root weight): G[i][0:H) = g_q and G[i][H:2H) = h_q for q = rows[i], over
+ * T = X [W_l0 ; W_r0]^T [n_table x 2H] (row stride ldt; columns [0, H) = X W_l0^T, [H, 2H) = X W_r0^T):
+ *   h_r = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b0),   g_q = sum_{j in row q} val[j] h_{col[j]}
+ * with t(r) = xrow ? xrow[r] : r, over the union's mean CSR (no self loops added, val = 1 / max(deg, 1)).  The tail with K = 2H,
+ * W1 = [W_l1 | W_r1] and b1 = b_l1 then gives conv1, ELU and the head.  One workgroup of four waves per query and 256-column slab
+ * (the columns are independent: H is not limited); the query's entries and, after them, the query itself are dealt round-robin to
+ * the waves, every sum runs in CSR order with fmaf, the partial rows are added in wave order, no atomics: two launches give the
+ * same bits (operation order: csrc/query.hip).  Any degree is served.  A row without entries gives ELU(T[t(r)][H:2H] + b0), a query
+ * without entries g = 0 and still h_q.  xrow, b0 may be NULL.  rows (int64, values in [0, n_rows)) may repeat and need no order.
+ * Writes G[0..Q) x [0..2H) only.  Requires H >= 4, H % 4 == 0, ldt, ldg >= 2H (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G
+ * 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+int fitgnn_sage_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                 const int32_t *xrow, const float *b0, const int64_t *rows, int32_t Q, int32_t H, float *G,
+                                 int64_t ldg, void *stream);
+
 /* out[i][:] = Wl ELU(W1 G[i] + b1) + bl for i < Q (network.py:31-34 on the aggregated rows: A (h W1^T) = (A h) W1^T), followed by a
  * max-subtracted log-softmax per row when log_softmax != 0 (network.py:35).  W1 [H2 x H], Wl [C x H2] contiguous; b1, bl may be
  * NULL.  One workgroup per tile of 16 queries: the product on the exact-fp32 MFMA (an ascending-k fmaf chain), the tile's z in LDS,

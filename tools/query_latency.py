@@ -2,17 +2,21 @@
 """Latency of one node query through fitgnn_amd.serve.QueryEngine against the per-subgraph forward inference.py times without
 --query_engine, on a workloads.py union (GPU only).
 
-    python tools/query_latency.py --workload S-pubmed [--layer GATConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
+    python tools/query_latency.py --workload S-pubmed [--layer GATConv | SAGEConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
 
 --layer GATConv: a two-layer GAT model through QueryEngine(gat_kernels=True) (fitgnn_gat_query_gather_f32 and the same tail).
-Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>_GATConv.json with --layer GATConv; or --out):
+--layer SAGEConv: a two-layer SAGE model through QueryEngine(sage_kernels=True) (fitgnn_sage_query_gather_f32 over the mean CSR and the
+same tail with K = 2H).
+Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>_<layer>.json with --layer GATConv / SAGEConv; or --out):
   (a) engine_single      median / p90 seconds of predict_rows([row]) per sampled core row, bracketed by device synchronisations as
                          inference.py brackets its forward;
   (b) subgraph_forward   the same rows through inference.timed_forward on the cached subgraph with its CSR pre-built -- measured TWICE
                          per row (b1 before the engine's turn, b2 after it) so that its own run-to-run spread is known;
                          (a), (b1), (b2) alternate row by row inside one process, after one untimed pass over every row;
   (c) engine_batch       queries per second at Q = --batch, and the gather kernel alone: sum_q sum_{j in row q} deg(j) * H * 4 bytes
-                         (GATConv: + deg(q) rows for h_q) over its HIP-event time, next to fitgnn_stream_copy_f32's rate in the same process.
+                         (GATConv: + deg(q) rows for h_q; SAGEConv: sum_j deg(j) + deg(q) aggregate half-rows and deg(q) + 1 root
+                         half-rows of 4 H bytes, 12 bytes of CSR per entry, 8 H bytes written per query) over its HIP-event time, next to
+                         fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded)."""
 import argparse
 import json
@@ -36,7 +40,7 @@ def _stats(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="S-pubmed")
-    ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv"])
+    ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv", "SAGEConv"])
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
@@ -65,8 +69,9 @@ def main():
     torch.manual_seed(2)
     model = network.Classify_node(margs).to(dev).eval()
     gat = a.layer == "GATConv"
-    engine = serve.QueryEngine(model, batch, gat_kernels=gat)
-    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.query_supported(model))
+    sage = a.layer == "SAGEConv"
+    engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage)
+    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.sage_query_supported(model) if sage else ops.query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -82,7 +87,7 @@ def main():
         r0, r1 = int(ptr[s]), int(ptr[s + 1])
         m = (ei[0] >= r0) & (ei[0] < r1)
         cache[int(s)] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
-        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "gcn")
+        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "mean" if sage else "gcn")
 
     def engine_once(row):
         torch.cuda.synchronize(dev)
@@ -125,10 +130,10 @@ def main():
             engine.predict_rows(qrows)
         torch.cuda.synchronize()
         t_batch = (time.time() - t) / reps
-        f = batch.graph.f
-        T = engine._gat_state()[0] if gat else engine._table()
+        f = engine._mean_csr().f if sage else batch.graph.f
+        T = engine._gat_state()[0] if gat else engine._sage_state()[0] if sage else engine._table()
         xrow = batch.row_index.index if batch.row_index is not None else None
-        G = torch.empty((a.batch, a.hidden), dtype=torch.float32, device=dev)
+        G = torch.empty((a.batch, 2 * a.hidden if sage else a.hidden), dtype=torch.float32, device=dev)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
         for e0, e1 in ev:
             e0.record()
@@ -136,6 +141,8 @@ def main():
                 _, a0s, a0d, u_s, u_d = engine._gat_state()
                 ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, qrows, xrow=xrow, b0=model.conv[0].bias,
                                      slope0=model.conv[0].negative_slope, slope1=model.conv[1].negative_slope, out=G)
+            elif sage:
+                ops.sage_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].lin_l.bias, out=G)
             else:
                 ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
             e1.record()
@@ -149,6 +156,10 @@ def main():
         if gat:   # every query also forms h_q from its own row
             table_rows += int(deg[qrows].sum())
         gather_bytes = table_rows * a.hidden * 4
+        if sage:   # aggregate half-rows of the neighbours' rows and of row q itself, one root half-row per layer-0 row made
+            dq = int(deg[qrows].sum())
+            table_rows += dq
+            gather_bytes = (table_rows + dq + a.batch) * a.hidden * 4 + 12 * table_rows + a.batch * 8 * a.hidden
         n = 64 * 1024 * 1024
         src, dst = torch.empty(n, dtype=torch.float32, device=dev).normal_(), torch.empty(n, dtype=torch.float32, device=dev)
         cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
@@ -173,7 +184,7 @@ def main():
                                  gather_kernel_s=round(t_gather, 6), gather_table_rows=table_rows, gather_bytes=gather_bytes,
                                  gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
                                  stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_GATConv' if gat else ''}.json")
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_' + a.layer if gat or sage else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
