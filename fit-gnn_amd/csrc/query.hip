@@ -9,6 +9,8 @@
 // The union is block-diagonal, so both hops stay inside the query's subgraph: the values are the per-subgraph forward's.
 // Two GATConv layers take the same tail behind fitgnn_gat_query_gather_f32 (attention over both hops: see gat_query_hops_kernel).
 // Two SAGEConv layers take it behind fitgnn_sage_query_gather_f32 (a gather plus a root term: see sage_query_gather_kernel).
+// Two GINConv layers have launches of their own, fitgnn_gin_query_hops_f32 and fitgnn_gin_query_tail_f32 (a dense product behind a
+// ReLU per one-hop row: see gin_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -447,6 +449,45 @@ __host__ __device__ constexpr size_t tail_lds_floats(int H2, int C) {
 }
 static_assert(tail_lds_floats(512, 48) * sizeof(float) <= kTailLdsMax, "the default model's tail must fit LDS");
 
+// The head and the log-softmax of a tile whose z [16][zld] is in LDS (written before a barrier): logits into lg [16][C], then out.
+__device__ __forceinline__ void tail_head(const float *zs, int zld, int32_t H2, const float *__restrict__ Wl, const float *__restrict__ bl,
+                                          int32_t C, float *lg, float *__restrict__ out, int64_t ldo, int q0, int nq, int32_t log_softmax) {
+    const int tid = threadIdx.x;
+    // the head: 16 consecutive lanes share a class (one broadcast read of Wl) and read 16 rows of z, 4 banks apart
+    for (int o = tid; o < kTailQ * C; o += 256) {
+        const int qi = o & (kTailQ - 1), c = o >> 4;
+        const float *wl = Wl + (int64_t)c * H2;
+        const float *z = zs + qi * zld;
+        float s = 0.f;
+        for (int h = 0; h < H2; h += 4) {
+            const float4 wv = *reinterpret_cast<const float4 *>(wl + h);
+            const float4 zv = *reinterpret_cast<const float4 *>(z + h);
+            s = fmaf(zv.x, wv.x, s);
+            s = fmaf(zv.y, wv.y, s);
+            s = fmaf(zv.z, wv.z, s);
+            s = fmaf(zv.w, wv.w, s);
+        }
+        lg[qi * C + c] = bl ? s + bl[c] : s;
+    }
+    __syncthreads();
+    if (log_softmax) {
+        if (tid < nq) {
+            float *row = lg + tid * C;
+            float m = row[0];
+            for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+            float s = 0.f;
+            for (int c = 0; c < C; ++c) s += expf(row[c] - m);
+            const float l = logf(s);
+            for (int c = 0; c < C; ++c) row[c] = (row[c] - m) - l;
+        }
+        __syncthreads();
+    }
+    for (int o = tid; o < nq * C; o += 256) {  // rows of a partial last tile are not stored
+        const int qi = o / C, c = o - qi * C;
+        out[(int64_t)(q0 + qi) * ldo + c] = lg[o];
+    }
+}
+
 // One workgroup per tile of up to 16 queries.  z = ELU(G W1^T + b1) on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4],
 // B: W1[n = l & 15][k = l >> 4], C/D: column l & 15, rows 4 (l >> 4) + r), W1 and the tile's rows of G staged through LDS in
 // k-stages of 32; the tile's z stays in LDS, the head reads it from there.
@@ -509,39 +550,311 @@ __global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict
     }
     __syncthreads();
 
-    // the head: 16 consecutive lanes share a class (one broadcast read of Wl) and read 16 rows of z, 4 banks apart
-    for (int o = tid; o < kTailQ * C; o += 256) {
-        const int qi = o & (kTailQ - 1), c = o >> 4;
-        const float *wl = Wl + (int64_t)c * H2;
-        const float *z = zs + qi * zld;
-        float s = 0.f;
-        for (int h = 0; h < H2; h += 4) {
-            const float4 wv = *reinterpret_cast<const float4 *>(wl + h);
-            const float4 zv = *reinterpret_cast<const float4 *>(z + h);
-            s = fmaf(zv.x, wv.x, s);
-            s = fmaf(zv.y, wv.y, s);
-            s = fmaf(zv.z, wv.z, s);
-            s = fmaf(zv.w, wv.w, s);
-        }
-        lg[qi * C + c] = bl ? s + bl[c] : s;
+    tail_head(zs, zld, H2, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
+}
+
+// ---- an MLP over both hops (two GINConv layers, nn = Linear, ReLU, Linear, ReLU) ----
+//   T     = X W0a^T                                                                  [n_table x Ha]   t(r) = xrow ? xrow[r] : r
+//   a_r   = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a)    [Ha]
+//   h_r   = ReLU(W0b a_r + b0b)                                                      [Hb]: a dense product per one-hop row
+//   s_q   = sum_{j in row q} val[j] h_{col[j]} + (1 + eps1) h_q                      [Hb] -> G[i];  gin_query_tail_kernel finishes.
+// Only W0a commutes with the aggregation; W0b sits behind a ReLU, so every one-hop row of the query takes the product itself.
+// Operation order (tests/gin_query_reference.py mirrors it), with o0 = 1.0f + eps0[0] and o1 = 1.0f + eps1[0] formed once in fp32:
+//   row r    a = 0; a = fmaf(val[e'], T[t(col[e'])][c], a) over row r's entries in CSR order; a = fmaf(o0, T[t(r)][c], a);
+//            a = a + b0a[c] (b0a == NULL: this add is absent); a_r[c] = max(a, 0).
+//   product  h_r[n] = max((fmaf chain over k ascending of a_r[k] W0b[n][k], from 0) + b0b[n], 0)   (v_mfma_f32_16x16x4_f32: exact fp32,
+//            bit-equal to that chain; b0b == NULL adds 0.0f).
+//   query q  the work items are q's deg(q) entries in CSR order followed by q itself, taken in tiles of 16; item i has weight
+//            w_i = val[e_i], the query's own item o1.  Item i belongs to fold group (i % 16) / 4.  A group folds its items in ascending i,
+//            across tiles: P_g = fmaf(w_i, h_i, P_g) from 0; the rows past the last item of a partial tile are not folded.
+//            s = ((P_0 + P_1) + P_2) + P_3 (a group without items holds 0).  A query without entries gives fmaf(o1, h_q, 0).
+// The bits depend on no split: a row of a_r is formed by one wave, whichever; a column of h and its fold live in one lane per group.
+constexpr int kGinRows = 16;  // items per tile: one MFMA tile of rows
+
+__host__ __device__ constexpr size_t gin_hops_lds_floats(int Ha) { return (size_t)kGinRows * (Ha + 4) + (size_t)kTailCols * kTailLd; }
+static_assert(2 * gin_hops_lds_floats(512) * sizeof(float) <= kTailLdsMax, "two workgroups per CU at Ha = 512");
+
+// One wave: row r of a (before the dense product) into a[].  Tc[s]: the lane's column of slot s in T (a lane past Ha reads column 0
+// and is never stored).  sage_row's scheme: the root float4 is requested first, the entries are fetched 64 at a time and broadcast
+// by v_readlane, four table rows in flight.
+template <int NS>
+__device__ __forceinline__ void gin_row(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+                                        const float *const (&Tc)[NS], int64_t ldt, const int32_t *__restrict__ xrow, float o0, bool has_bias,
+                                        const float4 (&bias)[NS], int r, int lane, float4 (&a)[NS]) {
+    const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+    const int tr = __builtin_amdgcn_readfirstlane(xrow ? xrow[r] : r);
+    float4 root[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        root[s] = *reinterpret_cast<const float4 *>(Tc[s] + (int64_t)tr * ldt);
+        a[s] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    __syncthreads();
-    if (log_softmax) {
-        if (tid < nq) {
-            float *row = lg + tid * C;
-            float m = row[0];
-            for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
-            float s = 0.f;
-            for (int c = 0; c < C; ++c) s += expf(row[c] - m);
-            const float l = logf(s);
-            for (int c = 0; c < C; ++c) row[c] = (row[c] - m) - l;
+    for (int base = n0; base < n1; base += 64) {
+        const int cnt = min(64, n1 - base);
+        int my = 0, mv = 0;
+        if (lane < cnt) {
+            const int cc = col[base + lane];
+            my = xrow ? xrow[cc] : cc;
+            mv = __float_as_int(val[base + lane]);
+        }
+        for (int k = 0; k < cnt; k += 4) {
+            float4 t[4][NS];
+            float wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                const int idx = k + u < cnt ? k + u : k;
+                const int node = __builtin_amdgcn_readlane(my, idx);
+                wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
+#pragma unroll
+                for (int s = 0; s < NS; ++s) t[u][s] = *reinterpret_cast<const float4 *>(Tc[s] + (int64_t)node * ldt);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k + u < cnt) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        a[s].x = fmaf(wv[u], t[u][s].x, a[s].x);
+                        a[s].y = fmaf(wv[u], t[u][s].y, a[s].y);
+                        a[s].z = fmaf(wv[u], t[u][s].z, a[s].z);
+                        a[s].w = fmaf(wv[u], t[u][s].w, a[s].w);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        a[s].x = fmaf(o0, root[s].x, a[s].x);
+        a[s].y = fmaf(o0, root[s].y, a[s].y);
+        a[s].z = fmaf(o0, root[s].z, a[s].z);
+        a[s].w = fmaf(o0, root[s].w, a[s].w);
+        if (has_bias) {  // wave-uniform
+            a[s].x += bias[s].x; a[s].y += bias[s].y; a[s].z += bias[s].z; a[s].w += bias[s].w;
+        }
+        a[s] = make_float4(fmaxf(a[s].x, 0.f), fmaxf(a[s].y, 0.f), fmaxf(a[s].z, 0.f), fmaxf(a[s].w, 0.f));
+    }
+}
+
+// acc += A W^T for one pass of up to 256 columns n0 .. n0 + ncols of W [N x K] (row-major, contiguous), the tile's 16 rows of A in
+// LDS (row stride lda): W staged through LDS in k-stages of 32 with query_tail_kernel's lane layout (A: lane l holds A[l & 15][k = l >> 4],
+// B: W[n = l & 15][k = l >> 4], C/D: column l & 15, rows 4 (l >> 4) + r).  The barrier in front of every stage also orders A's writers.
+__device__ __forceinline__ void lds_tile_product(const float *As, int lda, const float *__restrict__ W, int K, int n0, int ncols, float *Ws,
+                                                 f32x4 (&acc)[4]) {
+    const int tid = threadIdx.x, w = tid >> 6, r16 = tid & 15, kq = (tid & 63) >> 4;
+    for (int k0 = 0; k0 < K; k0 += kTailKS) {
+        const int k4 = min(kTailKS, K - k0) >> 2;  // float4 per staged row (K % 4 == 0)
+        __syncthreads();                           // the previous stage has been consumed; A is complete
+        for (int idx = tid; idx < ncols * k4; idx += 256) {
+            const int n = idx / k4, kk = idx - n * k4;
+            *reinterpret_cast<float4 *>(Ws + n * kTailLd + kk * 4) = *reinterpret_cast<const float4 *>(W + (int64_t)(n0 + n) * K + k0 + kk * 4);
         }
         __syncthreads();
+        for (int kk = 0; kk < k4; ++kk) {
+            const float a = As[r16 * lda + k0 + kk * 4 + kq];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int nb = (w * 4 + u) * 16;
+                if (nb < ncols) {  // wave-uniform
+                    const float b = Ws[(nb + r16) * kTailLd + kk * 4 + kq];
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[u], 0, 0, 0);
+                }
+            }
+        }
     }
-    for (int o = tid; o < nq * C; o += 256) {  // rows of a partial last tile are not stored
-        const int qi = o / C, c = o - qi * C;
-        out[(int64_t)(q0 + qi) * ldo + c] = lg[o];
+}
+
+// One workgroup of four waves per query.  Per tile of 16 items the waves form the rows a_r into LDS (item i by wave i % 4, whole rows
+// of Ha <= 256 NS columns), then all four multiply the tile by W0b^T (NP passes of 256 columns of Hb) and fold the rows of h into the
+// running sums: a lane keeps one column of each of its accumulators for its fold group l >> 4.  The groups meet by v shuffles at the end.
+template <int NS, int NP>
+__global__ __launch_bounds__(256) void gin_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                             const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
+                                                             const int32_t *__restrict__ xrow, const float *__restrict__ b0a,
+                                                             const float *__restrict__ eps0, const float *__restrict__ W0b,
+                                                             const float *__restrict__ b0b, const float *__restrict__ eps1,
+                                                             const int64_t *__restrict__ rows, int32_t Ha, int32_t Hb, float *__restrict__ G,
+                                                             int64_t ldg) {
+    extern __shared__ float smem[];
+    const int ald = Ha + 4;
+    float *As = smem;
+    float *Ws = As + (size_t)kGinRows * ald;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r16 = lane & 15, kq = lane >> 4;
+    const int qi = blockIdx.x;
+    const int q = __builtin_amdgcn_readfirstlane((int)rows[qi]);
+    const int e0 = __builtin_amdgcn_readfirstlane(rowptr[q]), e1 = __builtin_amdgcn_readfirstlane(rowptr[q + 1]);
+    const int deg = e1 - e0, items = deg + 1;
+    const float o0 = 1.0f + eps0[0], o1 = 1.0f + eps1[0];
+    const bool has_bias = b0a != nullptr;
+    const float *Tc[NS];
+    float4 bias[NS];
+    bool live[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int c = s * 256 + lane * 4;
+        live[s] = c < Ha;  // Ha % 4 == 0: a live lane owns four whole columns
+        Tc[s] = T + (live[s] ? c : 0);
+        bias[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (has_bias && live[s]) bias[s] = make_float4(b0a[c], b0a[c + 1], b0a[c + 2], b0a[c + 3]);
     }
+    float P[NP][4];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) P[p][u] = 0.f;
+
+    for (int t0 = 0; t0 < items; t0 += kGinRows) {
+        __syncthreads();  // the previous tile's product has read As
+        for (int i = w; i < kGinRows; i += 4) {
+            const int item = t0 + i;
+            float4 a[NS];
+            if (item < items) {  // wave-uniform
+                const int r = item < deg ? __builtin_amdgcn_readfirstlane(col[e0 + item]) : q;
+                gin_row<NS>(rowptr, col, val, Tc, ldt, xrow, o0, has_bias, bias, r, lane, a);
+            } else {  // a defined row for the MFMA; its h is never folded
+#pragma unroll
+                for (int s = 0; s < NS; ++s) a[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (live[s]) *reinterpret_cast<float4 *>(As + i * ald + s * 256 + lane * 4) = a[s];
+        }
+        float wt[4];
+        bool on[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // the lane's four rows of the tile
+            const int item = t0 + kq * 4 + r;
+            on[r] = item < items;
+            wt[r] = item < deg ? val[e0 + item] : o1;
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int n0 = p * kTailCols;
+            const int ncols = min(kTailCols, Hb - n0);  // a multiple of 16; NP > 1 only when Hb > 256
+            f32x4 acc[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            lds_tile_product(As, ald, W0b, Ha, n0, ncols, Ws, acc);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int nb = (w * 4 + u) * 16;
+                if (nb < ncols) {
+                    const float b = b0b ? b0b[n0 + nb + r16] : 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (on[r]) P[p][u] = fmaf(wt[r], fmaxf(acc[u][r] + b, 0.f), P[p][u]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int n0 = p * kTailCols;
+        const int ncols = min(kTailCols, Hb - n0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {  // wave-uniform: all 64 lanes take part in the shuffles
+                const float v = P[p][u];
+                const float v1 = __shfl(v, r16 + 16, 64), v2 = __shfl(v, r16 + 32, 64), v3 = __shfl(v, r16 + 48, 64);
+                if (kq == 0) G[(int64_t)qi * ldg + n0 + nb + r16] = ((v + v1) + v2) + v3;
+            }
+        }
+    }
+}
+
+// ---- the GIN tail: two dense stages, then the head ----
+__host__ __device__ constexpr size_t gin_tail_lds_floats(int H2a, int H2b, int C) {
+    return (size_t)kTailQ * (H2a + 4) + (size_t)kTailQ * (H2b + 4) + (size_t)kTailCols * kTailLd + (size_t)kTailQ * kTailLd + (size_t)kTailQ * C;
+}
+static_assert(gin_tail_lds_floats(512, 512, 48) * sizeof(float) <= kTailLdsMax, "the default model's tail must fit LDS");
+
+// zs[r][n] = max(A W^T + b, 0) for the tile's 16 rows of A in LDS and every column n < N, in passes of 256 columns.
+__device__ __forceinline__ void relu_stage(const float *As, int lda, const float *__restrict__ W, const float *__restrict__ b, int K, int N,
+                                           float *Ws, float *zs, int zld) {
+    const int w = threadIdx.x >> 6, r16 = threadIdx.x & 15, kq = (threadIdx.x & 63) >> 4;
+    for (int n0 = 0; n0 < N; n0 += kTailCols) {
+        const int ncols = min(kTailCols, N - n0);  // a multiple of 16
+        f32x4 acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        lds_tile_product(As, lda, W, K, n0, ncols, Ws, acc);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {
+                const int n = n0 + nb + r16;
+                const float bias = b ? b[n] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zs[(kq * 4 + r) * zld + n] = fmaxf(acc[u][r] + bias, 0.f);
+            }
+        }
+    }
+}
+
+// One workgroup per tile of up to 16 queries: z1 = ReLU(S W1a^T + b1a) with the tile's rows of S = G staged through LDS beside W1a
+// (query_tail_kernel's first product), z2 = ReLU(z1 W1b^T + b1b) from z1 in LDS, both on v_mfma_f32_16x16x4_f32, then tail_head on z2.
+__global__ __launch_bounds__(256) void gin_query_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1a,
+                                                             const float *__restrict__ b1a, const float *__restrict__ W1b,
+                                                             const float *__restrict__ b1b, const float *__restrict__ Wl,
+                                                             const float *__restrict__ bl, int32_t K, int32_t H2a, int32_t H2b, int32_t C,
+                                                             float *__restrict__ out, int64_t ldo, int32_t log_softmax) {
+    extern __shared__ float smem[];
+    const int z1ld = H2a + 4, z2ld = H2b + 4;
+    float *z1 = smem;
+    float *z2 = z1 + (size_t)kTailQ * z1ld;
+    float *Ws = z2 + (size_t)kTailQ * z2ld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *lg = Gs + kTailQ * kTailLd;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
+    const int q0 = blockIdx.x * kTailQ;
+    const int nq = min(kTailQ, Q - q0);
+
+    for (int n0 = 0; n0 < H2a; n0 += kTailCols) {
+        const int ncols = min(kTailCols, H2a - n0);  // a multiple of 16
+        f32x4 acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < K; k0 += kTailKS) {
+            const int k4 = min(kTailKS, K - k0) >> 2;  // float4 per staged row (K % 4 == 0)
+            __syncthreads();                           // the previous stage has been consumed
+            for (int idx = tid; idx < ncols * k4; idx += 256) {
+                const int n = idx / k4, kk = idx - n * k4;
+                *reinterpret_cast<float4 *>(Ws + n * kTailLd + kk * 4) =
+                    *reinterpret_cast<const float4 *>(W1a + (int64_t)(n0 + n) * K + k0 + kk * 4);
+            }
+            for (int idx = tid; idx < kTailQ * k4; idx += 256) {
+                const int r = idx / k4, kk = idx - r * k4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);  // rows past Q: computed as zeros, never stored
+                if (r < nq) v = *reinterpret_cast<const float4 *>(G + (int64_t)(q0 + r) * ldg + k0 + kk * 4);
+                *reinterpret_cast<float4 *>(Gs + r * kTailLd + kk * 4) = v;
+            }
+            __syncthreads();
+            for (int kk = 0; kk < k4; ++kk) {
+                const float a = Gs[r16 * kTailLd + kk * 4 + kq];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int nb = (w * 4 + u) * 16;
+                    if (nb < ncols) {  // wave-uniform
+                        const float b = Ws[(nb + r16) * kTailLd + kk * 4 + kq];
+                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[u], 0, 0, 0);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {
+                const int n = n0 + nb + r16;
+                const float bias = b1a ? b1a[n] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) z1[(kq * 4 + r) * z1ld + n] = fmaxf(acc[u][r] + bias, 0.f);
+            }
+        }
+    }
+    relu_stage(z1, z1ld, W1b, b1b, H2a, H2b, Ws, z2, z2ld);  // its first barrier orders z1's writers
+    __syncthreads();
+    tail_head(z2, z2ld, H2b, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
 }
 
 }  // namespace
@@ -613,5 +926,58 @@ extern "C" int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q,
     if (const int rc = fitgnn_lds_limit_once((const void *)query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
     hipLaunchKernelGGL(query_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1, b1,
                        Wl, bl, H, H2, C, out, ldo, log_softmax);
+    return (int)hipGetLastError();
+}
+
+template <int NS, int NP>
+static int launch_gin_hops(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt, const int32_t *xrow,
+                           const float *b0a, const float *eps0, const float *W0b, const float *b0b, const float *eps1, const int64_t *rows,
+                           int32_t Q, int32_t Ha, int32_t Hb, float *G, int64_t ldg, hipStream_t stream) {
+    static std::atomic<uint64_t> lds_done{0};
+    const size_t lds = gin_hops_lds_floats(Ha) * sizeof(float);
+    if (const int rc = fitgnn_lds_limit_once((const void *)gin_query_hops_kernel<NS, NP>, (int)(gin_hops_lds_floats(512) * sizeof(float)), lds_done))
+        return rc;
+    hipLaunchKernelGGL((gin_query_hops_kernel<NS, NP>), dim3((unsigned)Q), dim3(256), lds, stream, rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b,
+                       b0b, eps1, rows, Ha, Hb, G, ldg);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_gin_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                         const int32_t *xrow, const float *b0a, const float *eps0, const float *W0b, const float *b0b,
+                                         const float *eps1, const int64_t *rows, int32_t Q, int32_t Ha, int32_t Hb, float *G, int64_t ldg,
+                                         void *stream) {
+    if (Q < 0 || Ha < 4 || (Ha % 4) != 0 || Ha > 512 || Hb < 16 || (Hb % 16) != 0 || Hb > 512 || ldt < Ha || ldg < Hb) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !eps0 || !W0b || !eps1 || !rows || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G | (uintptr_t)W0b) % 16) != 0) return FITGNN_E_ALIGN;
+    const hipStream_t st = (hipStream_t)stream;
+    if (Ha <= 256)
+        return Hb <= 256 ? launch_gin_hops<1, 1>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, rows, Q, Ha, Hb, G, ldg, st)
+                         : launch_gin_hops<1, 2>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, rows, Q, Ha, Hb, G, ldg, st);
+    return Hb <= 256 ? launch_gin_hops<2, 1>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, rows, Q, Ha, Hb, G, ldg, st)
+                     : launch_gin_hops<2, 2>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, rows, Q, Ha, Hb, G, ldg, st);
+}
+
+extern "C" size_t fitgnn_gin_query_tail_lds_bytes(int32_t H2a, int32_t H2b, int32_t C) {
+    if (H2a <= 0 || H2b <= 0 || C <= 0) return 0;
+    return gin_tail_lds_floats(H2a, H2b, C) * sizeof(float);
+}
+
+extern "C" int fitgnn_gin_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1a, const float *b1a, const float *W1b,
+                                         const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a, int32_t H2b, int32_t C,
+                                         float *out, int64_t ldo, int32_t log_softmax, void *stream) {
+    if (Q < 0 || K < 4 || (K % 4) != 0 || H2a < 16 || (H2a % 16) != 0 || H2b < 16 || (H2b % 16) != 0 || C < 1 || ldg < K || ldo < C)
+        return FITGNN_E_BADARG;
+    if ((ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gin_query_tail_lds_bytes(H2a, H2b, C);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // z1 and z2 of the tile do not fit LDS
+    if (Q == 0) return 0;
+    if (!G || !W1a || !W1b || !Wl || !out) return FITGNN_E_BADARG;
+    if ((((uintptr_t)G | (uintptr_t)W1a | (uintptr_t)W1b | (uintptr_t)Wl | (uintptr_t)out) % 16) != 0) return FITGNN_E_ALIGN;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)gin_query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(gin_query_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1a,
+                       b1a, W1b, b1b, Wl, bl, K, H2a, H2b, C, out, ldo, log_softmax);
     return (int)hipGetLastError();
 }

@@ -1274,6 +1274,63 @@ def sage_query_supported(model):
             and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
 
 
+def gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow=None, b0a=None, out=None):
+    """G [Q, Hb]: row i = s_q = sum_{j in row q} val[j] h_j + (1 + eps1) h_q for union row q = rows[i], with
+    h_r = ReLU(W0b ReLU(sum_k val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a) + b0b) made on the fly from T = X W0a^T [n_table, Ha]
+    over the sum CSR (fitgnn_gin_query_hops_f32).  eps0 / eps1: float32 tensors of one element ON THE DEVICE, read by the kernel.
+    rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
+    _lib.require_cuda(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow, b0a)
+    Q, Ha, Hb = int(rows.numel()), int(T.shape[1]), int(W0b.shape[0])
+    G = out if out is not None else torch.empty((Q, Hb), dtype=torch.float32, device=T.device)
+    _lib.check(_lib.lib().fitgnn_gin_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                    _lib.dptr(xrow), _lib.dptr(b0a), _lib.dptr(eps0), _lib.dptr(W0b), _lib.dptr(b0b),
+                                                    _lib.dptr(eps1), _lib.dptr(rows), Q, Ha, Hb, _lib.dptr(G), G.stride(0),
+                                                    _lib.stream_ptr(T.device)), "fitgnn_gin_query_hops_f32")
+    return G
+
+
+def gin_query_tail(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax=False, out=None):
+    """[Q, C] = Wl ReLU(W1b ReLU(W1a G^T + b1a) + b1b) + bl per row, log-softmax on request (fitgnn_gin_query_tail_f32).
+    W1a [H2a, K], W1b [H2b, H2a], Wl [C, H2b] contiguous."""
+    _lib.require_cuda(G, W1a, b1a, W1b, b1b, Wl, bl)
+    Q, K = int(G.shape[0]), int(G.shape[1])
+    H2a, H2b, C = int(W1a.shape[0]), int(W1b.shape[0]), int(Wl.shape[0])
+    y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
+    _lib.check(_lib.lib().fitgnn_gin_query_tail_f32(_lib.dptr(G), G.stride(0), Q, _lib.dptr(W1a), _lib.dptr(b1a), _lib.dptr(W1b),
+                                                    _lib.dptr(b1b), _lib.dptr(Wl), _lib.dptr(bl), K, H2a, H2b, C, _lib.dptr(y), y.stride(0),
+                                                    1 if log_softmax else 0, _lib.stream_ptr(G.device)), "fitgnn_gin_query_tail_f32")
+    return y
+
+
+def gin_query_supported(model):
+    """fitgnn_gin_query_hops_f32 and fitgnn_gin_query_tail_f32 answer for `model`: exactly two GINConv layers and a head, each nn a
+    Sequential of exactly Linear, ReLU, Linear, ReLU (the model's ELU is the identity only behind a ReLU) whose shapes chain, hidden
+    sizes multiples of 16 and at most 512, a tail the LDS holds, contiguous float32 parameters and eps (buffer or parameter) on the GPU."""
+    from torch import nn as tnn
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GINConv for c in convs):
+        return False
+    for c in convs:
+        mlp = c.nn
+        if not (isinstance(mlp, tnn.Sequential) and len(mlp) == 4 and isinstance(mlp[0], tnn.Linear) and type(mlp[1]) is tnn.ReLU
+                and isinstance(mlp[2], tnn.Linear) and type(mlp[3]) is tnn.ReLU):
+            return False
+    lins = [convs[0].nn[0], convs[0].nn[2], convs[1].nn[0], convs[1].nn[2]]
+    eps = [getattr(c, "eps", None) for c in convs]
+    params = [w for l in lins for w in (l.weight, l.bias)] + [lt1.weight, lt1.bias]
+    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        return False
+    if not all(torch.is_tensor(e) and e.is_cuda and e.dtype == torch.float32 and e.numel() == 1 and e.is_contiguous() for e in eps):
+        return False
+    hidden = [int(l.weight.shape[0]) for l in lins]
+    chain = all(int(b.weight.shape[1]) == h for b, h in zip(lins[1:] + [lt1], hidden))
+    C = int(lt1.weight.shape[0])
+    return (chain and all(h % 16 == 0 and h <= 512 for h in hidden)
+            and 0 < _lib.lib().fitgnn_gin_query_tail_lds_bytes(hidden[2], hidden[3], C) <= 160 * 1024)
+
+
 def segment_sum(seg_off, members, X, n_seg):
     """out[s] = sum of X[members[seg_off[s]:seg_off[s+1]]] (fitgnn_segment_sum_f32)."""
     _lib.require_cuda(seg_off, members, X)

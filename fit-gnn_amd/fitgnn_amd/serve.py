@@ -27,8 +27,21 @@ union's mean CSR (no self loops added, val = 1 / max(deg, 1): what nn.SAGEConv.f
     G_q   = [sum_{j in row q} val[j] h_{col[j]} | h_q]                   ops.sage_query_gather
     out_q = Wl ELU([W_l1 | W_r1] G_q + b_l1) + bl   (+ log_softmax)      ops.gcn_query_tail, unchanged, with K = 2H
 
-Any other model (a GAT or SAGE model without its flag, GIN layers, one or three layers, hidden sizes the kernels do not take) is
-answered by that per-subgraph forward itself, each subgraph cut out of the union once and kept.
+With gin_kernels=True a model of two GINConv layers whose nn is Linear, ReLU, Linear, ReLU (network._make_convs) takes two launches
+of its own, over the union's sum CSR (no self loops added, val = 1: what nn.GINConv.forward looks up).  Only the first Linear of a
+layer commutes with the aggregation; the second sits behind a ReLU and runs once per one-hop row of the query, inside the first launch:
+
+    T     = X W0a^T    [n_table, Ha]                                    once per set of weights (one ops.Linear, no bias)
+    a_r   = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a)
+    h_r   = ReLU(W0b a_r + b0b)                                         the dense product, per one-hop row
+    s_q   = sum_{j in row q} val[j] h_{col[j]} + (1 + eps1) h_q         ops.gin_query_hops (eps read on the device)
+    out_q = Wl ReLU(W1b ReLU(W1a s_q + b1a) + b1b) + bl  (+ log_softmax) ops.gin_query_tail
+
+(the model's ELU after each conv is the identity on a ReLU output: the path holds only for an MLP that ends in ReLU).  Its latency
+against the per-subgraph forward is not measured, so it is opt-in as the other two are.
+
+Any other model (a GAT, SAGE or GIN model without its flag, a GIN model with another MLP, one or three layers, hidden sizes the
+kernels do not take) is answered by that per-subgraph forward itself, each subgraph cut out of the union once and kept.
 """
 import numpy as np
 import torch
@@ -66,12 +79,15 @@ class QueryEngine:
     data.SubgraphBatch, extra-node or cluster-node layout, with or without the de-duplicated feature table.  gat_kernels: a model of
     two GATConv layers is answered by the attention query kernel (off by default: its speed against the per-subgraph forward is
     not measured yet); it changes nothing for any other model.  sage_kernels: the same switch for a model of two SAGEConv layers
-    (the mean-aggregation query kernel), off by default for the same reason."""
+    (the mean-aggregation query kernel), off by default for the same reason.  gin_kernels: the same switch for a model of two GINConv
+    layers with the reference's two-Linear ReLU MLP (the hops kernel with its dense product and the two-stage tail), off by default
+    for the same reason."""
 
-    def __init__(self, model, batch, gat_kernels=False, sage_kernels=False):
+    def __init__(self, model, batch, gat_kernels=False, sage_kernels=False, gin_kernels=False):
         self.model, self.batch = model, batch
         self.gat_kernels = bool(gat_kernels)
         self.sage_kernels = bool(sage_kernels)
+        self.gin_kernels = bool(gin_kernels)
         self.log_softmax = not isinstance(model, _regressors())
         g = batch.graph
         if g is None:
@@ -85,15 +101,17 @@ class QueryEngine:
         self._core_row = torch.from_numpy(table).to(dev)
         self._T = None          # (W0, W0._version, T)
         self._subgraphs = {}    # the per-subgraph forward's inputs: s -> (x, edge_index, first row)
-        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "sage" | None: the kernels that answer)
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "sage" | "gin" | None: the kernels that answer)
         self._gat = None        # the GAT path's prepared state: ([(tensor, version)] of the six weights it is made from, a0s, a0d, u_s, u_d)
         self._sage = None       # the SAGE path's prepared state: ([(tensor, version)] of the four weights it is made from, T, W1cat)
         self._mean = None       # the union's mean CSR (the SAGE path's pattern), looked up once
+        self._gin = None        # the GIN path's prepared state: ((W0a, version), T)
+        self._sum = None        # the union's sum CSR (the GIN path's pattern), looked up once
 
     # -- the table T = X W0^T --
     def _kind(self):
         """"gcn" (ops.query_supported), "gat" (gat_kernels and ops.gat_query_supported), "sage" (sage_kernels and
-        ops.sage_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
+        ops.sage_query_supported), "gin" (gin_kernels and ops.gin_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
@@ -101,11 +119,18 @@ class QueryEngine:
             params += [getattr(c, a, None) for c in m.conv for a in ("att_src", "att_dst")]
         if self.sage_kernels:
             params += [getattr(getattr(c, l, None), a, None) for c in m.conv for l in ("lin_l", "lin_r") for a in ("weight", "bias")]
-        key = tuple(type(c) for c in m.conv) + tuple(None if p is None else (p.data_ptr(), p.dtype, p.shape) for p in params)
+        if self.gin_kernels:
+            mlps = [getattr(c, "nn", None) for c in m.conv]
+            subs = [list(n) if isinstance(n, torch.nn.Sequential) else [] for n in mlps]
+            params += [getattr(l, a, None) for n in subs for l in n for a in ("weight", "bias")] + [getattr(c, "eps", None) for c in m.conv]
+            params += [type(l) for n in subs for l in n]     # an activation swapped in place changes no parameter
+        key = tuple(type(c) for c in m.conv) + tuple((p.data_ptr(), p.dtype, p.shape) if torch.is_tensor(p) else p for p in params)
         if self._fused is None or self._fused[0] != key:
             kind = "gcn" if ops.query_supported(m) else ("gat" if self.gat_kernels and ops.gat_query_supported(m) else None)
             if kind is None and self.sage_kernels and ops.sage_query_supported(m):
                 kind = "sage"
+            if kind is None and self.gin_kernels and ops.gin_query_supported(m):
+                kind = "gin"
             self._fused = (key, kind)
         return self._fused[1]
 
@@ -125,6 +150,8 @@ class QueryEngine:
         current weights (done automatically when one of the weights they are made from changes)."""
         if self._kind() == "sage":
             return self._refresh_sage()
+        if self._kind() == "gin":
+            return self._refresh_gin()
         W0 = self.model.conv[0].lin.weight
         X, _ = self._operand()
         with torch.no_grad():
@@ -188,6 +215,27 @@ class QueryEngine:
             self._mean = csr_for(self.batch.edge_index, self.n_rows, "mean")
         return self._mean
 
+    def _refresh_gin(self):
+        """T = X W0a^T [n_table, Ha]: the first Linear of conv0's MLP, without its bias (the kernel adds it behind the aggregation)."""
+        W0a = self.model.conv[0].nn[0].weight
+        X, _ = self._operand()
+        with torch.no_grad():
+            T = ops.Linear.apply(X.float(), W0a, self.model.op_config).contiguous()
+        self._gin = ((W0a, W0a._version), T)
+        return self
+
+    def _gin_state(self):
+        """T, remade when the storage or version of W0a has changed; every other weight and both eps are read at every call."""
+        if self._gin is None or not ops._same_index(self._gin[0], self.model.conv[0].nn[0].weight):
+            self._refresh_gin()
+        return self._gin[1]
+
+    def _sum_csr(self):
+        """The union's sum CSR (rows = targets, no self loops added, val = 1): nn.GINConv.forward's own lookup."""
+        if self._sum is None:
+            self._sum = csr_for(self.batch.edge_index, self.n_rows, "sum")
+        return self._sum
+
     def _table(self):
         W0 = self.model.conv[0].lin.weight
         if not ops._same_index(self._T, W0):
@@ -196,7 +244,7 @@ class QueryEngine:
 
     @property
     def table_bytes(self):
-        """Bytes of T -- [n_table, 2H] on the SAGE path -- and of the two score vectors on the GAT path (0 on the per-subgraph path,
+        """Bytes of T -- [n_table, 2H] on the SAGE path, [n_table, Ha] on the GIN path -- and of the two score vectors on the GAT path (0 on the per-subgraph path,
         which keeps none)."""
         kind = self._kind()
         if kind is None:
@@ -204,7 +252,7 @@ class QueryEngine:
         if kind == "gat":
             T, a0s, a0d = self._gat_state()[:3]
             return int(T.numel()) * T.element_size() + int(a0s.numel() + a0d.numel()) * a0s.element_size()
-        T = self._sage_state()[0] if kind == "sage" else self._table()
+        T = self._sage_state()[0] if kind == "sage" else self._gin_state() if kind == "gin" else self._table()
         return int(T.numel()) * T.element_size()
 
     # -- queries --
@@ -248,6 +296,12 @@ class QueryEngine:
             f = self._mean_csr().f
             G = ops.sage_query_gather(f.rowptr, f.col, f.val, T, rows, xrow=xrow, b0=m.conv[0].lin_l.bias)
             return ops.gcn_query_tail(G, W1cat, m.conv[1].lin_l.bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
+        if self._kind() == "gin":    # eps0 / eps1 stay on the device: the kernel reads them
+            (_, _, l0b, _), (l1a, _, l1b, _) = m.conv[0].nn, m.conv[1].nn
+            f = self._sum_csr().f
+            G = ops.gin_query_hops(f.rowptr, f.col, f.val, self._gin_state(), m.conv[0].eps.detach(), l0b.weight, l0b.bias,
+                                   m.conv[1].eps.detach(), rows, xrow=xrow, b0a=m.conv[0].nn[0].bias)
+            return ops.gin_query_tail(G, l1a.weight, l1a.bias, l1b.weight, l1b.bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
         G = ops.gcn_query_gather(f.rowptr, f.col, f.val, self._table(), rows, xrow=xrow, b0=m.conv[0].bias)
         return ops.gcn_query_tail(G, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, log_softmax=self.log_softmax)
 
@@ -292,6 +346,8 @@ def _layer_mode(model):
         return "gcn"
     if isinstance(conv, fnn.GATConv):
         return "gat"
+    if isinstance(conv, fnn.GINConv):
+        return "sum"
     if isinstance(conv, fnn.SAGEConv):
         return "mean"
     return None

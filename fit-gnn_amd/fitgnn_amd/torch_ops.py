@@ -14,6 +14,8 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::gcn_query_tail(G, W1, b1?, Wl, bl?, log_softmax) -> out
     fitgnn::gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow?, b0?, slope0, slope1) -> G     its GAT counterpart
     fitgnn::sage_query_gather(rowptr, col, val, T, rows, xrow?, b0?) -> G [Q, 2H] = [g_q | h_q]     its SAGE counterpart (T [n_table, 2H], the mean CSR)
+    fitgnn::gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b?, eps1, rows, xrow?, b0a?) -> G [Q, Hb]     the GIN pair (T [n_table, Ha], the sum CSR,
+    fitgnn::gin_query_tail(G, W1a, b1a?, W1b, b1b?, Wl, bl?, log_softmax) -> out                           eps0 / eps1 one float each on the device)
                                               (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
@@ -41,6 +43,9 @@ _LIB.define("gcn_query_gather(Tensor rowptr, Tensor col, Tensor val, Tensor T, T
 _LIB.define("gat_query_gather(Tensor rowptr, Tensor col, Tensor T, Tensor a_src0, Tensor a_dst0, Tensor u_src, Tensor u_dst, Tensor rows, "
             "Tensor? xrow, Tensor? b0, float slope0, float slope1) -> Tensor")
 _LIB.define("sage_query_gather(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor rows, Tensor? xrow, Tensor? b0) -> Tensor")
+_LIB.define("gin_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor eps0, Tensor W0b, Tensor? b0b, Tensor eps1, Tensor rows, "
+            "Tensor? xrow, Tensor? b0a) -> Tensor")
+_LIB.define("gin_query_tail(Tensor G, Tensor W1a, Tensor? b1a, Tensor W1b, Tensor? b1b, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
 _LIB.define("gcn_query_tail(Tensor G, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
 
 
@@ -115,11 +120,19 @@ def _sage_query_gather(rowptr, col, val, T, rows, xrow, b0):
     return ops.sage_query_gather(rowptr, col, val, T, rows, xrow=xrow, b0=b0)
 
 
+def _gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow, b0a):
+    return ops.gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow=xrow, b0a=b0a)
+
+
+def _gin_query_tail(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax):
+    return ops.gin_query_tail(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax=log_softmax)
+
+
 def _gcn_query_tail(G, W1, b1, Wl, bl, log_softmax):
     return ops.gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=log_softmax)
 
 
-for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
+for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gin_query_hops", _gin_query_hops), ("gin_query_tail", _gin_query_tail), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
                    ("lift_adjacency", _lift_adjacency)):
     _LIB.impl(_name, _fn, "CUDA")
@@ -184,6 +197,16 @@ def _(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow, b0, slope0, slop
 @torch.library.register_fake("fitgnn::sage_query_gather")
 def _(rowptr, col, val, T, rows, xrow, b0):
     return T.new_empty((rows.shape[0], T.shape[1]))
+
+
+@torch.library.register_fake("fitgnn::gin_query_hops")
+def _(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow, b0a):
+    return T.new_empty((rows.shape[0], W0b.shape[0]))
+
+
+@torch.library.register_fake("fitgnn::gin_query_tail")
+def _(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax):
+    return G.new_empty((G.shape[0], Wl.shape[0]))
 
 
 @torch.library.register_fake("fitgnn::gcn_query_tail")

@@ -11,7 +11,8 @@ bracketed by a device synchronisation (the reference's time() around an asynchro
 Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50), --query_engine
 (opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows inside the same timing bracket; same CSV row),
 --query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel), --query_sage (with
---query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel).
+--query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel), --query_gin (with --query_engine: a
+two-layer GINConv model is answered by the GIN query kernels).
 """
 import argparse
 import os
@@ -79,6 +80,9 @@ def build_parser():
     p.add_argument('--query_sage', action='store_true',
                    help="with --query_engine: a --layer_name SAGEConv model of two layers is answered by the mean-aggregation query kernel "
                         "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
+    p.add_argument('--query_gin', action='store_true',
+                   help="with --query_engine: a --layer_name GINConv model of two layers is answered by the GIN query kernels "
+                        "(QueryEngine(gin_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
     return p
 
 
@@ -215,7 +219,7 @@ def main(argv=None):
     engine = None
     if args.query_engine:   # built outside the timed region, as the per-subgraph CSR is below; T = X W0^T is made here too
         from fitgnn_amd.serve import QueryEngine
-        engine = QueryEngine(model, batch, gat_kernels=args.query_attention, sage_kernels=args.query_sage)
+        engine = QueryEngine(model, batch, gat_kernels=args.query_attention, sage_kernels=args.query_sage, gin_kernels=args.query_gin)
         if engine.fused:
             engine.refresh()
         else:
@@ -238,7 +242,7 @@ def main(argv=None):
                 m = (ei[0] >= r0) & (ei[0] < r1)
                 cache[s] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
                 # static per-subgraph CSR in the mode the model's layers look up, built once outside the timed call
-                csr_for(cache[s][1], r1 - r0, {"GATConv": "gat", "SAGEConv": "mean"}.get(args.layer_name, "gcn"))
+                csr_for(cache[s][1], r1 - r0, {"GATConv": "gat", "SAGEConv": "mean", "GINConv": "sum"}.get(args.layer_name, "gcn"))
             x, e, r0 = cache[s]
             out, dt = timed_forward(model, x, e, dev)
             j = row - r0

@@ -650,6 +650,37 @@ size_t fitgnn_gcn_query_tail_lds_bytes(int32_t H2, int32_t C);
 int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl, const float *bl,
                               int32_t H, int32_t H2, int32_t C, float *out, int64_t ldo, int32_t log_softmax, void *stream);
 
+/* Two GINConv layers whose nn is Linear, ReLU, Linear, ReLU (network.py:19-21) have two launches of their own.  The first:
+ * G[i][0:Hb) = s_q for q = rows[i], over T = X W0a^T [n_table x Ha] (row stride ldt):
+ *   a_r = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a),   h_r = ReLU(W0b a_r + b0b),
+ *   s_q = sum_{j in row q} val[j] h_{col[j]} + (1 + eps1) h_q
+ * with t(r) = xrow ? xrow[r] : r, over the union's sum CSR (no self loops added, val = 1; val is read all the same).  W0b [Hb x Ha]
+ * contiguous.  eps0, eps1 are DEVICE pointers to one float each, read by the kernel; 1 + eps is formed once as 1.0f + eps.  One
+ * workgroup of four waves per query: the query's entries and, after them, the query itself are taken in tiles of 16 rows; the waves
+ * form the rows a_r into LDS, the tile is multiplied by W0b^T on the exact-fp32 MFMA (an ascending-k fmaf chain; W0b staged through
+ * LDS in k-stages of 32) and the rows of h are folded into s_q with fmaf in a fixed order, no atomics: two launches give the same
+ * bits (operation order: csrc/query.hip).  Any degree is served.  A query without entries gives (1 + eps1) h_q.  xrow, b0a, b0b may
+ * be NULL.  rows (int64, values in [0, n_rows)) may repeat and need no order.  Writes G[0..Q) x [0..Hb) only.  LDS: 16 (Ha + 4) + 9216
+ * floats (68 KiB at Ha = 512: two workgroups per CU).  Requires Ha >= 4, Ha % 4 == 0, Hb >= 16, Hb % 16 == 0, Ha, Hb <= 512, ldt >= Ha,
+ * ldg >= Hb (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, W0b, G 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a
+ * launch. */
+int fitgnn_gin_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                              const int32_t *xrow, const float *b0a, const float *eps0, const float *W0b, const float *b0b,
+                              const float *eps1, const int64_t *rows, int32_t Q, int32_t Ha, int32_t Hb, float *G, int64_t ldg,
+                              void *stream);
+
+/* The second: out[i][:] = Wl ReLU(W1b ReLU(W1a G[i] + b1a) + b1b) + bl for i < Q (conv1's nn on s_q, then lt1; the model's ELU is the
+ * identity on a ReLU output), followed by a max-subtracted log-softmax per row when log_softmax != 0.  W1a [H2a x K], W1b [H2b x H2a],
+ * Wl [C x H2b] contiguous; b1a, b1b, bl may be NULL.  One workgroup per tile of 16 queries: both products on the exact-fp32 MFMA
+ * (ascending-k fmaf chains), z1 and z2 of the tile in LDS, the head and the log-softmax exactly as fitgnn_gcn_query_tail_f32 makes
+ * them.  Rows of a partial last tile are not stored.  Requires K % 4 == 0, H2a % 16 == 0, H2b % 16 == 0, C >= 1, ldg >= K, ldo >= C
+ * and fitgnn_gin_query_tail_lds_bytes(H2a, H2b, C) <= 160 KiB (FITGNN_E_BADARG); ldg a multiple of 4 and G, W1a, W1b, Wl, out 16-byte
+ * aligned (FITGNN_E_ALIGN). */
+size_t fitgnn_gin_query_tail_lds_bytes(int32_t H2a, int32_t H2b, int32_t C);
+int fitgnn_gin_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1a, const float *b1a, const float *W1b,
+                              const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a, int32_t H2b, int32_t C,
+                              float *out, int64_t ldo, int32_t log_softmax, void *stream);
+
 /* =====================================================================================
  * Coarsen half: one contraction level of variation_neighborhoods
  * replaces: graph_coarsening/coarsening_utils.py contract_variation_linear :530-650,

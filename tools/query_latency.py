@@ -2,12 +2,14 @@
 """Latency of one node query through fitgnn_amd.serve.QueryEngine against the per-subgraph forward inference.py times without
 --query_engine, on a workloads.py union (GPU only).
 
-    python tools/query_latency.py --workload S-pubmed [--layer GATConv | SAGEConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
+    python tools/query_latency.py --workload S-pubmed [--layer GATConv | SAGEConv | GINConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
 
 --layer GATConv: a two-layer GAT model through QueryEngine(gat_kernels=True) (fitgnn_gat_query_gather_f32 and the same tail).
 --layer SAGEConv: a two-layer SAGE model through QueryEngine(sage_kernels=True) (fitgnn_sage_query_gather_f32 over the mean CSR and the
 same tail with K = 2H).
-Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>_<layer>.json with --layer GATConv / SAGEConv; or --out):
+--layer GINConv: a two-layer GIN model through QueryEngine(gin_kernels=True) (fitgnn_gin_query_hops_f32 over the sum CSR, with a dense
+H x H product per one-hop row, and fitgnn_gin_query_tail_f32).
+Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>_<layer>.json with --layer GATConv / SAGEConv / GINConv; or --out):
   (a) engine_single      median / p90 seconds of predict_rows([row]) per sampled core row, bracketed by device synchronisations as
                          inference.py brackets its forward;
   (b) subgraph_forward   the same rows through inference.timed_forward on the cached subgraph with its CSR pre-built -- measured TWICE
@@ -15,7 +17,9 @@ Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>
                          (a), (b1), (b2) alternate row by row inside one process, after one untimed pass over every row;
   (c) engine_batch       queries per second at Q = --batch, and the gather kernel alone: sum_q sum_{j in row q} deg(j) * H * 4 bytes
                          (GATConv: + deg(q) rows for h_q; SAGEConv: sum_j deg(j) + deg(q) aggregate half-rows and deg(q) + 1 root
-                         half-rows of 4 H bytes, 12 bytes of CSR per entry, 8 H bytes written per query) over its HIP-event time, next to
+                         half-rows of 4 H bytes, 12 bytes of CSR per entry, 8 H bytes written per query; GINConv: sum_j deg(j) + 2 deg(q) + 1
+                         table rows, 12 bytes of CSR per entry, 4 H bytes written and ceil((deg(q) + 1) / 16) passes over the 4 H H bytes of
+                         W0b per query, which come from L2: gather_bytes counts them, so its rate is not an HBM rate) over its HIP-event time, next to
                          fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded)."""
 import argparse
@@ -40,7 +44,7 @@ def _stats(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="S-pubmed")
-    ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv", "SAGEConv"])
+    ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv", "SAGEConv", "GINConv"])
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
@@ -70,8 +74,10 @@ def main():
     model = network.Classify_node(margs).to(dev).eval()
     gat = a.layer == "GATConv"
     sage = a.layer == "SAGEConv"
-    engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage)
-    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.sage_query_supported(model) if sage else ops.query_supported(model))
+    gin = a.layer == "GINConv"
+    engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage, gin_kernels=gin)
+    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.sage_query_supported(model) if sage
+                             else ops.gin_query_supported(model) if gin else ops.query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -87,7 +93,7 @@ def main():
         r0, r1 = int(ptr[s]), int(ptr[s + 1])
         m = (ei[0] >= r0) & (ei[0] < r1)
         cache[int(s)] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
-        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "mean" if sage else "gcn")
+        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "mean" if sage else "sum" if gin else "gcn")
 
     def engine_once(row):
         torch.cuda.synchronize(dev)
@@ -130,8 +136,8 @@ def main():
             engine.predict_rows(qrows)
         torch.cuda.synchronize()
         t_batch = (time.time() - t) / reps
-        f = engine._mean_csr().f if sage else batch.graph.f
-        T = engine._gat_state()[0] if gat else engine._sage_state()[0] if sage else engine._table()
+        f = engine._mean_csr().f if sage else engine._sum_csr().f if gin else batch.graph.f
+        T = engine._gat_state()[0] if gat else engine._sage_state()[0] if sage else engine._gin_state() if gin else engine._table()
         xrow = batch.row_index.index if batch.row_index is not None else None
         G = torch.empty((a.batch, 2 * a.hidden if sage else a.hidden), dtype=torch.float32, device=dev)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
@@ -143,6 +149,10 @@ def main():
                                      slope0=model.conv[0].negative_slope, slope1=model.conv[1].negative_slope, out=G)
             elif sage:
                 ops.sage_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].lin_l.bias, out=G)
+            elif gin:
+                l0a, l0b = model.conv[0].nn[0], model.conv[0].nn[2]
+                ops.gin_query_hops(f.rowptr, f.col, f.val, T, model.conv[0].eps.detach(), l0b.weight, l0b.bias, model.conv[1].eps.detach(),
+                                   qrows, xrow=xrow, b0a=l0a.bias, out=G)
             else:
                 ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
             e1.record()
@@ -160,6 +170,11 @@ def main():
             dq = int(deg[qrows].sum())
             table_rows += dq
             gather_bytes = (table_rows + dq + a.batch) * a.hidden * 4 + 12 * table_rows + a.batch * 8 * a.hidden
+        if gin:   # every layer-0 row made also reads its own table row; W0b once per tile of 16 items
+            dq = int(deg[qrows].sum())
+            tiles = int(((deg[qrows] + 1 + 15) // 16).sum())
+            table_rows += 2 * dq + a.batch
+            gather_bytes = table_rows * a.hidden * 4 + 12 * (table_rows - dq - a.batch) + a.batch * 4 * a.hidden + tiles * 4 * a.hidden * a.hidden
         n = 64 * 1024 * 1024
         src, dst = torch.empty(n, dtype=torch.float32, device=dev).normal_(), torch.empty(n, dtype=torch.float32, device=dev)
         cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
@@ -184,7 +199,7 @@ def main():
                                  gather_kernel_s=round(t_gather, 6), gather_table_rows=table_rows, gather_bytes=gather_bytes,
                                  gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
                                  stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_' + a.layer if gat or sage else ''}.json")
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_' + a.layer if gat or sage or gin else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
