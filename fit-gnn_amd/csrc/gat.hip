@@ -832,6 +832,7 @@ constexpr int kLdsKeep = 4;     // items per thread: rows of a range x w <= kLds
 constexpr int kLdsFly = 2;      // items of a thread whose operand reads are in flight together (2: the step's results, held in
                                 // registers until the barrier, spill at 1 024 threads x 128 registers)
 constexpr int kLdsShort = 16;   // rows of more entries than this are summed by a wavefront
+constexpr int kLdsNotMine = 31; // entry-count code of an item that is not its thread's to step (no short row has 31 entries)
 constexpr int kLdsMaxBytes = 160 * 1024;
 
 struct LdsPlan { int cap_rows, cap_entries, cap_long; size_t bytes; };
@@ -910,17 +911,21 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
 #pragma unroll
         for (int j = 0; j < kLdsKeep; ++j) {
             const int i = tid + j * T;
-            int e = 0, cnt = 0;   // cnt 0 = not this thread's (beyond the range, or a wavefront's long row)
+            // code kLdsNotMine = not this thread's (beyond the range, or a wavefront's long row); 0 .. kLdsShort = its row's entry count
+            // (0: a row without entries -- its sum is 0, its result alpha z_0, and its alpha-sum runs like any other row's)
+            int e = 0, cnt = 0, code = kLdsNotMine;
             if (i < total) {
                 const int row = i >> lw;
-                e = s_rp[row];
-                const int len = s_rp[row + 1] - e;
-                cnt = len <= kLdsShort ? len : 0;
+                const int len = s_rp[row + 1] - s_rp[row];
+                if (len <= kLdsShort) {
+                    e = s_rp[row];
+                    cnt = code = len;
+                }
             }
-            it_en[j] = ((uint32_t)e << 5) | (uint32_t)cnt;
+            it_en[j] = ((uint32_t)e << 5) | (uint32_t)code;
             uint32_t c4[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) c4[t] = s_col[e + (t < cnt ? t : 0)];   // (unconditional reads, all in flight: entry 0 exists)
+            for (int t = 0; t < 4; ++t) c4[t] = s_col[e + (t < cnt ? t : 0)];   // (unconditional reads, all in flight: e <= the range's entries, inside cap_entries' slack)
 #pragma unroll
             for (int t = 0; t < 4; ++t) c4[t] = t < cnt ? (uint32_t)(((int)c4[t] << lw) + (i & (w - 1))) : 0u;
             it_c[j][0] = c4[0] | (c4[1] << 16);
@@ -937,7 +942,7 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
             if (BWD) {   // the running alpha-sum first (its operand is not live beside the eight gathers below)
 #pragma unroll
                 for (int j = jh; j < jh + kLdsFly; ++j)
-                    if ((it_en[j] & 31u) > 0) {
+                    if ((it_en[j] & 31u) != (uint32_t)kLdsNotMine) {
                         const float4 xs = cur[tid + j * T];
                         keep[j].x = fmaf(alpha, xs.x, keep[j].x); keep[j].y = fmaf(alpha, xs.y, keep[j].y);
                         keep[j].z = fmaf(alpha, xs.z, keep[j].z); keep[j].w = fmaf(alpha, xs.w, keep[j].w);
@@ -952,12 +957,13 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
             for (int j = jh; j < jh + kLdsFly; ++j)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    x[j][t] = cur[(it_c[j][t >> 1] >> (16 * (t & 1))) & 0xffffu];   // (an absent entry reads slot 0 at weight 0)
+                    // (an absent entry reads slot 0 at weight 0; an item that is not this thread's reads s_val[0 .. 3], unused)
+                    x[j][t] = cur[(it_c[j][t >> 1] >> (16 * (t & 1))) & 0xffffu];
                     it_v[j][t] = t < (int)(it_en[j] & 31u) ? s_val[(it_en[j] >> 5) + t] : 0.f;
                 }
 #pragma unroll
             for (int j = jh; j < jh + kLdsFly; ++j) {
-                if ((it_en[j] & 31u) > 0) {
+                if ((it_en[j] & 31u) != (uint32_t)kLdsNotMine) {
                     const int i = tid + j * T;
                     const int q = i & (w - 1);
                     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1039,7 +1045,7 @@ __global__ __launch_bounds__(1024) void appnp_lds_kernel(const int32_t *__restri
             __syncthreads();   // every gather of the step done
 #pragma unroll
             for (int j = 0; j < kLdsKeep; ++j)
-                if ((it_en[j] & 31u) > 0) buf[tid + j * T] = yv[j];
+                if ((it_en[j] & 31u) != (uint32_t)kLdsNotMine) buf[tid + j * T] = yv[j];
             for (int i = tid; i < (n_long << lw); i += T) buf[((int)s_long[i >> lw] << lw) + (i & (w - 1))] = s_ylong[i];
             __syncthreads();
         }

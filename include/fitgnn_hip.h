@@ -581,7 +581,9 @@ int fitgnn_appnp_blocks_f32(const int32_t *rowptr, const int32_t *col, const flo
  * more than 16 entries is summed by a whole wavefront.  LDS: fitgnn_appnp_lds_bytes(max_rows, max_entries, slice) <=
  * fitgnn_appnp_lds_max_bytes(); max_rows / max_entries = the largest range of THIS list (a larger one is skipped by its workgroup).
  * Semantics of X, Y, K, alpha, backward as fitgnn_appnp_units_f32 (same reference lines).  Sums of a short row in CSR order; a long
- * row's in a fixed tree: results do not depend on the launch. */
+ * row's in a fixed tree: results do not depend on the launch.  A row WITHOUT entries is a row like any other (its sum is 0): for
+ * K >= 1 its result is alpha * X[row] forward and alpha * X[row] backward (alpha g_0: every later g_k of the row is 0), as the units,
+ * blocks and per-step kernels give; max_entries = 0 (a list of such rows only) is accepted. */
 int64_t fitgnn_appnp_lds_bytes(int32_t max_rows, int32_t max_entries, int32_t slice);
 int fitgnn_appnp_lds_max_bytes(void);
 int fitgnn_appnp_lds_items_per_thread(void);
