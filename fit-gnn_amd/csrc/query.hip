@@ -11,6 +11,8 @@
 // Two SAGEConv layers take it behind fitgnn_sage_query_gather_f32 (a gather plus a root term: see sage_query_gather_kernel).
 // Two GINConv layers have launches of their own, fitgnn_gin_query_hops_f32 and fitgnn_gin_query_tail_f32 (a dense product behind a
 // ReLU per one-hop row: see gin_query_hops_kernel).
+// Graph-level models (a pool over a graph's rows in front of the head) have fitgnn_gcn_graph_query_hops_f32 and
+// fitgnn_gcn_graph_query_tail_f32: a graph's layer-0 rows are formed once, in LDS (see graph_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -30,11 +32,48 @@ constexpr int kGatherWaves = 4;
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
+// One wave: columns c .. c + 3 of the sum of layer-0 row j before its bias, a = fmaf(val[e'], T[t(col[e'])][c], a) from 0 in CSR
+// order.  Tc: the lane's column in T.  The row's entries are fetched 64 at a time and broadcast by v_readlane, four table rows in flight.
+__device__ __forceinline__ float4 gcn_row(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+                                          const float *__restrict__ Tc, int64_t ldt, const int32_t *__restrict__ xrow, int j, int lane) {
+    const int n0 = __builtin_amdgcn_readfirstlane(rowptr[j]), n1 = __builtin_amdgcn_readfirstlane(rowptr[j + 1]);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int base = n0; base < n1; base += 64) {
+        const int cnt = min(64, n1 - base);
+        int my = 0, mv = 0;
+        if (lane < cnt) {
+            const int cc = col[base + lane];
+            my = xrow ? xrow[cc] : cc;
+            mv = __float_as_int(val[base + lane]);
+        }
+        for (int k = 0; k < cnt; k += 4) {
+            float4 t[4];
+            float wv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                const int idx = k + u < cnt ? k + u : k;
+                const int node = __builtin_amdgcn_readlane(my, idx);
+                wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
+                t[u] = *reinterpret_cast<const float4 *>(Tc + (int64_t)node * ldt);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k + u < cnt) {
+                    a.x = fmaf(wv[u], t[u].x, a.x);
+                    a.y = fmaf(wv[u], t[u].y, a.y);
+                    a.z = fmaf(wv[u], t[u].z, a.z);
+                    a.w = fmaf(wv[u], t[u].w, a.w);
+                }
+            }
+        }
+    }
+    return a;
+}
+
 // One workgroup per (query, 256-column slab), the slab fastest so that all of a table row's slabs are in flight together; 64 lanes x
 // float4 per slab (the columns are independent: the bits do not depend on the split).  The query's entries are dealt round-robin to
-// the four waves; a wave forms its neighbour's layer-0 row from the table -- the neighbour's entries fetched 64 at a time and broadcast by
-// v_readlane, four table rows in flight -- applies + b0 and ELU and folds the row into its partial.  Any degree is served by the
-// loops; the partials meet in LDS in wave order.
+// the four waves; a wave forms its neighbour's layer-0 row from the table (gcn_row), applies + b0 and ELU and folds the row into its
+// partial.  Any degree is served by the loops; the partials meet in LDS in wave order.
 __global__ __launch_bounds__(256) void query_gather_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                            const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
                                                            const int32_t *__restrict__ xrow, const float *__restrict__ b0,
@@ -55,37 +94,7 @@ __global__ __launch_bounds__(256) void query_gather_kernel(const int32_t *__rest
     for (int i = w; i < deg; i += kGatherWaves) {
         const int j = __builtin_amdgcn_readfirstlane(col[e0 + i]);
         const float vq = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(val[e0 + i])));
-        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[j]), n1 = __builtin_amdgcn_readfirstlane(rowptr[j + 1]);
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int base = n0; base < n1; base += 64) {
-            const int cnt = min(64, n1 - base);
-            int my = 0, mv = 0;
-            if (lane < cnt) {
-                const int cc = col[base + lane];
-                my = xrow ? xrow[cc] : cc;
-                mv = __float_as_int(val[base + lane]);
-            }
-            for (int k = 0; k < cnt; k += 4) {
-                float4 t[4];
-                float wv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
-                    const int idx = k + u < cnt ? k + u : k;
-                    const int node = __builtin_amdgcn_readlane(my, idx);
-                    wv[u] = __int_as_float(__builtin_amdgcn_readlane(mv, idx));
-                    t[u] = *reinterpret_cast<const float4 *>(Tc + (int64_t)node * ldt);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (k + u < cnt) {
-                        a.x = fmaf(wv[u], t[u].x, a.x);
-                        a.y = fmaf(wv[u], t[u].y, a.y);
-                        a.z = fmaf(wv[u], t[u].z, a.z);
-                        a.w = fmaf(wv[u], t[u].w, a.w);
-                    }
-                }
-            }
-        }
+        const float4 a = gcn_row(rowptr, col, val, Tc, ldt, xrow, j, lane);
         p.x = fmaf(vq, elu1(a.x + bias.x), p.x);
         p.y = fmaf(vq, elu1(a.y + bias.y), p.y);
         p.z = fmaf(vq, elu1(a.z + bias.z), p.z);
@@ -488,23 +497,13 @@ __device__ __forceinline__ void tail_head(const float *zs, int zld, int32_t H2, 
     }
 }
 
-// One workgroup per tile of up to 16 queries.  z = ELU(G W1^T + b1) on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4],
-// B: W1[n = l & 15][k = l >> 4], C/D: column l & 15, rows 4 (l >> 4) + r), W1 and the tile's rows of G staged through LDS in
-// k-stages of 32; the tile's z stays in LDS, the head reads it from there.
-__global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1,
-                                                         const float *__restrict__ b1, const float *__restrict__ Wl,
-                                                         const float *__restrict__ bl, int32_t H, int32_t H2, int32_t C,
-                                                         float *__restrict__ out, int64_t ldo, int32_t log_softmax) {
-    extern __shared__ float smem[];
-    const int zld = H2 + 4;
-    float *zs = smem;
-    float *Ws = zs + (size_t)kTailQ * zld;
-    float *Gs = Ws + kTailCols * kTailLd;
-    float *lg = Gs + kTailQ * kTailLd;
+// zs[r][n] = ELU(G[q0 + r] W1^T + b1) for the 16 rows of a tile (rows r >= nq are computed as zeros and never read by the callers)
+// and every column n < H2, on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4], B: W1[n = l & 15][k = l >> 4], C/D:
+// column l & 15, rows 4 (l >> 4) + r), W1 and the tile's rows of G staged through LDS in k-stages of 32.  The first barrier of the
+// first stage orders the readers of a previous tile's zs; the caller puts a barrier in front of its own reads.
+__device__ __forceinline__ void tail_tile_z(const float *__restrict__ G, int64_t ldg, int64_t q0, int nq, const float *__restrict__ W1,
+                                            const float *__restrict__ b1, int32_t H, int32_t H2, float *zs, int zld, float *Ws, float *Gs) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
-    const int q0 = blockIdx.x * kTailQ;
-    const int nq = min(kTailQ, Q - q0);
-
     for (int n0 = 0; n0 < H2; n0 += kTailCols) {
         const int ncols = min(kTailCols, H2 - n0);  // a multiple of 16
         f32x4 acc[4];
@@ -548,6 +547,24 @@ __global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict
             }
         }
     }
+}
+
+// One workgroup per tile of up to 16 queries.  z = ELU(G W1^T + b1) by tail_tile_z; the tile's z stays in LDS, the head reads it
+// from there.
+__global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1,
+                                                         const float *__restrict__ b1, const float *__restrict__ Wl,
+                                                         const float *__restrict__ bl, int32_t H, int32_t H2, int32_t C,
+                                                         float *__restrict__ out, int64_t ldo, int32_t log_softmax) {
+    extern __shared__ float smem[];
+    const int zld = H2 + 4;
+    float *zs = smem;
+    float *Ws = zs + (size_t)kTailQ * zld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *lg = Gs + kTailQ * kTailLd;
+    const int q0 = blockIdx.x * kTailQ;
+    const int nq = min(kTailQ, Q - q0);
+
+    tail_tile_z(G, ldg, q0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
     __syncthreads();
 
     tail_head(zs, zld, H2, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
@@ -857,6 +874,152 @@ __global__ __launch_bounds__(256) void gin_query_tail_kernel(const float *__rest
     tail_head(z2, z2ld, H2b, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
 }
 
+// ---- graph queries (two GCNConv layers, a pool over a graph's rows, the head) ----
+// A graph is a contiguous row range [r0, r1) of a block-diagonal view, so its layer-0 rows fit in LDS: each is formed ONCE per
+// (graph, slab) -- the per-row gather above forms row j once per entry that reaches it -- and layer 1 reads them from there.
+//   h_r   = ELU(sum_{e' in row r} val[e'] T[t(col[e'])] + b0)          r in [r0, r1)                     graph_query_hops_kernel
+//   g_r   = sum_{e in row r} val[e] h_{col[e]}                          r among the graph's pooled rows
+//   z_r   = ELU(W1 g_r + b1);  p = max_r z_r | mean_r z_r;  out = Wl p + bl  (softmax)                   graph_query_tail_kernel
+// Operation order (tests/graph_query_reference.py mirrors it):
+//   hops  phase 1: a = 0; a = fmaf(val[e'], T[t(col[e'])][c], a) over row r's entries in CSR order (gcn_row); h_r[c] = ELU(a + b0[c]);
+//         a row without entries: ELU(b0).  phase 2: g = 0; g = fmaf(val[e], h_{col[e]}[c], g) over the pooled row's entries in CSR
+//         order, ONE chain (no wave partials); a pooled row without entries gives zeros.
+//   tail  z_r[n] as query_tail_kernel's (tail_tile_z, tiles of 16 rows of the segment); the pool folds the segment's rows ascending,
+//         live rows only: max p[n] = z_first[n], then p[n] = fmaxf(p[n], z_r[n]); mean s[n] = s[n] + z_r[n] from 0, p[n] = s[n] / (float)cnt;
+//         an empty segment: p = 0.  logit[c] = (fmaf chain over h ascending of p[h] Wl[c][h], from 0) + bl[c]; softmax: m = max_c logit,
+//         e_c = expf(logit[c] - m), s = sum_c e_c ascending c from 0, out[c] = e_c / s.
+
+// One workgroup of four waves per (graph, 256-column slab), the slab fastest.  The graph's rows are dealt round-robin to the waves,
+// which form them (gcn_row, + b0, ELU) into the LDS window hs [r1 - r0][min(H, 256)]: a wave writes and later reads 64 consecutive
+// float4, every bank once.  After the barrier the graph's pooled rows are dealt round-robin to the waves; a wave fetches the row's
+// entries 64 at a time and broadcasts (window row, value) by v_readlane.
+__global__ __launch_bounds__(256) void graph_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                               const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
+                                                               const int32_t *__restrict__ xrow, const float *__restrict__ b0,
+                                                               const int64_t *__restrict__ seg, const int64_t *__restrict__ prow,
+                                                               const int64_t *__restrict__ pptr, int32_t H, int32_t max_rows,
+                                                               float *__restrict__ G, int64_t ldg, int32_t n_slabs) {
+    extern __shared__ float4 hs[];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gi = blockIdx.x / n_slabs, c0 = (blockIdx.x % n_slabs) * 256;
+    const int r0 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi]), r1 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi + 1]);
+    if (r1 - r0 > max_rows) return;  // workgroup-uniform: the window was sized for max_rows
+    const int w4 = min(H, 256) >> 2;  // float4 per window row
+    const int c = c0 + lane * 4;
+    const bool live = c < H;  // H % 4 == 0: a live lane owns four whole columns
+    const float *Tc = T + (live ? c : 0);
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (b0 && live) bias = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+    for (int r = r0 + w; r < r1; r += kGatherWaves) {
+        const float4 a = gcn_row(rowptr, col, val, Tc, ldt, xrow, r, lane);
+        if (live) hs[(r - r0) * w4 + lane] = make_float4(elu1(a.x + bias.x), elu1(a.y + bias.y), elu1(a.z + bias.z), elu1(a.w + bias.w));
+    }
+    __syncthreads();
+    const int64_t p1 = pptr[gi + 1];
+    for (int64_t j = pptr[gi] + w; j < p1; j += kGatherWaves) {
+        const int r = __builtin_amdgcn_readfirstlane((int)prow[j]);
+        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = n0; base < n1; base += 64) {
+            const int cnt = min(64, n1 - base);
+            int my = 0, mv = 0;
+            if (lane < cnt) {
+                my = col[base + lane] - r0;
+                mv = __float_as_int(val[base + lane]);
+            }
+            for (int k = 0; k < cnt; ++k) {
+                const int node = __builtin_amdgcn_readlane(my, k);
+                const float wv = __int_as_float(__builtin_amdgcn_readlane(mv, k));
+                if (live) {
+                    const float4 h = hs[node * w4 + lane];
+                    g.x = fmaf(wv, h.x, g.x);
+                    g.y = fmaf(wv, h.y, g.y);
+                    g.z = fmaf(wv, h.z, g.z);
+                    g.w = fmaf(wv, h.w, g.w);
+                }
+            }
+        }
+        if (live) *reinterpret_cast<float4 *>(G + j * ldg + c) = g;
+    }
+}
+
+__host__ __device__ constexpr size_t graph_tail_lds_floats(int H2, int C) {
+    return (size_t)kTailQ * (H2 + 4) + (size_t)kTailCols * kTailLd + (size_t)kTailQ * kTailLd + (size_t)H2 + (size_t)C;
+}
+static_assert(graph_tail_lds_floats(512, 48) * sizeof(float) <= kTailLdsMax, "the default model's graph tail must fit LDS");
+
+// One workgroup per graph: its segment of G in tiles of 16 rows through tail_tile_z; after each tile thread t folds the tile's live
+// rows into ps[n] for its columns n = t, t + 256, ... (the same thread owns a column from the first tile to the division, so ps
+// needs no barrier of its own before the head).  One thread per class then runs the head's chain over ps.
+__global__ __launch_bounds__(256) void graph_query_tail_kernel(const float *__restrict__ G, int64_t ldg, const int64_t *__restrict__ pptr,
+                                                               const float *__restrict__ W1, const float *__restrict__ b1,
+                                                               const float *__restrict__ Wl, const float *__restrict__ bl, int32_t H,
+                                                               int32_t H2, int32_t C, int32_t pool, int32_t softmax,
+                                                               float *__restrict__ out, int64_t ldo) {
+    extern __shared__ float smem[];
+    const int zld = H2 + 4;
+    float *zs = smem;
+    float *Ws = zs + (size_t)kTailQ * zld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *ps = Gs + kTailQ * kTailLd;  // 16-byte aligned: every part in front of it is a multiple of four floats
+    float *lg = ps + H2;
+    const int tid = threadIdx.x;
+    const int64_t s0 = pptr[blockIdx.x], s1 = pptr[blockIdx.x + 1];
+    for (int n = tid; n < H2; n += 256) ps[n] = 0.f;
+    for (int64_t t0 = s0; t0 < s1; t0 += kTailQ) {
+        const int nq = (int)min((int64_t)kTailQ, s1 - t0);
+        tail_tile_z(G, ldg, t0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
+        __syncthreads();
+        for (int n = tid; n < H2; n += 256) {
+            float p = ps[n];
+            int r = 0;
+            if (pool == 0 && t0 == s0) {  // the maximum starts from the segment's first row
+                p = zs[n];
+                r = 1;
+            }
+            for (; r < nq; ++r) {  // live rows only: a padded row holds ELU(b1)
+                const float z = zs[r * zld + n];
+                p = pool == 0 ? fmaxf(p, z) : p + z;
+            }
+            ps[n] = p;
+        }
+    }
+    if (pool != 0 && s1 > s0) {
+        const float cnt = (float)(s1 - s0);
+        for (int n = tid; n < H2; n += 256) ps[n] = ps[n] / cnt;
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += 256) {
+        const float *wl = Wl + (int64_t)c * H2;
+        float s = 0.f;
+        for (int h = 0; h < H2; h += 4) {
+            const float4 wv = *reinterpret_cast<const float4 *>(wl + h);
+            const float4 pv = *reinterpret_cast<const float4 *>(ps + h);
+            s = fmaf(pv.x, wv.x, s);
+            s = fmaf(pv.y, wv.y, s);
+            s = fmaf(pv.z, wv.z, s);
+            s = fmaf(pv.w, wv.w, s);
+        }
+        lg[c] = bl ? s + bl[c] : s;
+    }
+    __syncthreads();
+    if (softmax) {
+        if (tid == 0) {
+            float m = lg[0];
+            for (int c = 1; c < C; ++c) m = fmaxf(m, lg[c]);
+            float s = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float e = expf(lg[c] - m);
+                lg[c] = e;
+                s += e;
+            }
+            for (int c = 0; c < C; ++c) lg[c] = lg[c] / s;
+        }
+        __syncthreads();
+    }
+    for (int c = tid; c < C; c += 256) out[(int64_t)blockIdx.x * ldo + c] = lg[c];
+}
+
 }  // namespace
 
 extern "C" int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
@@ -979,5 +1142,53 @@ extern "C" int fitgnn_gin_query_tail_f32(const float *G, int64_t ldg, int32_t Q,
     if (const int rc = fitgnn_lds_limit_once((const void *)gin_query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
     hipLaunchKernelGGL(gin_query_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1a,
                        b1a, W1b, b1b, Wl, bl, K, H2a, H2b, C, out, ldo, log_softmax);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t fitgnn_gcn_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H) {
+    if (max_rows < 0 || H < 4) return 0;
+    return (size_t)max_rows * (size_t)std::min(H, 256) * sizeof(float);
+}
+
+extern "C" int fitgnn_gcn_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                               const int32_t *xrow, const float *b0, const int64_t *seg, const int64_t *prow,
+                                               const int64_t *pptr, int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg,
+                                               void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || max_rows < 0 || ldt < H || ldg < H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gcn_graph_query_hops_lds_bytes(max_rows, H);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // the largest graph's layer-0 rows do not fit LDS
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !seg || !prow || !pptr || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G) % 16) != 0) return FITGNN_E_ALIGN;
+    const int n_slabs = (H + 255) / 256;
+    if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)graph_query_hops_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(graph_query_hops_kernel, dim3((unsigned)(Q * n_slabs)), dim3(256), lds, (hipStream_t)stream, rowptr, col, val, T, ldt,
+                       xrow, b0, seg, prow, pptr, H, max_rows, G, ldg, n_slabs);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t fitgnn_gcn_graph_query_tail_lds_bytes(int32_t H2, int32_t C) {
+    if (H2 <= 0 || C <= 0) return 0;
+    return graph_tail_lds_floats(H2, C) * sizeof(float);
+}
+
+extern "C" int fitgnn_gcn_graph_query_tail_f32(const float *G, int64_t ldg, const int64_t *pptr, int32_t Q, const float *W1, const float *b1,
+                                               const float *Wl, const float *bl, int32_t H, int32_t H2, int32_t C, int32_t pool,
+                                               int32_t softmax, float *out, int64_t ldo, void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || H2 < 16 || (H2 % 16) != 0 || C < 1 || ldg < H || ldo < C || pool < 0 || pool > 1)
+        return FITGNN_E_BADARG;
+    if ((ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gcn_graph_query_tail_lds_bytes(H2, C);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // z of the tile and the pooled row do not fit LDS
+    if (Q == 0) return 0;
+    if (!G || !pptr || !W1 || !Wl || !out) return FITGNN_E_BADARG;
+    if ((((uintptr_t)G | (uintptr_t)W1 | (uintptr_t)Wl | (uintptr_t)out) % 16) != 0) return FITGNN_E_ALIGN;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)graph_query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(graph_query_tail_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, G, ldg, pptr, W1, b1, Wl, bl, H, H2, C,
+                       pool, softmax, out, ldo);
     return (int)hipGetLastError();
 }

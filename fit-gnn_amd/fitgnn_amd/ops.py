@@ -1209,6 +1209,60 @@ def query_supported(model):
             and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
 
 
+def gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=None, b0=None, out=None):
+    """G [P, H]: row j = the layer-1 aggregation of view row prow[j] over its graph's layer-0 rows, each formed once in LDS from
+    T = X W0^T (fitgnn_gcn_graph_query_hops_f32).  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled
+    rows, graph i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int).  The caller checks that
+    prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
+    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)
+    Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1])
+    G = out if out is not None else torch.empty((P, H), dtype=torch.float32, device=T.device)
+    if P == 0:
+        return G
+    _lib.check(_lib.lib().fitgnn_gcn_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                          _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q, H,
+                                                          int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
+               "fitgnn_gcn_graph_query_hops_f32")
+    return G
+
+
+def gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool="max", softmax=False, out=None):
+    """[Q, C] = Wl pool_i(ELU(W1 G[r] + b1): r in pptr[i] .. pptr[i + 1]) + bl per graph, pool "max" or "mean", a softmax on request
+    (fitgnn_gcn_graph_query_tail_f32).  W1 [H2, H], Wl [C, H2] contiguous; pptr int64 [Q + 1]."""
+    _lib.require_cuda(G, pptr, W1, b1, Wl, bl)
+    Q, H = int(pptr.numel()) - 1, int(G.shape[1])
+    H2, C = int(W1.shape[0]), int(Wl.shape[0])
+    y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
+    _lib.check(_lib.lib().fitgnn_gcn_graph_query_tail_f32(_lib.dptr(G), G.stride(0), _lib.dptr(pptr), Q, _lib.dptr(W1), _lib.dptr(b1),
+                                                          _lib.dptr(Wl), _lib.dptr(bl), H, H2, C, {"max": 0, "mean": 1}[pool],
+                                                          1 if softmax else 0, _lib.dptr(y), y.stride(0), _lib.stream_ptr(G.device)),
+               "fitgnn_gcn_graph_query_tail_f32")
+    return y
+
+
+def graph_query_max_rows(H):
+    """The largest graph (rows) whose layer-0 rows fitgnn_gcn_graph_query_hops_f32 holds in LDS at hidden size H."""
+    per_row = int(_lib.lib().fitgnn_gcn_graph_query_hops_lds_bytes(1, int(H)))
+    return (160 * 1024) // per_row if per_row > 0 else 0
+
+
+def graph_query_supported(model):
+    """The two graph-query kernels answer for `model`: query_supported's conditions (exactly two GCNConv layers, hidden sizes
+    multiples of 16, contiguous float32 parameters on the GPU) with the graph tail's LDS bound in place of the node tail's."""
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GCNConv for c in convs):
+        return False
+    W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
+    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias]
+    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        return False
+    H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
+    return (H % 16 == 0 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+            and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+
+
 def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=None, b0=None, slope0=0.2, slope1=0.2, out=None):
     """G [Q, H]: row i = the layer-1 attention aggregation (before its Linear) of union row rows[i] over layer-0 GAT rows made from
     T = X W0^T on the fly (fitgnn_gat_query_gather_f32).  a_src0 / a_dst0: the layer-0 score dots per TABLE row; u_src / u_dst [H]:

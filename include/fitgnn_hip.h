@@ -652,6 +652,43 @@ size_t fitgnn_gcn_query_tail_lds_bytes(int32_t H2, int32_t C);
 int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl, const float *bl,
                               int32_t H, int32_t H2, int32_t C, float *out, int64_t ldo, int32_t log_softmax, void *stream);
 
+/* Graph-level queries (inference.py:288-538 of the reference: graph_cls / graph_reg, the model on ONE graph of the set): two
+ * GCNConv layers, a pool over the graph's rows, the head -- two launches for any number of graphs.  Both take the GCN-normalised CSR
+ * (rowptr, col, val) of a whole view, all rows of all graphs, block-diagonal per graph.
+ *
+ * The first: G[j][:] = g_{prow[j]} for every pooled row of every queried graph, over layer-0 rows made from T = X W0^T [n_table x H]
+ * (row stride ldt):
+ *   h_r = ELU(sum_{e' in row r} val[e'] * T[xrow ? xrow[col[e']] : col[e']] + b0)   for EVERY row r of graph i's range [seg[i][0], seg[i][1]),
+ *   g_r = sum_{e in row r} val[e] * h_{col[e]}                                      for r = prow[j], pptr[i] <= j < pptr[i + 1].
+ * One workgroup of four waves per graph and 256-column slab: the graph's rows are dealt round-robin to the waves, which form each
+ * h_r ONCE into LDS (the per-row gather above forms it once per entry that reaches it); after one barrier the graph's pooled rows are
+ * dealt round-robin to the waves, each a single fmaf chain over the row's entries in CSR order.  No atomics: two launches give the
+ * same bits (operation order: csrc/query.hip).  A row without entries gives h_r = ELU(b0); a pooled row without entries zeros.  seg
+ * (int64 [Q][2]) may repeat graphs and needs no order; prow (int64, rows of view) lists graph i's pooled rows inside its range;
+ * pptr is int64 [Q + 1].  The kernel cannot check that prow and col stay inside the graph's range: the caller does.  max_rows: the
+ * host-known largest seg[i][1] - seg[i][0] (a graph with more rows is skipped: its rows of G are not written).  Dynamic LDS:
+ * fitgnn_gcn_graph_query_hops_lds_bytes(max_rows, H) = max_rows * min(H, 256) * 4 bytes.  xrow, b0 may be NULL.  Writes
+ * G[0..pptr[Q]) x [0..H) only.  Requires H >= 4, H % 4 == 0 (H is not limited), ldt, ldg >= H and the LDS at most 160 KiB
+ * (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_gcn_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H);
+int fitgnn_gcn_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                    const int32_t *xrow, const float *b0, const int64_t *seg, const int64_t *prow, const int64_t *pptr,
+                                    int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg, void *stream);
+
+/* The second: out[i][:] = Wl pool(ELU(W1 G[r] + b1) : pptr[i] <= r < pptr[i + 1]) + bl for i < Q (network.py:87-95, :158-166), pool
+ * the maximum (pool == 0) or the mean (pool == 1) per column, followed by a max-subtracted softmax per row when softmax != 0.  One
+ * workgroup per graph: its segment of G in tiles of 16 rows through fitgnn_gcn_query_tail_f32's exact-fp32 MFMA product (z_r is
+ * bit-equal to that kernel's); after each tile the live rows alone are folded into the pooled row in ascending order (maximum: from
+ * the segment's first row; mean: a running sum from 0 divided once by the count; an empty segment pools to zeros), then the head in
+ * ascending h and out[c] = expf(logit[c] - m) / sum.  W1 [H2 x H], Wl [C x H2] contiguous; b1, bl may be NULL; pptr is the first
+ * launch's.  Requires H % 4 == 0, H2 % 16 == 0, C >= 1, ldg >= H, ldo >= C, pool in {0, 1} and
+ * fitgnn_gcn_graph_query_tail_lds_bytes(H2, C) <= 160 KiB (FITGNN_E_BADARG); ldg a multiple of 4 and G, W1, Wl, out 16-byte aligned
+ * (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_gcn_graph_query_tail_lds_bytes(int32_t H2, int32_t C);
+int fitgnn_gcn_graph_query_tail_f32(const float *G, int64_t ldg, const int64_t *pptr, int32_t Q, const float *W1, const float *b1,
+                                    const float *Wl, const float *bl, int32_t H, int32_t H2, int32_t C, int32_t pool, int32_t softmax,
+                                    float *out, int64_t ldo, void *stream);
+
 /* Two GINConv layers whose nn is Linear, ReLU, Linear, ReLU (network.py:19-21) have two launches of their own.  The first:
  * G[i][0:Hb) = s_q for q = rows[i], over T = X W0a^T [n_table x Ha] (row stride ldt):
  *   a_r = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a),   h_r = ReLU(W0b a_r + b0b),

@@ -1,0 +1,315 @@
+"""GPU tier: fitgnn_amd.serve.GraphQueryEngine -- graph ids in, predictions out -- against a float64 forward built from the oracle's
+conv_stack / mean_pool on the whole view and against the model's own forward on GraphSet.batch_ids, on sets of a dozen synthetic
+graphs; the per-row gather for graphs beyond the window; the model's own forward for the models the two kernels do not take; the
+torch.ops bindings; inference.py --query_engine on the graph-level tasks."""
+import argparse
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_query import rel
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N_GRAPHS = 12
+IDS = [7, 2, 11, 2, 0, 5, 7, 9]    # unsorted, with repeats
+
+
+@pytest.fixture(scope="module")
+def mods():
+    assert torch.cuda.is_available()
+    from fitgnn_amd import graph_data, network, ops, serve
+    from oracle import gnn_oracle as gorc
+    return graph_data, network, ops, serve, gorc
+
+
+_SETS = {}
+
+
+def _gset(graph_data, kind, extra_node=False, cluster_node=False):
+    """A GraphSet of N_GRAPHS graphs, built once per layout: "mol" (synthetic_molecules: 11 features, 10 to 28 nodes), "cls"
+    (synthetic_graph_classes: 3 features) or "small" (synthetic_graph_classes with 4 to 18 nodes, most of them 4 or 5)."""
+    key = (kind, extra_node, cluster_node)
+    if key not in _SETS:
+        mol = (graph_data.synthetic_molecules(N_GRAPHS, seed=3) if kind == "mol" else
+               graph_data.synthetic_graph_classes(N_GRAPHS, seed=3, mean_nodes=6 if kind == "small" else 19))
+        _SETS[key] = graph_data.GraphSet(mol, ratio=0.5, extra_node=extra_node, cluster_node=cluster_node, device="cuda")
+    return _SETS[key]
+
+
+def _model(network, cls, F, hidden, layer="GCNConv", layers=2, seed=0):
+    args = argparse.Namespace(num_layers1=layers, layer_name=layer, num_features=F, hidden=hidden, num_classes=5)
+    torch.manual_seed(seed)
+    m = getattr(network, cls)(args).cuda()
+    with torch.no_grad():
+        for name, p in m.named_parameters():
+            if name.endswith("bias"):
+                p.normal_(0, 0.3)   # the default zero biases would hide a dropped bias
+    return m.eval()
+
+
+def _view(gset, view):
+    """(x, row pointer per graph, edge list, pooled-row mask) of a view, read from the set itself."""
+    if view == "gs":
+        return gset.gs_x, np.asarray(gset.gs_ptr), gset.gs_edge_index, gset.gs_mask
+    if view == "gc":
+        return gset.gc_x, np.asarray(gset.cluster_ptr), gset.gc_edge_index, None
+    return gset.x, np.asarray(gset.node_ptr), gset.edge_index, None
+
+
+def _oracle(gorc, model, gset, view, ids):
+    """float64: the conv stack on the whole (block-diagonal) view, per graph the pool over its pooled rows, the head, the softmax."""
+    sd = {k: v.detach().cpu().double() for k, v in model.state_dict().items()}
+    x, ptr, ei, mask = _view(gset, view)
+    z = gorc.conv_stack(sd, x.cpu().double(), ei.cpu(), 2)
+    classify = type(model).__name__.startswith("Classify")
+    keep = torch.ones(z.shape[0], dtype=torch.bool) if mask is None else mask.cpu()
+    out = []
+    for g in ids:
+        rows = torch.arange(int(ptr[g]), int(ptr[g + 1]))
+        zr = z[rows[keep[rows]]]
+        p = zr.max(0).values if classify else gorc.mean_pool(zr, torch.zeros(zr.shape[0], dtype=torch.long), 1)[0]
+        y = p @ sd["lt1.weight"].t() + sd["lt1.bias"]
+        out.append(torch.softmax(y, 0) if classify else y)
+    return torch.stack(out)
+
+
+def _forward(model, gset, view, ids):
+    """The model's own forward on batch_ids(unique ids), spread back over ids."""
+    from fitgnn_amd.train import _cat_pieces
+    uniq, inv = np.unique(np.asarray(ids), return_inverse=True)
+    piece = gset.batch_ids(uniq.tolist(), view)
+    with torch.no_grad():
+        if type(model).__name__.endswith("_gs"):
+            b = _cat_pieces([piece], "gs", types)
+            out = model(b, b["graph_of_masked"])
+        else:
+            out = model(_cat_pieces([piece], "gc", types)["gc"])
+    return out.float().reshape(len(uniq), -1)[torch.from_numpy(inv).to(out.device)]
+
+
+def _check(mods, model, gset, view, ids=IDS, **kw):
+    graph_data, network, ops, serve, gorc = mods
+    eng = serve.GraphQueryEngine(model, gset, view=view, **kw)
+    assert eng.fused is True and ops.graph_query_supported(model)
+    out = eng.predict(ids)
+    C = model.lt1.weight.shape[0]
+    assert out.shape == (len(ids), C) and out.dtype == torch.float32
+    v = eng.view
+    assert rel(out.cpu().double(), _oracle(gorc, model, gset, v, ids)) <= 1e-4
+    assert rel(out.cpu().double(), _forward(model, gset, v, ids).cpu().double()) <= 1e-4
+    assert torch.equal(out[1], out[3]) and torch.equal(out[0], out[6])      # the repeated graphs
+    assert torch.equal(eng.predict(torch.tensor(ids, device="cuda")), out)  # host and device ids: equal bits
+    assert torch.equal(eng.predict(np.asarray(ids)), out)
+    n_rows = int(_view(gset, v)[1][-1])
+    assert eng.table_bytes == n_rows * model.conv[0].lin.weight.shape[0] * 4
+    return eng, out
+
+
+@pytest.mark.parametrize("hidden", [64, 512])
+@pytest.mark.parametrize("cls,kind,view", [("Classify_graph_gs", "cls", "gs"), ("Classify_graph_gc", "cls", "gc"),
+                                           ("Regress_graph_gs", "mol", "gs"), ("Regress_graph_gc", "mol", "gc")], ids=str)
+def test_every_model_class_on_its_default_view(mods, cls, kind, view, hidden):
+    graph_data, network = mods[:2]
+    gset = _gset(graph_data, kind)
+    model = _model(network, cls, gset.x.shape[1], hidden)
+    eng, out = _check(mods, model, gset, None)
+    assert eng.view == view
+    if cls.startswith("Classify"):
+        assert float((out.sum(1) - 1).abs().max()) <= 1e-5 and out.shape[1] == 5
+    else:
+        assert out.shape[1] == 1
+
+
+@pytest.mark.parametrize("hidden", [64, 512])
+def test_the_baseline_on_the_uncoarsened_graphs(mods, hidden):
+    graph_data, network = mods[:2]
+    gset = _gset(graph_data, "cls")
+    _check(mods, _model(network, "Classify_graph_gc", gset.x.shape[1], hidden), gset, "orig")
+    gm = _gset(graph_data, "mol")
+    _check(mods, _model(network, "Regress_graph_gc", gm.x.shape[1], hidden), gm, "orig")
+
+
+@pytest.mark.parametrize("extra_node,cluster_node", [(False, False), (True, False), (False, True)], ids=["plain", "extra", "cluster"])
+def test_the_subgraph_view_in_every_layout(mods, extra_node, cluster_node):
+    graph_data, network = mods[:2]
+    gset = _gset(graph_data, "mol", extra_node=extra_node, cluster_node=cluster_node)
+    if extra_node or cluster_node:
+        assert not bool(gset.gs_mask.all()), "every row pooled: the layout adds no rows"
+    _check(mods, _model(network, "Regress_graph_gs", gset.x.shape[1], 64), gset, "gs")
+    _check(mods, _model(network, "Classify_graph_gs", gset.x.shape[1], 64), gset, "gs")
+
+
+def test_max_window_rows_4_splits_a_call_between_the_window_and_the_gather(mods):
+    """Uncoarsened graphs of 4 to 18 nodes: max_window_rows=4 sends the graphs of four rows through the window and the others
+    through the per-row gather, in one call, into one G in front of one tail."""
+    graph_data, network, ops, serve, gorc = mods
+    gset = _gset(graph_data, "small")
+    n_rows = np.diff(np.asarray(gset.node_ptr))
+    ids = list(range(N_GRAPHS))[::-1] + [3, 0]
+    fits = torch.from_numpy(n_rows[ids] <= 4)
+    assert bool(fits.any()) and not bool(fits.all()), n_rows
+    for cls in ("Classify_graph_gc", "Regress_graph_gc"):
+        model = _model(network, cls, gset.x.shape[1], 64)
+        out = serve.GraphQueryEngine(model, gset, view="orig", max_window_rows=4).predict(ids)
+        assert rel(out.cpu().double(), _oracle(gorc, model, gset, "orig", ids)) <= 1e-4
+        assert rel(out.cpu().double(), _forward(model, gset, "orig", ids).cpu().double()) <= 1e-4
+        whole = serve.GraphQueryEngine(model, gset, view="orig").predict(ids)     # every graph in the window
+        assert torch.equal(out[fits], whole[fits])                                # the window's graphs: the same arithmetic, the same bits
+        assert rel(out.cpu().double(), whole.cpu().double()) <= 1e-4
+    # the subgraph view of the same set: every graph has more than four rows there, all of them take the gather
+    model = _model(network, "Classify_graph_gs", gset.x.shape[1], 64)
+    out = serve.GraphQueryEngine(model, gset, max_window_rows=4).predict(ids)
+    assert rel(out.cpu().double(), _oracle(gorc, model, gset, "gs", ids)) <= 1e-4
+
+
+def test_weight_update_is_picked_up(mods):
+    graph_data, network, ops, serve, gorc = mods
+    gset = _gset(graph_data, "mol")
+    model = _model(network, "Regress_graph_gs", gset.x.shape[1], 64)
+    eng = serve.GraphQueryEngine(model, gset)
+    before = eng.predict(IDS).clone()
+    with torch.no_grad():
+        model.conv[0].lin.weight.mul_(0.5).add_(0.01)     # in place: same storage, new version
+        model.lt1.bias.add_(0.25)
+    after = eng.predict(IDS)
+    assert rel(after.cpu().double(), _oracle(gorc, model, gset, "gs", IDS)) <= 1e-4
+    assert not torch.allclose(after, before, atol=1e-3)
+    assert torch.equal(eng.refresh().predict(IDS), after)
+
+
+@pytest.mark.parametrize("cls,layer,layers,hidden", [("Classify_graph_gs", "GATConv", 2, 64), ("Regress_graph_gc", "GCNConv", 1, 64),
+                                                     ("Regress_graph_gs", "GCNConv", 2, 40)], ids=str)
+def test_other_models_take_their_own_forward(mods, cls, layer, layers, hidden):
+    graph_data, network, ops, serve, gorc = mods
+    gset = _gset(graph_data, "mol")
+    model = _model(network, cls, gset.x.shape[1], hidden, layer=layer, layers=layers)
+    eng = serve.GraphQueryEngine(model, gset)
+    assert eng.fused is False and eng.table_bytes == 0 and not ops.graph_query_supported(model)
+    out = eng.predict(IDS)
+    assert out.shape == (len(IDS), model.lt1.weight.shape[0])
+    assert rel(out.cpu().double(), _forward(model, gset, eng.view, IDS).cpu().double()) <= 1e-4
+    if layer == "GCNConv" and layers == 2:   # hidden 40: not a multiple of 16, but the oracle still applies
+        assert rel(out.cpu().double(), _oracle(gorc, model, gset, eng.view, IDS)) <= 1e-4
+
+
+def test_refusals(mods):
+    graph_data, network, ops, serve, gorc = mods
+    gset = _gset(graph_data, "mol")
+    model = _model(network, "Regress_graph_gs", gset.x.shape[1], 64)
+    eng = serve.GraphQueryEngine(model, gset)
+    with pytest.raises(ValueError, match=r"graph 12\b"):
+        eng.predict([3, 12, 13])
+    with pytest.raises(ValueError, match=r"graph -1\b"):
+        eng.predict(torch.tensor([3, -1], device="cuda"))
+    assert eng.predict([]).shape == (0, 1)
+    with pytest.raises(ValueError, match="view"):
+        serve.GraphQueryEngine(model, gset, view="union")
+    with pytest.raises(ValueError):
+        serve.GraphQueryEngine(_model(network, "Regress_graph_gc", gset.x.shape[1], 64), gset, view="gs")
+    with pytest.raises(TypeError):
+        serve.GraphQueryEngine(_model(network, "Regress_node", gset.x.shape[1], 64), gset)
+    # a graph without pooled rows: its mask cleared on a copy of the set's attributes
+    import copy
+    bare = copy.copy(gset)
+    bare.gs_mask = gset.gs_mask.clone()
+    bare.gs_mask[int(gset.gs_ptr[4]):int(gset.gs_ptr[5])] = False
+    be = serve.GraphQueryEngine(model, bare)
+    assert be.predict([3, 5]).shape == (2, 1)
+    with pytest.raises(ValueError, match=r"graph 4\b.*no pooled rows"):
+        be.predict([3, 4, 5])
+    model.train()
+    with pytest.raises(RuntimeError):
+        eng.predict([3])
+    model.eval()
+
+
+def test_torch_ops_hold_the_two_launchers(mods):
+    graph_data, network, ops, serve, gorc = mods
+    from fitgnn_amd import torch_ops  # noqa: F401  (registers torch.ops.fitgnn)
+    gset = _gset(graph_data, "cls", extra_node=True)
+    model = _model(network, "Classify_graph_gs", gset.x.shape[1], 64)
+    eng = serve.GraphQueryEngine(model, gset)
+    f, T = eng.graph.f, eng._table()
+    ids = np.asarray(IDS)
+    seg = torch.from_numpy(np.stack([eng._ptr[ids], eng._ptr[ids + 1]], 1)).cuda()
+    cnt = torch.from_numpy(eng._pp[ids + 1] - eng._pp[ids]).cuda()
+    pptr = torch.cat([cnt.new_zeros(1), torch.cumsum(cnt, 0)])
+    prow = torch.cat([eng._prow[int(eng._pp[g]):int(eng._pp[g + 1])] for g in IDS])
+    max_rows = int((seg[:, 1] - seg[:, 0]).max())
+    b0 = model.conv[0].bias
+    G = torch.ops.fitgnn.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, max_rows, None, b0)
+    assert G.shape == (prow.numel(), 64)
+    assert torch.equal(G, ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, max_rows, b0=b0))
+    W1, b1, Wl, bl = model.conv[1].lin.weight, model.conv[1].bias, model.lt1.weight, model.lt1.bias
+    y = torch.ops.fitgnn.gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, 0, True)
+    assert torch.equal(y, ops.gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool="max", softmax=True)) and torch.equal(y, eng.predict(IDS))
+    assert torch.equal(torch.ops.fitgnn.gcn_graph_query_tail(G, pptr, W1, None, Wl, None, 1, False),
+                       ops.gcn_graph_query_tail(G, pptr, W1, None, Wl, None, pool="mean"))
+    meta = lambda t: t.to("meta")   # noqa: E731
+    m = torch.ops.fitgnn.gcn_graph_query_hops(meta(f.rowptr), meta(f.col), meta(f.val), meta(T), meta(seg), meta(prow), meta(pptr), max_rows,
+                                              None, None)
+    assert m.shape == G.shape
+    assert torch.ops.fitgnn.gcn_graph_query_tail(m, meta(pptr), meta(W1), None, meta(Wl), None, 0, True).shape == y.shape
+
+
+def _inference_pair(tmp_path, task_csv, train, infer, line):
+    """Train a checkpoint with main.py, then inference.py with and without --query_engine, each a process of its own (as a user
+    starts it; see tests/test_gpu_query.py for why).  Returns the two printed lines starting with `line` and the CSV's rows."""
+    import subprocess
+    import sys
+
+    import main as cli
+    cli.main(train)
+    inf = [sys.executable, os.path.join(ROOT, "fit-gnn_amd", "inference.py")] + infer
+    outs = []
+    for extra in ([], ["--query_engine"]):
+        r = subprocess.run(inf + extra, cwd=tmp_path, check=True, timeout=300, stdout=subprocess.PIPE, text=True)
+        outs.append(r.stdout)
+    shown = [ln for o in outs for ln in o.splitlines() if ln.startswith(line)]
+    rows = open(os.path.join("inference_results", task_csv)).read().strip().split("\n")
+    return shown, rows
+
+
+def _same_csv_rows(rows, n_models):
+    assert len(rows) == 1 + 2 * n_models and rows[0].startswith("dataset,baseline,experiment,exp_setup")
+    head = rows[0].split(",")
+    plain, engine = rows[1:1 + n_models], rows[1 + n_models:]
+    for a, b in zip(plain, engine):
+        a, b = a.split(","), b.split(",")
+        assert len(a) == len(b) == len(head)
+        la, lb = float(a[head.index("avg_loss")]), float(b[head.index("avg_loss")])
+        assert abs(la - lb) <= 1e-4 * abs(la), (la, lb)
+        assert a[:head.index("avg_inf_time")] == b[:head.index("avg_inf_time")] and a[-1] == b[-1]    # the accuracy column too
+
+
+def test_inference_cli_graph_regression_with_and_without_the_engine(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    common = ["--dataset", "synthetic-qm9", "--n_graphs", "200", "--hidden", "64", "--seed", "0", "--extra_node"]
+    shown, rows = _inference_pair(
+        tmp_path, "graph_reg.csv",
+        common + ["--train_fitgnn", "--batch_size", "64", "--lr", "0.002", "--property", "0", "--epochs1", "3", "--epochs2", "3", "--output_dir", "q",
+                  "--exp_setup", "Gs_train_2_Gs_infer"],
+        common + ["--num_test_samples", "12", "--property", "0", "--exp_setup", "Gs_train_2_Gs_infer", "--path_gs", "save/graph_reg/q/"],
+        "L1 loss:")
+    assert len(shown) == 2
+    la, lb = (float(s.split(":")[1]) for s in shown)
+    assert abs(la - lb) <= 1e-4 * abs(la), shown
+    _same_csv_rows(rows, 1)
+
+
+def test_inference_cli_graph_classification_with_and_without_the_engine(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    common = ["--dataset", "synthetic-proteins", "--n_graphs", "200", "--hidden", "64", "--seed", "0"]
+    shown, rows = _inference_pair(
+        tmp_path, "graph_cls.csv",
+        common + ["--train_fitgnn", "--batch_size", "50", "--lr", "0.005", "--epochs1", "3", "--epochs2", "3", "--output_dir", "p",
+                  "--exp_setup", "Gc_train_2_Gc_infer"],
+        common + ["--num_test_samples", "12", "--exp_setup", "Gc_train_2_Gc_infer", "--path_gc", "save/graph_cls/p/", "--model_name_gc", "model.pt"],
+        "Accuracy:")
+    assert len(shown) == 2 and shown[0] == shown[1], shown
+    _same_csv_rows(rows, 1)

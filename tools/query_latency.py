@@ -21,7 +21,22 @@ Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>
                          table rows, 12 bytes of CSR per entry, 4 H bytes written and ceil((deg(q) + 1) / 16) passes over the 4 H H bytes of
                          W0b per query, which come from L2: gather_bytes counts them, so its rate is not an HBM rate) over its HIP-event time, next to
                          fitgnn_stream_copy_f32's rate in the same process.
-The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded)."""
+The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded).
+
+    python tools/query_latency.py --task graph_reg | graph_cls [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512] [--samples 256]
+                                  [--rounds 5] [--batch 1024] [--out FILE]
+
+--task graph_reg / graph_cls: one GRAPH query through fitgnn_amd.serve.GraphQueryEngine (fitgnn_gcn_graph_query_hops_f32 and
+fitgnn_gcn_graph_query_tail_f32) against the per-graph forward inference.py times without --query_engine, on a GraphSet of
+graph_data.synthetic_molecules (graph_reg: Regress_graph_gs / _gc) or synthetic_graph_classes (graph_cls: Classify_graph_gs / _gc),
+extra-node layout.  Writes profiles/query_latency_<task>_<view>.json (or --out):
+  (a) engine_single      predict([g]) per sampled graph, bracketed as above;
+  (b) graph_forward      the model on the graph cut out of the set (gset.batch(g, g + 1, view), its CSR and pool index pre-built),
+                         measured twice per graph around the engine's turn, after one untimed pass;
+  (c) engine_batch       predict(ids) at Q = --batch (ids drawn with repeats) against the same graphs one forward each (the loop (b)
+                         runs) and against ONE forward of the model on gset.batch_ids(the unique ids) pre-built;
+  table_row_reads        counted, not timed: sum over the pooled rows r of sum_{c in row r} deg(c) (the per-row gather on every pooled
+                         row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio."""
 import argparse
 import json
 import os
@@ -50,7 +65,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--task", default="node", choices=["node", "graph_reg", "graph_cls"])
+    ap.add_argument("--n_graphs", type=int, default=2000)
+    ap.add_argument("--view", default="gs", choices=["gs", "gc", "orig"])
     a = ap.parse_args()
+    if a.task != "node":
+        return graph_main(a)
 
     import time
 
@@ -159,7 +179,7 @@ def main():
         torch.cuda.synchronize()
         t_gather = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e-3
         deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
-        csum = torch.zeros(deg.numel() + 1, dtype=torch.int64, device=dev)
+        csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
         csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)     # prefix sums of deg(col[e]) over the entries
         rp = f.rowptr.long()
         table_rows = int((csum[rp[qrows + 1]] - csum[rp[qrows]]).sum())
@@ -200,6 +220,123 @@ def main():
                                  gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
                                  stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
     out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_' + a.layer if gat or sage or gin else ''}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+def graph_main(a):
+    import time
+    import types
+
+    import numpy as np
+    import torch
+
+    from fitgnn_amd import graph_data, network, ops, serve
+    from fitgnn_amd.train import _cat_pieces
+
+    assert torch.cuda.is_available(), "query_latency.py measures on the GPU only"
+    dev = torch.device("cuda", 0)
+    reg = a.task == "graph_reg"
+    mol = graph_data.synthetic_molecules(a.n_graphs, seed=0) if reg else graph_data.synthetic_graph_classes(a.n_graphs, seed=0)
+    gset = graph_data.GraphSet(mol, ratio=0.5, extra_node=True, device=dev)
+    gs = a.view == "gs"
+    cls = ("Regress_graph_" if reg else "Classify_graph_") + ("gs" if gs else "gc")
+    C = 1 if reg else int(mol["y"].max()) + 1
+    margs = argparse.Namespace(num_layers1=2, layer_name="GCNConv", num_features=int(gset.x.shape[1]), hidden=a.hidden, num_classes=C)
+    torch.manual_seed(2)
+    model = getattr(network, cls)(margs).to(dev).eval()
+    engine = serve.GraphQueryEngine(model, gset, view=a.view)
+    assert engine.fused and ops.graph_query_supported(model)
+    t0 = time.time()
+    engine.refresh()
+    torch.cuda.synchronize()
+    t_table = time.time() - t0
+
+    rng = np.random.default_rng(0)
+    graphs = rng.permutation(gset.n_graphs)[: a.samples].tolist()
+    kind = "gs" if gs else "gc"   # (how _cat_pieces shapes the batch: the "orig" view is a *_gc model's input too)
+    cache = {g: _cat_pieces([gset.batch(g, g + 1, a.view)], kind, types) for g in graphs}   # inference.py's batch, built outside the timed call
+
+    def call(b):
+        return model(b, b["graph_of_masked"]) if gs else model(b["gc"])
+
+    def engine_once(g):
+        torch.cuda.synchronize(dev)
+        t = time.time()
+        out = engine.predict([g])
+        torch.cuda.synchronize(dev)
+        return out, time.time() - t
+
+    def forward_once(g):
+        torch.cuda.synchronize(dev)
+        t = time.time()
+        out = call(cache[g])
+        torch.cuda.synchronize(dev)
+        return out, time.time() - t
+
+    worst = 0.0
+    with torch.no_grad():
+        for g in graphs:   # untimed pass: every shape warmed, answers compared
+            oa, ob = engine_once(g)[0], forward_once(g)[0].reshape(1, -1)
+            worst = max(worst, float((oa - ob).abs().max() / ob.abs().max().clamp(min=1e-20)))
+        ta, tb1, tb2, per_round = [], [], [], []
+        for _ in range(a.rounds):
+            ra, r1_, r2_ = [], [], []
+            for g in graphs:
+                r1_.append(forward_once(g)[1])
+                ra.append(engine_once(g)[1])
+                r2_.append(forward_once(g)[1])
+            per_round.append(dict(engine_median_us=round(float(np.median(ra)) * 1e6, 2), forward_first_median_us=round(float(np.median(r1_)) * 1e6, 2),
+                                  forward_second_median_us=round(float(np.median(r2_)) * 1e6, 2)))
+            ta += ra; tb1 += r1_; tb2 += r2_
+
+        # (c) a batch of graph queries
+        ids = rng.integers(0, gset.n_graphs, size=a.batch)
+        ids_d = torch.from_numpy(ids).to(dev)
+        uniq = np.unique(ids)
+        whole = _cat_pieces([gset.batch_ids(uniq.tolist(), a.view)], kind, types)
+        reps = 20
+
+        def timed(fn):
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            t = time.time()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.time() - t) / reps
+
+        t_batch = timed(lambda: engine.predict(ids_d))
+        t_whole = timed(lambda: call(whole))
+
+    # counted: table rows read by the per-row gather on every pooled row against every layer-0 row formed once
+    f = engine.graph.f
+    deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
+    csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
+    csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)
+    rp = f.rowptr.long()
+    prow = engine._prow
+    per_row = int((csum[rp[prow + 1]] - csum[rp[prow]]).sum())
+    once = int(deg.sum())
+
+    sa, s1, s2 = _stats(ta), _stats(tb1), _stats(tb2)
+    base = min(s1["median_us"], s2["median_us"])
+    spread = abs(s1["median_us"] - s2["median_us"])
+    res = dict(task=a.task, view=a.view, model=cls, hidden=a.hidden, classes=C, graphs=int(gset.n_graphs), view_rows=int(engine.n_rows),
+               nnz=int(f.col.numel()), pooled_rows=int(prow.numel()), samples=len(graphs), rounds=a.rounds, device=torch.cuda.get_device_name(0),
+               table=dict(rows=int(engine.n_rows), bytes=engine.table_bytes, build_s=round(t_table, 4)),
+               engine_single=sa, graph_forward_first=s1, graph_forward_second=s2, per_round=per_round,
+               graph_forward_spread_us=round(spread, 2), engine_below_forward_by_us=round(base - sa["median_us"], 2),
+               engine_faster_beyond_spread=bool(base - sa["median_us"] > spread), max_rel_diff_engine_vs_forward=worst,
+               engine_batch=dict(Q=a.batch, unique_graphs=int(len(uniq)), seconds=round(t_batch, 6), graphs_per_s=round(a.batch / t_batch, 1),
+                                 one_forward_per_graph_s=round(a.batch * base * 1e-6, 6),
+                                 one_forward_on_the_unique_graphs_s=round(t_whole, 6)),
+               table_row_reads=dict(per_row_gather=per_row, each_row_once=once, ratio=round(per_row / max(once, 1), 3)))
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
