@@ -12,7 +12,9 @@
 // Two GINConv layers have launches of their own, fitgnn_gin_query_hops_f32 and fitgnn_gin_query_tail_f32 (a dense product behind a
 // ReLU per one-hop row: see gin_query_hops_kernel).
 // Graph-level models (a pool over a graph's rows in front of the head) have fitgnn_gcn_graph_query_hops_f32 and
-// fitgnn_gcn_graph_query_tail_f32: a graph's layer-0 rows are formed once, in LDS (see graph_query_hops_kernel).
+// fitgnn_gcn_graph_query_tail_f32: a graph's layer-0 rows are formed once, in LDS (see graph_query_hops_kernel).  Two GINConv layers
+// have fitgnn_gin_graph_query_hops_f32 and fitgnn_gin_graph_query_tail_f32: the dense product behind layer 0's ReLU runs once per
+// row of the graph (see gin_graph_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -497,10 +499,11 @@ __device__ __forceinline__ void tail_head(const float *zs, int zld, int32_t H2, 
     }
 }
 
-// zs[r][n] = ELU(G[q0 + r] W1^T + b1) for the 16 rows of a tile (rows r >= nq are computed as zeros and never read by the callers)
-// and every column n < H2, on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4], B: W1[n = l & 15][k = l >> 4], C/D:
+// zs[r][n] = act(G[q0 + r] W1^T + b1), act = ELU or (kRelu) ReLU, for the 16 rows of a tile (rows r >= nq are computed as zeros and
+// never read by the callers) and every column n < H2, on v_mfma_f32_16x16x4_f32 (A: lane l holds G[l & 15][k = l >> 4], B: W1[n = l & 15][k = l >> 4], C/D:
 // column l & 15, rows 4 (l >> 4) + r), W1 and the tile's rows of G staged through LDS in k-stages of 32.  The first barrier of the
 // first stage orders the readers of a previous tile's zs; the caller puts a barrier in front of its own reads.
+template <bool kRelu>
 __device__ __forceinline__ void tail_tile_z(const float *__restrict__ G, int64_t ldg, int64_t q0, int nq, const float *__restrict__ W1,
                                             const float *__restrict__ b1, int32_t H, int32_t H2, float *zs, int zld, float *Ws, float *Gs) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
@@ -543,7 +546,7 @@ __device__ __forceinline__ void tail_tile_z(const float *__restrict__ G, int64_t
                 const int n = n0 + nb + r16;
                 const float bias = b1 ? b1[n] : 0.f;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) zs[(kq * 4 + r) * zld + n] = elu1(acc[u][r] + bias);
+                for (int r = 0; r < 4; ++r) zs[(kq * 4 + r) * zld + n] = kRelu ? fmaxf(acc[u][r] + bias, 0.f) : elu1(acc[u][r] + bias);
             }
         }
     }
@@ -564,7 +567,7 @@ __global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict
     const int q0 = blockIdx.x * kTailQ;
     const int nq = min(kTailQ, Q - q0);
 
-    tail_tile_z(G, ldg, q0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
+    tail_tile_z<false>(G, ldg, q0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
     __syncthreads();
 
     tail_head(zs, zld, H2, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
@@ -809,7 +812,8 @@ __device__ __forceinline__ void relu_stage(const float *As, int lda, const float
 }
 
 // One workgroup per tile of up to 16 queries: z1 = ReLU(S W1a^T + b1a) with the tile's rows of S = G staged through LDS beside W1a
-// (query_tail_kernel's first product), z2 = ReLU(z1 W1b^T + b1b) from z1 in LDS, both on v_mfma_f32_16x16x4_f32, then tail_head on z2.
+// (tail_tile_z<true>: query_tail_kernel's first product behind a ReLU), z2 = ReLU(z1 W1b^T + b1b) from z1 in LDS, both on
+// v_mfma_f32_16x16x4_f32, then tail_head on z2.
 __global__ __launch_bounds__(256) void gin_query_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1a,
                                                              const float *__restrict__ b1a, const float *__restrict__ W1b,
                                                              const float *__restrict__ b1b, const float *__restrict__ Wl,
@@ -822,53 +826,10 @@ __global__ __launch_bounds__(256) void gin_query_tail_kernel(const float *__rest
     float *Ws = z2 + (size_t)kTailQ * z2ld;
     float *Gs = Ws + kTailCols * kTailLd;
     float *lg = Gs + kTailQ * kTailLd;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
     const int q0 = blockIdx.x * kTailQ;
     const int nq = min(kTailQ, Q - q0);
 
-    for (int n0 = 0; n0 < H2a; n0 += kTailCols) {
-        const int ncols = min(kTailCols, H2a - n0);  // a multiple of 16
-        f32x4 acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < K; k0 += kTailKS) {
-            const int k4 = min(kTailKS, K - k0) >> 2;  // float4 per staged row (K % 4 == 0)
-            __syncthreads();                           // the previous stage has been consumed
-            for (int idx = tid; idx < ncols * k4; idx += 256) {
-                const int n = idx / k4, kk = idx - n * k4;
-                *reinterpret_cast<float4 *>(Ws + n * kTailLd + kk * 4) =
-                    *reinterpret_cast<const float4 *>(W1a + (int64_t)(n0 + n) * K + k0 + kk * 4);
-            }
-            for (int idx = tid; idx < kTailQ * k4; idx += 256) {
-                const int r = idx / k4, kk = idx - r * k4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);  // rows past Q: computed as zeros, never stored
-                if (r < nq) v = *reinterpret_cast<const float4 *>(G + (int64_t)(q0 + r) * ldg + k0 + kk * 4);
-                *reinterpret_cast<float4 *>(Gs + r * kTailLd + kk * 4) = v;
-            }
-            __syncthreads();
-            for (int kk = 0; kk < k4; ++kk) {
-                const float a = Gs[r16 * kTailLd + kk * 4 + kq];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int nb = (w * 4 + u) * 16;
-                    if (nb < ncols) {  // wave-uniform
-                        const float b = Ws[(nb + r16) * kTailLd + kk * 4 + kq];
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[u], 0, 0, 0);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int nb = (w * 4 + u) * 16;
-            if (nb < ncols) {
-                const int n = n0 + nb + r16;
-                const float bias = b1a ? b1a[n] : 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) z1[(kq * 4 + r) * z1ld + n] = fmaxf(acc[u][r] + bias, 0.f);
-            }
-        }
-    }
+    tail_tile_z<true>(G, ldg, q0, nq, W1a, b1a, K, H2a, z1, z1ld, Ws, Gs);
     relu_stage(z1, z1ld, W1b, b1b, H2a, H2b, Ws, z2, z2ld);  // its first barrier orders z1's writers
     __syncthreads();
     tail_head(z2, z2ld, H2b, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
@@ -948,44 +909,30 @@ __host__ __device__ constexpr size_t graph_tail_lds_floats(int H2, int C) {
 }
 static_assert(graph_tail_lds_floats(512, 48) * sizeof(float) <= kTailLdsMax, "the default model's graph tail must fit LDS");
 
-// One workgroup per graph: its segment of G in tiles of 16 rows through tail_tile_z; after each tile thread t folds the tile's live
-// rows into ps[n] for its columns n = t, t + 256, ... (the same thread owns a column from the first tile to the division, so ps
-// needs no barrier of its own before the head).  One thread per class then runs the head's chain over ps.
-__global__ __launch_bounds__(256) void graph_query_tail_kernel(const float *__restrict__ G, int64_t ldg, const int64_t *__restrict__ pptr,
-                                                               const float *__restrict__ W1, const float *__restrict__ b1,
-                                                               const float *__restrict__ Wl, const float *__restrict__ bl, int32_t H,
-                                                               int32_t H2, int32_t C, int32_t pool, int32_t softmax,
-                                                               float *__restrict__ out, int64_t ldo) {
-    extern __shared__ float smem[];
-    const int zld = H2 + 4;
-    float *zs = smem;
-    float *Ws = zs + (size_t)kTailQ * zld;
-    float *Gs = Ws + kTailCols * kTailLd;
-    float *ps = Gs + kTailQ * kTailLd;  // 16-byte aligned: every part in front of it is a multiple of four floats
-    float *lg = ps + H2;
-    const int tid = threadIdx.x;
-    const int64_t s0 = pptr[blockIdx.x], s1 = pptr[blockIdx.x + 1];
-    for (int n = tid; n < H2; n += 256) ps[n] = 0.f;
-    for (int64_t t0 = s0; t0 < s1; t0 += kTailQ) {
-        const int nq = (int)min((int64_t)kTailQ, s1 - t0);
-        tail_tile_z(G, ldg, t0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
-        __syncthreads();
-        for (int n = tid; n < H2; n += 256) {
-            float p = ps[n];
-            int r = 0;
-            if (pool == 0 && t0 == s0) {  // the maximum starts from the segment's first row
-                p = zs[n];
-                r = 1;
-            }
-            for (; r < nq; ++r) {  // live rows only: a padded row holds ELU(b1)
-                const float z = zs[r * zld + n];
-                p = pool == 0 ? fmaxf(p, z) : p + z;
-            }
-            ps[n] = p;
+// The pool over a tile's z [16][zld] in LDS (written before a barrier): thread t folds the tile's live rows, ascending, into ps[n] for
+// its columns n = t, t + 256, ...  first: the segment's first tile (the maximum starts from its first row).
+__device__ __forceinline__ void graph_pool_fold(const float *zs, int zld, int32_t H2, int nq, bool first, int32_t pool, float *ps) {
+    for (int n = threadIdx.x; n < H2; n += 256) {
+        float p = ps[n];
+        int r = 0;
+        if (pool == 0 && first) {  // the maximum starts from the segment's first row
+            p = zs[n];
+            r = 1;
         }
+        for (; r < nq; ++r) {  // live rows only: a padded row holds act(b1)
+            const float z = zs[r * zld + n];
+            p = pool == 0 ? fmaxf(p, z) : p + z;
+        }
+        ps[n] = p;
     }
-    if (pool != 0 && s1 > s0) {
-        const float cnt = (float)(s1 - s0);
+}
+
+// The mean's division, the head's chain over ps (one thread per class) and the softmax of one graph; lg [C] in LDS, out: the graph's row.
+__device__ __forceinline__ void graph_pool_head(float *ps, int32_t H2, int64_t cnt_rows, int32_t pool, const float *__restrict__ Wl,
+                                                const float *__restrict__ bl, int32_t C, int32_t softmax, float *lg, float *__restrict__ out) {
+    const int tid = threadIdx.x;
+    if (pool != 0 && cnt_rows > 0) {
+        const float cnt = (float)cnt_rows;
         for (int n = tid; n < H2; n += 256) ps[n] = ps[n] / cnt;
     }
     __syncthreads();
@@ -1017,7 +964,200 @@ __global__ __launch_bounds__(256) void graph_query_tail_kernel(const float *__re
         }
         __syncthreads();
     }
-    for (int c = tid; c < C; c += 256) out[(int64_t)blockIdx.x * ldo + c] = lg[c];
+    for (int c = tid; c < C; c += 256) out[c] = lg[c];
+}
+
+// One workgroup per graph: its segment of G in tiles of 16 rows through tail_tile_z; after each tile thread t folds the tile's live
+// rows into ps[n] for its columns n = t, t + 256, ... (the same thread owns a column from the first tile to the division, so ps
+// needs no barrier of its own before the head).  One thread per class then runs the head's chain over ps.
+__global__ __launch_bounds__(256) void graph_query_tail_kernel(const float *__restrict__ G, int64_t ldg, const int64_t *__restrict__ pptr,
+                                                               const float *__restrict__ W1, const float *__restrict__ b1,
+                                                               const float *__restrict__ Wl, const float *__restrict__ bl, int32_t H,
+                                                               int32_t H2, int32_t C, int32_t pool, int32_t softmax,
+                                                               float *__restrict__ out, int64_t ldo) {
+    extern __shared__ float smem[];
+    const int zld = H2 + 4;
+    float *zs = smem;
+    float *Ws = zs + (size_t)kTailQ * zld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *ps = Gs + kTailQ * kTailLd;  // 16-byte aligned: every part in front of it is a multiple of four floats
+    float *lg = ps + H2;
+    const int tid = threadIdx.x;
+    const int64_t s0 = pptr[blockIdx.x], s1 = pptr[blockIdx.x + 1];
+    for (int n = tid; n < H2; n += 256) ps[n] = 0.f;
+    for (int64_t t0 = s0; t0 < s1; t0 += kTailQ) {
+        const int nq = (int)min((int64_t)kTailQ, s1 - t0);
+        tail_tile_z<false>(G, ldg, t0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
+        __syncthreads();
+        graph_pool_fold(zs, zld, H2, nq, t0 == s0, pool, ps);
+    }
+    graph_pool_head(ps, H2, s1 - s0, pool, Wl, bl, C, softmax, lg, out + (int64_t)blockIdx.x * ldo);
+}
+
+// ---- graph queries for two GINConv layers (nn = Linear, ReLU, Linear, ReLU) ----
+// gin_query_hops_kernel on every pooled row of a graph forms h_c once per entry that reaches row c plus once for c itself: sum_r (deg(r) + 1)
+// dense row-products of Hb x Ha.  Here every row of the graph takes the product ONCE per (graph, slab) and stays in LDS:
+//   a_r   = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a)      EVERY r in [r0, r1)      gin_graph_query_hops_kernel
+//   h_r   = ReLU(W0b a_r + b0b)                                                        EVERY r in [r0, r1), in the LDS window
+//   s_r   = sum_{e in row r} val[e] h_{col[e]} + (1 + eps1) h_r                        r among the graph's pooled rows -> G
+//   z_r   = ReLU(W1b ReLU(W1a s_r + b1a) + b1b);  p = max_r z_r | mean_r z_r;  out = Wl p + bl  (softmax)      gin_graph_query_tail_kernel
+// Operation order (tests/gin_graph_query_reference.py mirrors it), with o0 = 1.0f + eps0[0] and o1 = 1.0f + eps1[0] formed once in fp32:
+//   hops  phase 1: a_r and h_r exactly as gin_query_hops_kernel's "row r" and "product" (gin_row, lds_tile_product: the same bits; a slab
+//         takes its own 256 columns of W0b, every slab forms the same a_r).  phase 2: s = 0; s = fmaf(val[e], h_{col[e]}[c], s) over the
+//         pooled row's entries in CSR order, ONE chain (no fold groups: the sum differs from gin_query_hops_kernel's s_q only by that
+//         order); then s = fmaf(o1, h_r[c], s).  A pooled row without entries gives fmaf(o1, h_r, 0).
+//   tail  z1 = ReLU(fmaf chain over k ascending of G[r][k] W1a[n][k], from 0, + b1a[n]), z2 = ReLU(the same chain of z1 and W1b + b1b[n])
+//         as gin_query_tail_kernel's, in tiles of 16 rows of the segment; the pool, the head and the softmax as graph_query_tail_kernel's
+//         (graph_pool_fold, graph_pool_head: live rows only, ascending; an empty segment: p = 0).
+constexpr int kGinWinPad = 4;  // the window's row stride is min(Hb, 256) + 4 floats: see gin_graph_query_hops_kernel
+
+__host__ __device__ constexpr size_t gin_graph_hops_lds_floats(int max_rows, int Ha, int Hb) {
+    return gin_hops_lds_floats(Ha) + (size_t)max_rows * ((Hb < kTailCols ? Hb : kTailCols) + kGinWinPad);
+}
+
+// One workgroup of four waves per (graph, 256-column slab of Hb), the slab fastest.  Phase 1, per tile of 16 rows of the graph: the
+// waves form a_r into the A stage (row i of the tile by wave i % 4, all Ha columns in NS slots; rows past r1 are zeros), all four
+// multiply the tile by the slab's rows of W0b (lds_tile_product) and store ReLU(. + b0b) for the tile's live rows into the window
+// hs [r1 - r0][wld].  wld = min(Hb, 256) + 4: the MFMA result gives lane l rows 4 (l >> 4) + r of column l & 15, so one store
+// instruction writes 16 consecutive columns of four rows that lie 4 wld floats apart; ds_write_b32 banks are (address / 4) % 32
+// within a half wave (rows 4 kq + r for kq = 0, 1 or 2, 3), and 4 wld = 16 (mod 32) puts the half's two rows on disjoint halves of
+// the banks (a stride of min(Hb, 256) itself would put both on the same 16: 2-way).  wld stays a multiple of 4, so phase 2's rows
+// are 16-byte aligned and a wave reads 64 consecutive float4 of one row, as graph_query_hops_kernel does.  One barrier, then phase 2:
+// the graph's pooled rows dealt round-robin to the waves, entries fetched 64 at a time, (window row, value) broadcast by v_readlane.
+template <int NS>
+__global__ __launch_bounds__(256) void gin_graph_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                                   const float *__restrict__ val, const float *__restrict__ T, int64_t ldt,
+                                                                   const int32_t *__restrict__ xrow, const float *__restrict__ b0a,
+                                                                   const float *__restrict__ eps0, const float *__restrict__ W0b,
+                                                                   const float *__restrict__ b0b, const float *__restrict__ eps1,
+                                                                   const int64_t *__restrict__ seg, const int64_t *__restrict__ prow,
+                                                                   const int64_t *__restrict__ pptr, int32_t Ha, int32_t Hb, int32_t max_rows,
+                                                                   float *__restrict__ G, int64_t ldg, int32_t n_slabs) {
+    extern __shared__ float smem[];
+    const int ald = Ha + 4, wld = min(Hb, kTailCols) + kGinWinPad;
+    float *As = smem;
+    float *Ws = As + (size_t)kGinRows * ald;
+    float *hs = Ws + kTailCols * kTailLd;  // 16-byte aligned: both parts in front of it are multiples of four floats
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r16 = lane & 15, kq = lane >> 4;
+    const int gi = blockIdx.x / n_slabs, c0 = (blockIdx.x % n_slabs) * kTailCols;
+    const int r0 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi]), r1 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi + 1]);
+    if (r1 - r0 > max_rows) return;  // workgroup-uniform: the window was sized for max_rows
+    const int ncols = min(kTailCols, Hb - c0);  // the slab's columns: a multiple of 16
+    const float o0 = 1.0f + eps0[0], o1 = 1.0f + eps1[0];
+    const bool has_bias = b0a != nullptr;
+    const float *Tc[NS];
+    float4 bias[NS];
+    bool live[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int c = s * 256 + lane * 4;
+        live[s] = c < Ha;  // Ha % 4 == 0: a live lane owns four whole columns
+        Tc[s] = T + (live[s] ? c : 0);
+        bias[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (has_bias && live[s]) bias[s] = make_float4(b0a[c], b0a[c + 1], b0a[c + 2], b0a[c + 3]);
+    }
+    for (int t0 = r0; t0 < r1; t0 += kGinRows) {
+        __syncthreads();  // the previous tile's product has read As
+        for (int i = w; i < kGinRows; i += 4) {
+            float4 a[NS];
+            if (t0 + i < r1) {  // wave-uniform
+                gin_row<NS>(rowptr, col, val, Tc, ldt, xrow, o0, has_bias, bias, t0 + i, lane, a);
+            } else {  // a defined row for the MFMA; its h is never stored
+#pragma unroll
+                for (int s = 0; s < NS; ++s) a[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (live[s]) *reinterpret_cast<float4 *>(As + i * ald + s * 256 + lane * 4) = a[s];
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        lds_tile_product(As, ald, W0b, Ha, c0, ncols, Ws, acc);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {
+                const float b = b0b ? b0b[c0 + nb + r16] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = t0 + kq * 4 + r;
+                    if (row < r1) hs[(row - r0) * wld + nb + r16] = fmaxf(acc[u][r] + b, 0.f);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const bool on = lane * 4 < ncols;  // ncols % 4 == 0: a live lane owns four whole columns of the slab
+    const float *hc = hs + (on ? lane * 4 : 0);
+    const int64_t p1 = pptr[gi + 1];
+    for (int64_t j = pptr[gi] + w; j < p1; j += kGatherWaves) {
+        const int r = __builtin_amdgcn_readfirstlane((int)prow[j]);
+        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = n0; base < n1; base += 64) {
+            const int cnt = min(64, n1 - base);
+            int my = 0, mv = 0;
+            if (lane < cnt) {
+                my = col[base + lane] - r0;
+                mv = __float_as_int(val[base + lane]);
+            }
+            for (int k = 0; k < cnt; ++k) {
+                const int node = __builtin_amdgcn_readlane(my, k);
+                const float wv = __int_as_float(__builtin_amdgcn_readlane(mv, k));
+                if (on) {
+                    const float4 h = *reinterpret_cast<const float4 *>(hc + node * wld);
+                    g.x = fmaf(wv, h.x, g.x);
+                    g.y = fmaf(wv, h.y, g.y);
+                    g.z = fmaf(wv, h.z, g.z);
+                    g.w = fmaf(wv, h.w, g.w);
+                }
+            }
+        }
+        if (on) {
+            const float4 h = *reinterpret_cast<const float4 *>(hc + (r - r0) * wld);
+            g.x = fmaf(o1, h.x, g.x);
+            g.y = fmaf(o1, h.y, g.y);
+            g.z = fmaf(o1, h.z, g.z);
+            g.w = fmaf(o1, h.w, g.w);
+            *reinterpret_cast<float4 *>(G + j * ldg + c0 + lane * 4) = g;
+        }
+    }
+}
+
+__host__ __device__ constexpr size_t gin_graph_tail_lds_floats(int H2a, int H2b, int C) {
+    return gin_tail_lds_floats(H2a, H2b, C) + (size_t)H2b + (size_t)C;
+}
+static_assert(gin_graph_tail_lds_floats(512, 512, 48) * sizeof(float) <= kTailLdsMax, "the default model's graph tail must fit LDS");
+
+// One workgroup per graph: its segment of G in tiles of 16 rows through gin_query_tail_kernel's two stages (tail_tile_z<true>, then
+// relu_stage from z1 in LDS), the tile's live rows of z2 folded into ps as graph_query_tail_kernel does, then its head.  The LDS is
+// gin_query_tail_kernel's (whose 16 C floats of logits are not used here) with ps [H2b] and lg [C] behind it.
+__global__ __launch_bounds__(256) void gin_graph_query_tail_kernel(const float *__restrict__ G, int64_t ldg, const int64_t *__restrict__ pptr,
+                                                                   const float *__restrict__ W1a, const float *__restrict__ b1a,
+                                                                   const float *__restrict__ W1b, const float *__restrict__ b1b,
+                                                                   const float *__restrict__ Wl, const float *__restrict__ bl, int32_t K,
+                                                                   int32_t H2a, int32_t H2b, int32_t C, int32_t pool, int32_t softmax,
+                                                                   float *__restrict__ out, int64_t ldo) {
+    extern __shared__ float smem[];
+    const int z1ld = H2a + 4, z2ld = H2b + 4;
+    float *z1 = smem;
+    float *z2 = z1 + (size_t)kTailQ * z1ld;
+    float *Ws = z2 + (size_t)kTailQ * z2ld;
+    float *Gs = Ws + kTailCols * kTailLd;
+    float *ps = Gs + kTailQ * kTailLd;  // 16-byte aligned: every part in front of it is a multiple of four floats
+    float *lg = ps + H2b;
+    const int tid = threadIdx.x;
+    const int64_t s0 = pptr[blockIdx.x], s1 = pptr[blockIdx.x + 1];
+    for (int n = tid; n < H2b; n += 256) ps[n] = 0.f;
+    for (int64_t t0 = s0; t0 < s1; t0 += kTailQ) {
+        const int nq = (int)min((int64_t)kTailQ, s1 - t0);
+        tail_tile_z<true>(G, ldg, t0, nq, W1a, b1a, K, H2a, z1, z1ld, Ws, Gs);  // its first barrier orders the previous tile's readers
+        relu_stage(z1, z1ld, W1b, b1b, H2a, H2b, Ws, z2, z2ld);                 // its first barrier orders z1's writers
+        __syncthreads();
+        graph_pool_fold(z2, z2ld, H2b, nq, t0 == s0, pool, ps);
+    }
+    graph_pool_head(ps, H2b, s1 - s0, pool, Wl, bl, C, softmax, lg, out + (int64_t)blockIdx.x * ldo);
 }
 
 }  // namespace
@@ -1190,5 +1330,67 @@ extern "C" int fitgnn_gcn_graph_query_tail_f32(const float *G, int64_t ldg, cons
     if (const int rc = fitgnn_lds_limit_once((const void *)graph_query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
     hipLaunchKernelGGL(graph_query_tail_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, G, ldg, pptr, W1, b1, Wl, bl, H, H2, C,
                        pool, softmax, out, ldo);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t fitgnn_gin_graph_query_hops_lds_bytes(int32_t max_rows, int32_t Ha, int32_t Hb) {
+    if (max_rows < 0 || Ha < 4 || Hb < 16) return 0;
+    return gin_graph_hops_lds_floats(max_rows, Ha, Hb) * sizeof(float);
+}
+
+template <int NS>
+static int launch_gin_graph_hops(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt, const int32_t *xrow,
+                                 const float *b0a, const float *eps0, const float *W0b, const float *b0b, const float *eps1,
+                                 const int64_t *seg, const int64_t *prow, const int64_t *pptr, int32_t Q, int32_t Ha, int32_t Hb,
+                                 int32_t max_rows, float *G, int64_t ldg, size_t lds, int n_slabs, hipStream_t stream) {
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)gin_graph_query_hops_kernel<NS>, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL((gin_graph_query_hops_kernel<NS>), dim3((unsigned)(Q * n_slabs)), dim3(256), lds, stream, rowptr, col, val, T, ldt, xrow,
+                       b0a, eps0, W0b, b0b, eps1, seg, prow, pptr, Ha, Hb, max_rows, G, ldg, n_slabs);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_gin_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                               const int32_t *xrow, const float *b0a, const float *eps0, const float *W0b, const float *b0b,
+                                               const float *eps1, const int64_t *seg, const int64_t *prow, const int64_t *pptr, int32_t Q,
+                                               int32_t Ha, int32_t Hb, int32_t max_rows, float *G, int64_t ldg, void *stream) {
+    if (Q < 0 || Ha < 4 || (Ha % 4) != 0 || Ha > 512 || Hb < 16 || (Hb % 16) != 0 || Hb > 512 || max_rows < 0 || ldt < Ha || ldg < Hb)
+        return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gin_graph_query_hops_lds_bytes(max_rows, Ha, Hb);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // the largest graph's layer-0 rows do not fit LDS beside the two stages
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !eps0 || !W0b || !eps1 || !seg || !prow || !pptr || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G | (uintptr_t)W0b) % 16) != 0) return FITGNN_E_ALIGN;
+    const int n_slabs = (Hb + kTailCols - 1) / kTailCols;
+    if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
+    const hipStream_t st = (hipStream_t)stream;
+    return Ha <= 256 ? launch_gin_graph_hops<1>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, seg, prow, pptr, Q, Ha, Hb, max_rows,
+                                                G, ldg, lds, n_slabs, st)
+                     : launch_gin_graph_hops<2>(rowptr, col, val, T, ldt, xrow, b0a, eps0, W0b, b0b, eps1, seg, prow, pptr, Q, Ha, Hb, max_rows,
+                                                G, ldg, lds, n_slabs, st);
+}
+
+extern "C" size_t fitgnn_gin_graph_query_tail_lds_bytes(int32_t H2a, int32_t H2b, int32_t C) {
+    if (H2a <= 0 || H2b <= 0 || C <= 0) return 0;
+    return gin_graph_tail_lds_floats(H2a, H2b, C) * sizeof(float);
+}
+
+extern "C" int fitgnn_gin_graph_query_tail_f32(const float *G, int64_t ldg, const int64_t *pptr, int32_t Q, const float *W1a, const float *b1a,
+                                               const float *W1b, const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a,
+                                               int32_t H2b, int32_t C, int32_t pool, int32_t softmax, float *out, int64_t ldo, void *stream) {
+    if (Q < 0 || K < 4 || (K % 4) != 0 || H2a < 16 || (H2a % 16) != 0 || H2b < 16 || (H2b % 16) != 0 || C < 1 || ldg < K || ldo < C ||
+        pool < 0 || pool > 1)
+        return FITGNN_E_BADARG;
+    if ((ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gin_graph_query_tail_lds_bytes(H2a, H2b, C);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // z1, z2 of the tile and the pooled row do not fit LDS
+    if (Q == 0) return 0;
+    if (!G || !pptr || !W1a || !W1b || !Wl || !out) return FITGNN_E_BADARG;
+    if ((((uintptr_t)G | (uintptr_t)W1a | (uintptr_t)W1b | (uintptr_t)Wl | (uintptr_t)out) % 16) != 0) return FITGNN_E_ALIGN;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)gin_graph_query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(gin_graph_query_tail_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, G, ldg, pptr, W1a, b1a, W1b, b1b, Wl,
+                       bl, K, H2a, H2b, C, pool, softmax, out, ldo);
     return (int)hipGetLastError();
 }

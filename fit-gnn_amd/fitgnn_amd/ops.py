@@ -1385,6 +1385,58 @@ def gin_query_supported(model):
             and 0 < _lib.lib().fitgnn_gin_query_tail_lds_bytes(hidden[2], hidden[3], C) <= 160 * 1024)
 
 
+def gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow=None, b0a=None, out=None):
+    """G [P, Hb]: row j = s_r = sum_{e in row r} val[e] h_{col[e]} + (1 + eps1) h_r for view row r = prow[j], over its graph's layer-0
+    GIN rows h = ReLU(W0b ReLU(agg + (1 + eps0) root + b0a) + b0b), each formed once in LDS from T = X W0a^T [n_table, Ha] over the sum
+    CSR (fitgnn_gin_graph_query_hops_f32).  eps0 / eps1: float32 tensors of one element ON THE DEVICE.  seg int64 [Q, 2]: the row range
+    of every queried graph; prow int64 [P]: the pooled rows, graph i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the
+    largest range (host int, at most gin_graph_query_max_rows(Ha, Hb)).  The caller checks that prow and the CSR's columns stay inside
+    their graph's range: the kernel cannot."""
+    _lib.require_cuda(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, xrow, b0a)
+    Q, P, Ha, Hb = int(seg.shape[0]), int(prow.numel()), int(T.shape[1]), int(W0b.shape[0])
+    G = out if out is not None else torch.empty((P, Hb), dtype=torch.float32, device=T.device)
+    if P == 0:
+        return G
+    _lib.check(_lib.lib().fitgnn_gin_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                          _lib.dptr(xrow), _lib.dptr(b0a), _lib.dptr(eps0), _lib.dptr(W0b), _lib.dptr(b0b),
+                                                          _lib.dptr(eps1), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q, Ha, Hb,
+                                                          int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
+               "fitgnn_gin_graph_query_hops_f32")
+    return G
+
+
+def gin_graph_query_tail(G, pptr, W1a, b1a, W1b, b1b, Wl, bl, pool="max", softmax=False, out=None):
+    """[Q, C] = Wl pool_i(ReLU(W1b ReLU(W1a G[r] + b1a) + b1b): r in pptr[i] .. pptr[i + 1]) + bl per graph, pool "max" or "mean", a
+    softmax on request (fitgnn_gin_graph_query_tail_f32).  W1a [H2a, K], W1b [H2b, H2a], Wl [C, H2b] contiguous; pptr int64 [Q + 1]."""
+    _lib.require_cuda(G, pptr, W1a, b1a, W1b, b1b, Wl, bl)
+    Q, K = int(pptr.numel()) - 1, int(G.shape[1])
+    H2a, H2b, C = int(W1a.shape[0]), int(W1b.shape[0]), int(Wl.shape[0])
+    y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
+    _lib.check(_lib.lib().fitgnn_gin_graph_query_tail_f32(_lib.dptr(G), G.stride(0), _lib.dptr(pptr), Q, _lib.dptr(W1a), _lib.dptr(b1a),
+                                                          _lib.dptr(W1b), _lib.dptr(b1b), _lib.dptr(Wl), _lib.dptr(bl), K, H2a, H2b, C,
+                                                          {"max": 0, "mean": 1}[pool], 1 if softmax else 0, _lib.dptr(y), y.stride(0),
+                                                          _lib.stream_ptr(G.device)), "fitgnn_gin_graph_query_tail_f32")
+    return y
+
+
+def gin_graph_query_max_rows(Ha, Hb):
+    """The largest graph (rows) whose layer-0 rows fitgnn_gin_graph_query_hops_f32 holds in LDS beside its two stages at the MLP widths
+    Ha, Hb (0 for widths it does not take)."""
+    L = _lib.lib()
+    base, one = int(L.fitgnn_gin_graph_query_hops_lds_bytes(0, int(Ha), int(Hb))), int(L.fitgnn_gin_graph_query_hops_lds_bytes(1, int(Ha), int(Hb)))
+    return max(0, (160 * 1024 - base) // (one - base)) if one > base > 0 else 0
+
+
+def gin_graph_query_supported(model):
+    """The two GIN graph-query kernels answer for `model`: gin_query_supported's conditions with the graph tail's LDS bound in place of
+    the node tail's."""
+    if not gin_query_supported(model):
+        return False
+    lins = [model.conv[1].nn[0], model.conv[1].nn[2]]
+    return 0 < _lib.lib().fitgnn_gin_graph_query_tail_lds_bytes(int(lins[0].weight.shape[0]), int(lins[1].weight.shape[0]),
+                                                                int(model.lt1.weight.shape[0])) <= 160 * 1024
+
+
 def segment_sum(seg_off, members, X, n_seg):
     """out[s] = sum of X[members[seg_off[s]:seg_off[s+1]]] (fitgnn_segment_sum_f32)."""
     _lib.require_cuda(seg_off, members, X)

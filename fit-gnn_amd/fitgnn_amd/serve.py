@@ -55,6 +55,21 @@ predict() call shares two launches:
 A graph is a contiguous, block-diagonal row range of its view, so the layer-0 rows of a graph of up to 160 rows at hidden 512 fit the
 LDS window of one workgroup; calling the per-row gather on every pooled row would form each h_r once per entry that reaches it.  A
 larger graph's pooled rows take that per-row gather all the same (correct for any size), into the same G in front of the one tail.
+
+With gin_kernels=True a model of two GINConv layers (nn = Linear, ReLU, Linear, ReLU) takes two launches of its own over the view's sum
+CSR (no self loops added, val = 1).  A GIN layer-0 row carries a dense Hb x Ha product behind a ReLU; the per-row kernel
+(ops.gin_query_hops) forms it once per entry that reaches the row and once for the row itself, sum_r (deg(r) + 1) products for a graph
+whose rows are all pooled, where the window forms each ONCE:
+
+    T     = X W0a^T    [n_rows, Ha]                                     once per set of weights (one ops.Linear, no bias)
+    a_r   = ReLU(sum_{k in row r} val[k] T[col[k]] + (1 + eps0) T[r] + b0a)     EVERY row r of the graph
+    h_r   = ReLU(W0b a_r + b0b)                                         EVERY row r of the graph, formed once, in LDS
+    s_r   = sum_{e in row r} val[e] h_{col[e]} + (1 + eps1) h_r         r among the graph's pooled rows     ops.gin_graph_query_hops
+    out   = Wl pool_r ReLU(W1b ReLU(W1a s_r + b1a) + b1b) + bl  (softmax)                                   ops.gin_graph_query_tail
+
+The window shares LDS with the product's two stages: ops.gin_graph_query_max_rows(Ha, Hb) rows, about 90 at 512 / 512 and about 450 at
+64 / 64.  A larger graph's pooled rows take ops.gin_query_hops (the same s_r), into the same G in front of the one tail.  The path is
+opt-in, as on the node engine; without the flag, and for any GIN model the kernels do not take, the model's own forward answers.
 """
 import numpy as np
 import torch
@@ -354,12 +369,15 @@ class GraphQueryEngine:
     graphs: gc_x, cluster_ptr, gc_edge_index) or "orig" (the uncoarsened graphs: x, node_ptr, edge_index -- the baseline); on "gc" and
     "orig" every row of a graph is pooled.  Default: "gs" for the *_gs classes, "gc" for the *_gc classes (whose forward pools every
     row: they do not take "gs").  max_window_rows: graphs with more rows than this -- or than the hops kernel's LDS window holds at the
-    model's hidden size -- are answered through the per-row gather inside the same call.
+    model's hidden size -- are answered through the per-row gather inside the same call.  gin_kernels: a model of two GINConv layers
+    with the reference's two-Linear ReLU MLP is answered by the GIN graph-query pair (off by default, as QueryEngine's switch is); it
+    changes nothing for any other model.
 
     The view's CSR, the per-graph pointers and the index of pooled rows are built here, once.  Any model the two kernels do not
-    take (ops.graph_query_supported) is answered by its own forward on gset.batch_ids(the unique ids, view)."""
+    take (ops.graph_query_supported, ops.gin_graph_query_supported behind gin_kernels) is answered by its own forward on
+    gset.batch_ids(the unique ids, view)."""
 
-    def __init__(self, model, gset, view=None, max_window_rows=None):
+    def __init__(self, model, gset, view=None, max_window_rows=None, gin_kernels=False):
         from . import network
         gs_cls = (network.Classify_graph_gs, network.Regress_graph_gs)
         gc_cls = (network.Classify_graph_gc, network.Regress_graph_gc)
@@ -377,6 +395,7 @@ class GraphQueryEngine:
         self.model, self.gset, self.view = model, gset, view
         self.classify = isinstance(model, (network.Classify_graph_gs, network.Classify_graph_gc))
         self.max_window_rows = None if max_window_rows is None else int(max_window_rows)
+        self.gin_kernels = bool(gin_kernels)
         ptr, x, mask = {"gs": (gset.gs_ptr, gset.gs_x, gset.gs_mask), "gc": (gset.cluster_ptr, gset.gc_x, None),
                         "orig": (gset.node_ptr, gset.x, None)}[view]
         ptr = np.asarray(ptr, dtype=np.int64)
@@ -391,38 +410,62 @@ class GraphQueryEngine:
             pp = np.searchsorted(prow.cpu().numpy(), ptr, side="left").astype(np.int64)
         self._prow, self._pp = prow, pp
         self._prow_host = prow.cpu().numpy()
-        self._T = None          # (W0, W0._version, T)
-        self._fused = None      # (key of the model's layers and parameters, the kernels answer)
+        self._T = None          # (W0, W0._version, T): W0 = conv[0].lin.weight, on the GIN path conv[0].nn[0].weight
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gin" | None: the kernels that answer)
+        self._sum = None        # the view's sum CSR (the GIN path's pattern), looked up once
 
-    @property
-    def fused(self):
-        """The two graph-query kernels answer for the model (otherwise its own forward does); re-evaluated when a layer or a
-        parameter's storage, type or shape has changed."""
+    def _kind(self):
+        """"gcn" (ops.graph_query_supported), "gin" (gin_kernels and ops.gin_graph_query_supported) or None, re-evaluated only when a
+        layer or a parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
+        if self.gin_kernels:
+            mlps = [getattr(c, "nn", None) for c in m.conv]
+            subs = [list(n) if isinstance(n, torch.nn.Sequential) else [] for n in mlps]
+            params += [getattr(l, a, None) for n in subs for l in n for a in ("weight", "bias")] + [getattr(c, "eps", None) for c in m.conv]
+            params += [type(l) for n in subs for l in n]     # an activation swapped in place changes no parameter
         key = tuple(type(c) for c in m.conv) + tuple((p.data_ptr(), p.dtype, p.shape) if torch.is_tensor(p) else p for p in params)
         if self._fused is None or self._fused[0] != key:
-            self._fused = (key, bool(ops.graph_query_supported(m)))
+            kind = "gcn" if ops.graph_query_supported(m) else None
+            if kind is None and self.gin_kernels and ops.gin_graph_query_supported(m):
+                kind = "gin"
+            self._fused = (key, kind)
         return self._fused[1]
 
+    @property
+    def fused(self):
+        """The graph-query kernels answer for the model (otherwise its own forward does)."""
+        return self._kind() is not None
+
+    def _w0(self):
+        conv0 = self.model.conv[0]
+        return conv0.nn[0].weight if self._kind() == "gin" else conv0.lin.weight
+
     def refresh(self):
-        """Remake T = X W0^T from the model's current weights (done automatically when W0's storage or version changes)."""
+        """Remake T = X W0^T (on the GIN path X W0a^T, without the bias: the kernel adds it behind the aggregation) from the model's
+        current weights (done automatically when that weight's storage or version changes)."""
         if self.fused:
-            W0 = self.model.conv[0].lin.weight
+            W0 = self._w0()
             with torch.no_grad():
                 T = ops.Linear.apply(self.x.float(), W0, self.model.op_config).contiguous()
             self._T = (W0, W0._version, T)
         return self
 
     def _table(self):
-        if not ops._same_index(self._T, self.model.conv[0].lin.weight):
+        if not ops._same_index(self._T, self._w0()):
             self.refresh()
         return self._T[2]
 
+    def _sum_csr(self):
+        """The view's sum CSR (rows = targets, no self loops added, val = 1): nn.GINConv.forward's own lookup."""
+        if self._sum is None:
+            self._sum = csr_for(self._whole["edge_index"], self.n_rows, "sum")
+        return self._sum
+
     @property
     def table_bytes(self):
-        """Bytes of T (0 when the model's own forward answers: it keeps none)."""
+        """Bytes of T -- [n_rows, Ha] on the GIN path -- (0 when the model's own forward answers: it keeps none)."""
         if not self.fused:
             return 0
         T = self._table()
@@ -447,12 +490,14 @@ class GraphQueryEngine:
             return self._predict_forward(ids)
 
     def _predict_fused(self, ids, cnt):
-        m, f, dev = self.model, self.graph.f, self.x.device
+        m, dev = self.model, self.x.device
+        gin = self._kind() == "gin"
+        f = self._sum_csr().f if gin else self.graph.f
         C = int(m.lt1.weight.shape[0])
         if ids.size == 0:
             return torch.empty((0, C), dtype=torch.float32, device=dev)
         T = self._table()
-        H, Q = int(T.shape[1]), int(ids.size)
+        Q = int(ids.size)
         # the launch's index arrays are made on the host, where the ids and the pointers are, and go up in ONE copy: no device glue
         pptr_h = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         P = int(pptr_h[-1])
@@ -462,20 +507,40 @@ class GraphQueryEngine:
         seg_h = np.stack([self._ptr[ids], self._ptr[ids + 1]], 1).reshape(-1)
         packed = torch.from_numpy(np.concatenate([seg_h, pptr_h, prow_h])).to(dev)
         seg, pptr, prow = packed[:2 * Q].view(Q, 2), packed[2 * Q:3 * Q + 1], packed[3 * Q + 1:]
-        limit = ops.graph_query_max_rows(H)
+        pool = "max" if self.classify else "mean"
+        if gin:    # eps0 / eps1 stay on the device: the kernels read them
+            (l0a, _, l0b, _), (l1a, _, l1b, _) = m.conv[0].nn, m.conv[1].nn
+            eps0, eps1 = m.conv[0].eps.detach(), m.conv[1].eps.detach()
+            Hg = int(l0b.weight.shape[0])
+            limit = ops.gin_graph_query_max_rows(int(T.shape[1]), Hg)
+        else:
+            Hg = int(T.shape[1])
+            limit = ops.graph_query_max_rows(Hg)
+            b0 = m.conv[0].bias
         if self.max_window_rows is not None:
             limit = min(limit, self.max_window_rows)
         large = n_rows > limit
-        G = torch.empty((P, H), dtype=torch.float32, device=dev)
-        b0 = m.conv[0].bias
+        G = torch.empty((P, Hg), dtype=torch.float32, device=dev)
         if not large.all():
-            # a graph beyond max_rows is skipped by the launch itself: its rows of G are written by the gather below
-            ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, int(n_rows[~large].max()), b0=b0, out=G)
-        if large.any():   # the per-row gather: correct for any size, the view being block-diagonal
+            # a graph beyond max_rows is skipped by the launch itself: its rows of G are written by the per-row kernel below
+            window = int(n_rows[~large].max())
+            if gin:
+                ops.gin_graph_query_hops(f.rowptr, f.col, f.val, T, eps0, l0b.weight, l0b.bias, eps1, seg, prow, pptr, window,
+                                         b0a=l0a.bias, out=G)
+            else:
+                ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, window, b0=b0, out=G)
+        if large.any():   # the per-row kernel: correct for any size, the view being block-diagonal
             pos = torch.from_numpy(np.nonzero(np.repeat(large, cnt))[0]).to(dev)
-            G.index_copy_(0, pos, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, prow.index_select(0, pos), b0=b0))
-        return ops.gcn_graph_query_tail(G, pptr, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias,
-                                        pool="max" if self.classify else "mean", softmax=self.classify)
+            rows = prow.index_select(0, pos)
+            if gin:
+                G.index_copy_(0, pos, ops.gin_query_hops(f.rowptr, f.col, f.val, T, eps0, l0b.weight, l0b.bias, eps1, rows, b0a=l0a.bias))
+            else:
+                G.index_copy_(0, pos, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, b0=b0))
+        if gin:
+            return ops.gin_graph_query_tail(G, pptr, l1a.weight, l1a.bias, l1b.weight, l1b.bias, m.lt1.weight, m.lt1.bias, pool=pool,
+                                            softmax=self.classify)
+        return ops.gcn_graph_query_tail(G, pptr, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, pool=pool,
+                                        softmax=self.classify)
 
     def _predict_forward(self, ids):
         """The model's own forward on the unique graphs as one block-diagonal batch."""

@@ -18,6 +18,8 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::gin_query_tail(G, W1a, b1a?, W1b, b1b?, Wl, bl?, log_softmax) -> out                           eps0 / eps1 one float each on the device)
     fitgnn::gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow?, b0?) -> G [P, H]     the two graph-query launches
     fitgnn::gcn_graph_query_tail(G, pptr, W1, b1?, Wl, bl?, pool (0 max, 1 mean), softmax) -> out [Q, C]     (fitgnn_amd.serve.GraphQueryEngine)
+    fitgnn::gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b?, eps1, seg, prow, pptr, max_rows, xrow?, b0a?) -> G [P, Hb]     their GIN
+    fitgnn::gin_graph_query_tail(G, pptr, W1a, b1a?, W1b, b1b?, Wl, bl?, pool (0 max, 1 mean), softmax) -> out [Q, C]                 counterparts
                                               (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
@@ -52,6 +54,10 @@ _LIB.define("gcn_query_tail(Tensor G, Tensor W1, Tensor? b1, Tensor Wl, Tensor? 
 _LIB.define("gcn_graph_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor seg, Tensor prow, Tensor pptr, int max_rows, "
             "Tensor? xrow, Tensor? b0) -> Tensor")
 _LIB.define("gcn_graph_query_tail(Tensor G, Tensor pptr, Tensor W1, Tensor? b1, Tensor Wl, Tensor? bl, int pool, bool softmax) -> Tensor")
+_LIB.define("gin_graph_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor eps0, Tensor W0b, Tensor? b0b, Tensor eps1, "
+            "Tensor seg, Tensor prow, Tensor pptr, int max_rows, Tensor? xrow, Tensor? b0a) -> Tensor")
+_LIB.define("gin_graph_query_tail(Tensor G, Tensor pptr, Tensor W1a, Tensor? b1a, Tensor W1b, Tensor? b1b, Tensor Wl, Tensor? bl, int pool, "
+            "bool softmax) -> Tensor")
 
 
 def _spmm_csr(rowptr, col, val, X, tiles, window_rows, bias, epilogue, p, seed, mask):
@@ -145,7 +151,16 @@ def _gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool, softmax):
     return ops.gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool=("max", "mean")[pool], softmax=softmax)
 
 
+def _gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow, b0a):
+    return ops.gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow=xrow, b0a=b0a)
+
+
+def _gin_graph_query_tail(G, pptr, W1a, b1a, W1b, b1b, Wl, bl, pool, softmax):
+    return ops.gin_graph_query_tail(G, pptr, W1a, b1a, W1b, b1b, Wl, bl, pool=("max", "mean")[pool], softmax=softmax)
+
+
 for _name, _fn in (("gcn_graph_query_hops", _gcn_graph_query_hops), ("gcn_graph_query_tail", _gcn_graph_query_tail),
+                   ("gin_graph_query_hops", _gin_graph_query_hops), ("gin_graph_query_tail", _gin_graph_query_tail),
                    ("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gin_query_hops", _gin_query_hops), ("gin_query_tail", _gin_query_tail), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
                    ("lift_adjacency", _lift_adjacency)):
@@ -235,6 +250,16 @@ def _(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow, b0):
 
 @torch.library.register_fake("fitgnn::gcn_graph_query_tail")
 def _(G, pptr, W1, b1, Wl, bl, pool, softmax):
+    return G.new_empty((pptr.shape[0] - 1, Wl.shape[0]))
+
+
+@torch.library.register_fake("fitgnn::gin_graph_query_hops")
+def _(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow, b0a):
+    return T.new_empty((prow.shape[0], W0b.shape[0]))
+
+
+@torch.library.register_fake("fitgnn::gin_graph_query_tail")
+def _(G, pptr, W1a, b1a, W1b, b1b, Wl, bl, pool, softmax):
     return G.new_empty((pptr.shape[0] - 1, Wl.shape[0]))
 
 

@@ -720,6 +720,44 @@ int fitgnn_gin_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const floa
                               const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a, int32_t H2b, int32_t C,
                               float *out, int64_t ldo, int32_t log_softmax, void *stream);
 
+/* Graph-level queries for two such GINConv layers: two launches for any number of graphs, over a whole view's sum CSR (all rows of all
+ * graphs, block-diagonal per graph; no self loops added, val = 1, read all the same).  The first: G[j][0:Hb) = s_{prow[j]} for every
+ * pooled row of every queried graph, over T = X W0a^T [n_table x Ha] (row stride ldt), t(r) = xrow ? xrow[r] : r:
+ *   a_r = ReLU(sum_{k in row r} val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a),  h_r = ReLU(W0b a_r + b0b)   for EVERY row r of graph i's
+ *                                                                                  range [seg[i][0], seg[i][1]), each formed ONCE,
+ *   s_r = sum_{e in row r} val[e] h_{col[e]} + (1 + eps1) h_r                      for r = prow[j], pptr[i] <= j < pptr[i + 1].
+ * fitgnn_gin_query_hops_f32 on the same rows forms h_c once per entry that reaches c and once for c itself: sum_r (deg(r) + 1) dense
+ * row-products instead of seg[i][1] - seg[i][0].  One workgroup of four waves per graph and 256-column slab of Hb.  Phase 1 takes the
+ * graph's rows in tiles of 16: the waves form the rows a_r into LDS, the tile is multiplied by the slab's rows of W0b on the exact-fp32
+ * MFMA (an ascending-k fmaf chain; a_r and h_r are bit-equal to fitgnn_gin_query_hops_f32's), and the live rows of h go into an LDS
+ * window of the graph.  After one barrier the graph's pooled rows are dealt round-robin to the waves, each a single fmaf chain over the
+ * row's entries in CSR order followed by the root term.  No atomics: two launches give the same bits (operation order:
+ * csrc/query.hip).  A pooled row without entries gives (1 + eps1) h_r.  eps0, eps1 are DEVICE pointers to one float each.  seg
+ * (int64 [Q][2]) may repeat graphs and needs no order; prow (int64, rows of the view) lists graph i's pooled rows inside its range; pptr is
+ * int64 [Q + 1].  The kernel cannot check that prow and col stay inside the graph's range: the caller does.  max_rows: the host-known
+ * largest seg[i][1] - seg[i][0] (a graph with more rows is skipped: its rows of G are not written).  Dynamic LDS:
+ * fitgnn_gin_graph_query_hops_lds_bytes(max_rows, Ha, Hb) = (16 (Ha + 4) + 9216 + max_rows (min(Hb, 256) + 4)) * 4 bytes (0 for widths
+ * below the smallest the kernel takes).  xrow, b0a, b0b may be NULL.  Writes G[0..pptr[Q]) x [0..Hb) only.  Requires Ha >= 4, Ha % 4 == 0,
+ * Hb >= 16, Hb % 16 == 0, Ha, Hb <= 512, max_rows >= 0, ldt >= Ha, ldg >= Hb and the LDS at most 160 KiB (FITGNN_E_BADARG), ldt, ldg
+ * multiples of 4 and T, W0b, G 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_gin_graph_query_hops_lds_bytes(int32_t max_rows, int32_t Ha, int32_t Hb);
+int fitgnn_gin_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                    const int32_t *xrow, const float *b0a, const float *eps0, const float *W0b, const float *b0b,
+                                    const float *eps1, const int64_t *seg, const int64_t *prow, const int64_t *pptr, int32_t Q, int32_t Ha,
+                                    int32_t Hb, int32_t max_rows, float *G, int64_t ldg, void *stream);
+
+/* The second: out[i][:] = Wl pool(ReLU(W1b ReLU(W1a G[r] + b1a) + b1b) : pptr[i] <= r < pptr[i + 1]) + bl for i < Q, pool the maximum
+ * (pool == 0) or the mean (pool == 1) per column, followed by a max-subtracted softmax per row when softmax != 0.  One workgroup per
+ * graph: its segment of G in tiles of 16 rows through fitgnn_gin_query_tail_f32's two products (z2 is bit-equal to that kernel's), the
+ * live rows folded into the pooled row and the head exactly as fitgnn_gcn_graph_query_tail_f32 makes them.  W1a [H2a x K],
+ * W1b [H2b x H2a], Wl [C x H2b] contiguous; b1a, b1b, bl may be NULL; pptr is the first launch's.  Requires K % 4 == 0, H2a % 16 == 0,
+ * H2b % 16 == 0, C >= 1, ldg >= K, ldo >= C, pool in {0, 1} and fitgnn_gin_graph_query_tail_lds_bytes(H2a, H2b, C) <= 160 KiB
+ * (FITGNN_E_BADARG); ldg a multiple of 4 and G, W1a, W1b, Wl, out 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_gin_graph_query_tail_lds_bytes(int32_t H2a, int32_t H2b, int32_t C);
+int fitgnn_gin_graph_query_tail_f32(const float *G, int64_t ldg, const int64_t *pptr, int32_t Q, const float *W1a, const float *b1a,
+                                    const float *W1b, const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a,
+                                    int32_t H2b, int32_t C, int32_t pool, int32_t softmax, float *out, int64_t ldo, void *stream);
+
 /* =====================================================================================
  * Coarsen half: one contraction level of variation_neighborhoods
  * replaces: graph_coarsening/coarsening_utils.py contract_variation_linear :530-650,

@@ -23,20 +23,25 @@ Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>
                          fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded).
 
-    python tools/query_latency.py --task graph_reg | graph_cls [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512] [--samples 256]
-                                  [--rounds 5] [--batch 1024] [--out FILE]
+    python tools/query_latency.py --task graph_reg | graph_cls [--layer GINConv] [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512]
+                                  [--samples 256] [--rounds 5] [--batch 1024] [--out FILE]
 
 --task graph_reg / graph_cls: one GRAPH query through fitgnn_amd.serve.GraphQueryEngine (fitgnn_gcn_graph_query_hops_f32 and
 fitgnn_gcn_graph_query_tail_f32) against the per-graph forward inference.py times without --query_engine, on a GraphSet of
 graph_data.synthetic_molecules (graph_reg: Regress_graph_gs / _gc) or synthetic_graph_classes (graph_cls: Classify_graph_gs / _gc),
-extra-node layout.  Writes profiles/query_latency_<task>_<view>.json (or --out):
+extra-node layout.  --layer GINConv: a two-layer GIN model through GraphQueryEngine(gin_kernels=True)
+(fitgnn_gin_graph_query_hops_f32 over the sum CSR and fitgnn_gin_graph_query_tail_f32).  Writes
+profiles/query_latency_<task>_<view>.json (profiles/query_latency_<task>_<view>_GINConv.json with --layer GINConv; or --out):
   (a) engine_single      predict([g]) per sampled graph, bracketed as above;
   (b) graph_forward      the model on the graph cut out of the set (gset.batch(g, g + 1, view), its CSR and pool index pre-built),
                          measured twice per graph around the engine's turn, after one untimed pass;
   (c) engine_batch       predict(ids) at Q = --batch (ids drawn with repeats) against the same graphs one forward each (the loop (b)
                          runs) and against ONE forward of the model on gset.batch_ids(the unique ids) pre-built;
   table_row_reads        counted, not timed: sum over the pooled rows r of sum_{c in row r} deg(c) (the per-row gather on every pooled
-                         row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio."""
+                         row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio;
+  dense_rows             --layer GINConv, counted, not timed: the layer-0 rows that take the dense Hb x Ha product -- every row of the
+                         view once (the window path) against sum over the pooled rows r of deg(r) + 1 (fitgnn_gin_query_hops_f32 on
+                         every pooled row), and their ratio."""
 import argparse
 import json
 import os
@@ -245,11 +250,14 @@ def graph_main(a):
     gs = a.view == "gs"
     cls = ("Regress_graph_" if reg else "Classify_graph_") + ("gs" if gs else "gc")
     C = 1 if reg else int(mol["y"].max()) + 1
-    margs = argparse.Namespace(num_layers1=2, layer_name="GCNConv", num_features=int(gset.x.shape[1]), hidden=a.hidden, num_classes=C)
+    if a.layer not in ("GCNConv", "GINConv"):
+        raise SystemExit("--task graph_reg / graph_cls takes --layer GCNConv or GINConv")
+    gin = a.layer == "GINConv"
+    margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=int(gset.x.shape[1]), hidden=a.hidden, num_classes=C)
     torch.manual_seed(2)
     model = getattr(network, cls)(margs).to(dev).eval()
-    engine = serve.GraphQueryEngine(model, gset, view=a.view)
-    assert engine.fused and ops.graph_query_supported(model)
+    engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin)
+    assert engine.fused and (ops.gin_graph_query_supported(model) if gin else ops.graph_query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -314,7 +322,7 @@ def graph_main(a):
         t_whole = timed(lambda: call(whole))
 
     # counted: table rows read by the per-row gather on every pooled row against every layer-0 row formed once
-    f = engine.graph.f
+    f = engine._sum_csr().f if gin else engine.graph.f
     deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
     csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
     csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)
@@ -322,11 +330,14 @@ def graph_main(a):
     prow = engine._prow
     per_row = int((csum[rp[prow + 1]] - csum[rp[prow]]).sum())
     once = int(deg.sum())
+    if gin:   # every layer-0 row formed also reads its own table row
+        per_row += int(deg[prow].sum()) + int(prow.numel())
+        once += int(engine.n_rows)
 
     sa, s1, s2 = _stats(ta), _stats(tb1), _stats(tb2)
     base = min(s1["median_us"], s2["median_us"])
     spread = abs(s1["median_us"] - s2["median_us"])
-    res = dict(task=a.task, view=a.view, model=cls, hidden=a.hidden, classes=C, graphs=int(gset.n_graphs), view_rows=int(engine.n_rows),
+    res = dict(task=a.task, view=a.view, model=cls, layer=a.layer, hidden=a.hidden, classes=C, graphs=int(gset.n_graphs), view_rows=int(engine.n_rows),
                nnz=int(f.col.numel()), pooled_rows=int(prow.numel()), samples=len(graphs), rounds=a.rounds, device=torch.cuda.get_device_name(0),
                table=dict(rows=int(engine.n_rows), bytes=engine.table_bytes, build_s=round(t_table, 4)),
                engine_single=sa, graph_forward_first=s1, graph_forward_second=s2, per_round=per_round,
@@ -336,7 +347,13 @@ def graph_main(a):
                                  one_forward_per_graph_s=round(a.batch * base * 1e-6, 6),
                                  one_forward_on_the_unique_graphs_s=round(t_whole, 6)),
                table_row_reads=dict(per_row_gather=per_row, each_row_once=once, ratio=round(per_row / max(once, 1), 3)))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}.json")
+    if gin:
+        per_row_dense = int(deg[prow].sum()) + int(prow.numel())
+        res["dense_rows"] = dict(per_row_hops=per_row_dense, each_row_once=int(engine.n_rows),
+                                 ratio=round(per_row_dense / max(int(engine.n_rows), 1), 3),
+                                 window_rows=int(ops.gin_graph_query_max_rows(a.hidden, a.hidden)),
+                                 largest_graph_rows=int(np.diff(engine._ptr).max()))
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_GINConv' if gin else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
