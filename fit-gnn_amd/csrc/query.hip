@@ -14,7 +14,8 @@
 // Graph-level models (a pool over a graph's rows in front of the head) have fitgnn_gcn_graph_query_hops_f32 and
 // fitgnn_gcn_graph_query_tail_f32: a graph's layer-0 rows are formed once, in LDS (see graph_query_hops_kernel).  Two GINConv layers
 // have fitgnn_gin_graph_query_hops_f32 and fitgnn_gin_graph_query_tail_f32: the dense product behind layer 0's ReLU runs once per
-// row of the graph (see gin_graph_query_hops_kernel).
+// row of the graph (see gin_graph_query_hops_kernel).  Two GATConv layers have fitgnn_gat_graph_query_hops_f32 in front of the GCN graph
+// tail: a graph's attention rows and their two score dots are formed once, in LDS (see gat_graph_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -1160,6 +1161,119 @@ __global__ __launch_bounds__(256) void gin_graph_query_tail_kernel(const float *
     graph_pool_head(ps, H2b, s1 - s0, pool, Wl, bl, C, softmax, lg, out + (int64_t)blockIdx.x * ldo);
 }
 
+// ---- graph queries for two GATConv layers (heads = 1) ----
+// gat_query_hops_kernel on every pooled row q of a graph re-forms the layer-0 row h_j of every neighbour j (a softmax over row j, a
+// gather of deg(j) table rows) and its score dot u_s . h_j once per entry that reaches j, and h_q once per wave: sum_r (deg(r) + 1)
+// layer-0 rows for a graph whose rows are all pooled.  Here every row of the graph is formed ONCE and stays in LDS with its two dots:
+//   h_r   = ELU(sum_k alpha_rk T[t(k)] + b0),  alpha_r. = softmax_k lrelu(a0s[t(k)] + a0d[t(r)], slope0)   EVERY r in [r0, r1)
+//   ds_r  = u_s . h_r,  dd_r = u_d . h_r                                                                    EVERY r in [r0, r1)
+//   g_r   = sum_j beta_j h_j,  beta = softmax_j lrelu(ds_j + dd_r, slope1)      j in CSR row r, r among the graph's pooled rows -> G
+// and graph_query_tail_kernel finishes (sum beta = 1, so W1 g_r + b1 is conv1's output: the node path's argument).
+// Operation order (tests/gat_graph_query_reference.py mirrors it):
+//   hops  phase 1: h_r exactly as gat_query_hops_kernel's "row r" (gat_row: the same bits); ds_r and dd_r as its "dot" (row_dot: per
+//         lane d = fmaf(u[c], h[c], d) from 0 over its columns ascending, then the butterfly ^ 32 .. ^ 1).
+//         phase 2, pooled row r with entries e in CSR order: f_e = lrelu(ds[col[e] - r0] + dd[r - r0], slope1), lrelu(s) = s > 0 ? s :
+//         slope1 * s; m = max_e f_e; p_e = expf(f_e - m); from 0, over the entries in CSR order, ONE chain (no wave partials, no online
+//         rescaling): l = l + p_e, g[c] = fmaf(p_e, h_{col[e]}[c], g[c]); G[j][c] = g[c] * (1 / l).  A pooled row without entries gives
+//         zeros.  The sum differs from gat_query_hops_kernel's g_q only by that order (and by the one maximum in place of four running ones).
+//   tail  graph_query_tail_kernel's, unchanged.
+
+// One workgroup of four waves per graph, every wave on whole rows of H <= 256 NS columns (a score is a dot over all of H: no column
+// slabs).  Phase 1: the graph's rows dealt round-robin to the waves, each h_r into the window hs [r1 - r0][H] (a wave writes and later
+// reads 64 consecutive float4 per slot, every bank once), lane 0 stores the row's two dots into ds / dd [max_rows] behind the window.
+// One barrier, then phase 2: the graph's pooled rows dealt round-robin to the waves; a wave fetches the row's entries 64 at a time --
+// a lane reads ds of its entry (one scalar LDS read per lane) -- and broadcasts (window row, weight) by v_readlane.
+template <int NS>
+__global__ __launch_bounds__(256) void gat_graph_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                                   const float *__restrict__ T, int64_t ldt, const int32_t *__restrict__ xrow,
+                                                                   const float *__restrict__ a_src0, const float *__restrict__ a_dst0,
+                                                                   const float *__restrict__ b0, float slope0, const float *__restrict__ u_src,
+                                                                   const float *__restrict__ u_dst, float slope1,
+                                                                   const int64_t *__restrict__ seg, const int64_t *__restrict__ prow,
+                                                                   const int64_t *__restrict__ pptr, int32_t H, int32_t max_rows,
+                                                                   float *__restrict__ G, int64_t ldg) {
+    extern __shared__ float4 hs4[];
+    float *hs = reinterpret_cast<float *>(hs4);
+    float *ds = hs + (size_t)max_rows * H;  // the window was sized for max_rows
+    float *dd = ds + max_rows;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gi = blockIdx.x;
+    const int r0 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi]), r1 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi + 1]);
+    if (r1 - r0 > max_rows) return;  // workgroup-uniform
+    bool live[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) live[s] = s * 256 + lane * 4 < H;  // H % 4 == 0: a live lane owns four whole columns
+    {
+        const float *Tc[NS];
+        float4 bias[NS], us[NS], ud[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int c = s * 256 + lane * 4;
+            Tc[s] = T + (live[s] ? c : 0);
+            bias[s] = us[s] = ud[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live[s]) {
+                if (b0) bias[s] = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+                us[s] = *reinterpret_cast<const float4 *>(u_src + c);
+                ud[s] = *reinterpret_cast<const float4 *>(u_dst + c);
+            }
+        }
+        for (int r = r0 + w; r < r1; r += kHopsWaves) {
+            float4 h[NS];
+            gat_row<NS>(rowptr, col, Tc, ldt, xrow, a_src0, a_dst0, slope0, bias, r, lane, h);
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (live[s]) *reinterpret_cast<float4 *>(hs + (size_t)(r - r0) * H + s * 256 + lane * 4) = h[s];
+            const float s_r = row_dot<NS>(us, h), d_r = row_dot<NS>(ud, h);
+            if (lane == 0) {
+                ds[r - r0] = s_r;
+                dd[r - r0] = d_r;
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t p1 = pptr[gi + 1];
+    for (int64_t j = pptr[gi] + w; j < p1; j += kHopsWaves) {
+        const int r = __builtin_amdgcn_readfirstlane((int)prow[j]);
+        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+        const float dr = dd[r - r0];
+        float mx = -INFINITY;
+        for (int base = n0 + lane; base < n1; base += 64) mx = fmaxf(mx, lrelu1(ds[col[base] - r0] + dr, slope1));
+        mx = wave_max(mx);
+        float l = 0.f;
+        float4 g[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) g[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = n0; base < n1; base += 64) {
+            const int cnt = min(64, n1 - base);
+            int my = 0, mv = 0;
+            if (lane < cnt) {
+                my = col[base + lane] - r0;
+                mv = __float_as_int(expf(lrelu1(ds[my] + dr, slope1) - mx));
+            }
+            for (int k = 0; k < cnt; ++k) {
+                const int node = __builtin_amdgcn_readlane(my, k);
+                const float wv = __int_as_float(__builtin_amdgcn_readlane(mv, k));
+                l += wv;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    if (live[s]) {
+                        const float4 h = *reinterpret_cast<const float4 *>(hs + (size_t)node * H + s * 256 + lane * 4);
+                        g[s].x = fmaf(wv, h.x, g[s].x);
+                        g[s].y = fmaf(wv, h.y, g[s].y);
+                        g[s].z = fmaf(wv, h.z, g[s].z);
+                        g[s].w = fmaf(wv, h.w, g[s].w);
+                    }
+                }
+            }
+        }
+        const float inv = n1 > n0 ? 1.f / l : 0.f;  // l >= 1: the row's largest score gives expf(0)
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            if (live[s])
+                *reinterpret_cast<float4 *>(G + j * ldg + s * 256 + lane * 4) = make_float4(g[s].x * inv, g[s].y * inv, g[s].z * inv, g[s].w * inv);
+    }
+}
+
 }  // namespace
 
 extern "C" int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
@@ -1393,4 +1507,40 @@ extern "C" int fitgnn_gin_graph_query_tail_f32(const float *G, int64_t ldg, cons
     hipLaunchKernelGGL(gin_graph_query_tail_kernel, dim3((unsigned)Q), dim3(256), lds, (hipStream_t)stream, G, ldg, pptr, W1a, b1a, W1b, b1b, Wl,
                        bl, K, H2a, H2b, C, pool, softmax, out, ldo);
     return (int)hipGetLastError();
+}
+
+extern "C" size_t fitgnn_gat_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H) {
+    if (max_rows < 0 || H < 4) return 0;
+    return (size_t)max_rows * ((size_t)H + 2) * sizeof(float);
+}
+
+template <int NS>
+static int launch_gat_graph_hops(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                 const float *a_src0, const float *a_dst0, const float *b0, float slope0, const float *u_src,
+                                 const float *u_dst, float slope1, const int64_t *seg, const int64_t *prow, const int64_t *pptr, int32_t Q,
+                                 int32_t H, int32_t max_rows, float *G, int64_t ldg, size_t lds, hipStream_t stream) {
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)gat_graph_query_hops_kernel<NS>, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL((gat_graph_query_hops_kernel<NS>), dim3((unsigned)Q), dim3(256), lds, stream, rowptr, col, T, ldt, xrow, a_src0, a_dst0,
+                       b0, slope0, u_src, u_dst, slope1, seg, prow, pptr, H, max_rows, G, ldg);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_gat_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                               const float *a_src0, const float *a_dst0, const float *b0, float slope0, const float *u_src,
+                                               const float *u_dst, float slope1, const int64_t *seg, const int64_t *prow,
+                                               const int64_t *pptr, int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg,
+                                               void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || H > 512 || max_rows < 0 || ldt < H || ldg < H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_gat_graph_query_hops_lds_bytes(max_rows, H);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // the largest graph's layer-0 rows and their dots do not fit LDS
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !T || !a_src0 || !a_dst0 || !u_src || !u_dst || !seg || !prow || !pptr || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G | (uintptr_t)u_src | (uintptr_t)u_dst) % 16) != 0) return FITGNN_E_ALIGN;
+    const hipStream_t st = (hipStream_t)stream;
+    return H <= 256 ? launch_gat_graph_hops<1>(rowptr, col, T, ldt, xrow, a_src0, a_dst0, b0, slope0, u_src, u_dst, slope1, seg, prow, pptr, Q, H,
+                                               max_rows, G, ldg, lds, st)
+                    : launch_gat_graph_hops<2>(rowptr, col, T, ldt, xrow, a_src0, a_dst0, b0, slope0, u_src, u_dst, slope1, seg, prow, pptr, Q, H,
+                                               max_rows, G, ldg, lds, st);
 }

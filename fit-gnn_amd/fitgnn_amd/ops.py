@@ -1277,24 +1277,64 @@ def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=No
     return G
 
 
-def gat_query_supported(model):
-    """fitgnn_gat_query_gather_f32 and the tail answer for `model`: exactly two GATConv layers and a head, hidden sizes multiples of
-    16 with the first at most 512 (a wave holds a whole layer-0 row), a head the tail's LDS holds, contiguous float32 parameters on
-    the GPU."""
+def _gat_query_shapes(model):
+    """(H2, C) when `model` is exactly two GATConv layers and a head with hidden sizes multiples of 16, the first at most 512 (a wave
+    holds a whole layer-0 row), and contiguous float32 parameters on the GPU; None otherwise.  The callers add their tail's LDS bound."""
     from . import nn as fnn
     convs = list(getattr(model, "conv", ()))
     lt1 = getattr(model, "lt1", None)
     if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GATConv for c in convs):
-        return False
+        return None
     W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
     att = [convs[0].att_src, convs[0].att_dst, convs[1].att_src, convs[1].att_dst]
     params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias] + att
     if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
-        return False
+        return None
     H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
-    return (H % 16 == 0 and H <= 512 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
-            and att[0].numel() == H and att[1].numel() == H and att[2].numel() == H2 and att[3].numel() == H2
-            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+    ok = (H % 16 == 0 and H <= 512 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+          and att[0].numel() == H and att[1].numel() == H and att[2].numel() == H2 and att[3].numel() == H2)
+    return (H2, C) if ok else None
+
+
+def gat_query_supported(model):
+    """fitgnn_gat_query_gather_f32 and the tail answer for `model`: exactly two GATConv layers and a head, hidden sizes multiples of
+    16 with the first at most 512 (a wave holds a whole layer-0 row), a head the tail's LDS holds, contiguous float32 parameters on
+    the GPU."""
+    shapes = _gat_query_shapes(model)
+    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes) <= 160 * 1024
+
+
+def gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, max_rows, xrow=None, b0=None, slope0=0.2,
+                         slope1=0.2, out=None):
+    """G [P, H]: row j = the layer-1 attention aggregation (before its Linear) of view row prow[j] over its graph's layer-0 GAT rows,
+    each formed once in LDS with its two score dots from T = X W0^T (fitgnn_gat_graph_query_hops_f32).  a_src0 / a_dst0, u_src / u_dst:
+    as gat_query_gather's.  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled rows, graph i's at
+    pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int, at most gat_graph_query_max_rows(H)).  The
+    caller checks that prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
+    _lib.require_cuda(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, xrow, b0)
+    Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1])
+    G = out if out is not None else torch.empty((P, H), dtype=torch.float32, device=T.device)
+    if P == 0:
+        return G
+    _lib.check(_lib.lib().fitgnn_gat_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(T), T.stride(0), _lib.dptr(xrow),
+                                                          _lib.dptr(a_src0), _lib.dptr(a_dst0), _lib.dptr(b0), float(slope0),
+                                                          _lib.dptr(u_src), _lib.dptr(u_dst), float(slope1), _lib.dptr(seg), _lib.dptr(prow),
+                                                          _lib.dptr(pptr), Q, H, int(max_rows), _lib.dptr(G), G.stride(0),
+                                                          _lib.stream_ptr(T.device)), "fitgnn_gat_graph_query_hops_f32")
+    return G
+
+
+def gat_graph_query_max_rows(H):
+    """The largest graph (rows) whose layer-0 rows and score dots fitgnn_gat_graph_query_hops_f32 holds in LDS at hidden size H."""
+    per_row = int(_lib.lib().fitgnn_gat_graph_query_hops_lds_bytes(1, int(H)))
+    return (160 * 1024) // per_row if per_row > 0 else 0
+
+
+def gat_graph_query_supported(model):
+    """fitgnn_gat_graph_query_hops_f32 and the graph tail answer for `model`: gat_query_supported's conditions with the graph tail's
+    LDS bound in place of the node tail's."""
+    shapes = _gat_query_shapes(model)
+    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes) <= 160 * 1024
 
 
 def sage_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):

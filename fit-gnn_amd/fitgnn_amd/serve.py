@@ -70,6 +70,22 @@ whose rows are all pooled, where the window forms each ONCE:
 The window shares LDS with the product's two stages: ops.gin_graph_query_max_rows(Ha, Hb) rows, about 90 at 512 / 512 and about 450 at
 64 / 64.  A larger graph's pooled rows take ops.gin_query_hops (the same s_r), into the same G in front of the one tail.  The path is
 opt-in, as on the node engine; without the flag, and for any GIN model the kernels do not take, the model's own forward answers.
+
+With gat_kernels=True a model of two GATConv layers (heads = 1) takes one launch of its own over the view's "gat" CSR (existing self
+loops removed, one added per row) in front of the GCN graph tail, unchanged (sum beta = 1, as on the node engine).  The per-row kernel
+(ops.gat_query_gather) re-forms h_j -- a softmax over row j and a gather of deg(j) table rows -- and its H-long score dot once per
+entry that reaches j, sum_r (deg(r) + 1) layer-0 rows per graph; the window forms each ONCE and keeps its two dots beside it, so a
+layer-1 score is two LDS scalar reads and an add:
+
+    T, a0s, a0d, u_s, u_d                                               as on the node engine, once per set of the six weights
+    h_r   = ELU(sum_k alpha_rk T[k] + b0)                               EVERY row r of the graph, formed once, in LDS
+    ds_r  = u_s . h_r,  dd_r = u_d . h_r                                EVERY row r of the graph, behind the window
+    g_r   = sum_j beta_j h_j,  beta = softmax_j lrelu(ds_j + dd_r, slope1)   r among the graph's pooled rows   ops.gat_graph_query_hops
+    out   = Wl pool_r ELU(W1 g_r + b1) + bl   (softmax)                                                       ops.gcn_graph_query_tail
+
+A wave holds a whole row (a score is a dot over all of H), so the window's row is H floats: ops.gat_graph_query_max_rows(H) rows, 79 at
+hidden 512 and 620 at 64.  A larger graph's pooled rows take ops.gat_query_gather (the same g_r up to the summation order), into the
+same G in front of the one tail.  Opt-in, as the node engine's switch is.
 """
 import numpy as np
 import torch
@@ -100,6 +116,30 @@ def first_missing(table, node_ids):
     ok[inside] = table[ids[inside]] >= 0
     bad = np.nonzero(~ok)[0]
     return None if bad.size == 0 else int(ids[bad[0]])
+
+
+def gat_prepared_state(T, ws):
+    """The GAT paths' state made from T = X W0^T and the six weights ws = [W0, att_src0, att_dst0, W1, att_src1, att_dst1]:
+    ([(tensor, version)] of ws, a0s, a0d, u_s, u_d) with a0s / a0d = T att0 per table row (fitgnn_gat_scores_f32) and u = W1^T att1,
+    formed in float64 and rounded once.  Both engines call it."""
+    from . import _lib
+    W0, as0, ad0, W1, as1, ad1 = ws
+    n, H = T.shape
+    with torch.no_grad():
+        a0s = torch.empty(n, dtype=torch.float32, device=T.device)
+        a0d = torch.empty(n, dtype=torch.float32, device=T.device)
+        as0, ad0 = as0.detach().reshape(-1).contiguous(), ad0.detach().reshape(-1).contiguous()
+        _lib.check(_lib.lib().fitgnn_gat_scores_f32(_lib.dptr(T), T.stride(0), n, H, _lib.dptr(as0), _lib.dptr(ad0), _lib.dptr(a0s),
+                                                    _lib.dptr(a0d), _lib.stream_ptr(T.device)), "fitgnn_gat_scores_f32")
+        W1d = W1.detach().double()
+        u_s = (as1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
+        u_d = (ad1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
+    return ([(w, w._version) for w in ws], a0s, a0d, u_s, u_d)
+
+
+def _gat_weights(model):
+    c0, c1 = model.conv
+    return [c0.lin.weight, c0.att_src, c0.att_dst, c1.lin.weight, c1.att_src, c1.att_dst]
 
 
 class QueryEngine:
@@ -190,24 +230,11 @@ class QueryEngine:
         return self
 
     def _gat_weights(self):
-        c0, c1 = self.model.conv
-        return [c0.lin.weight, c0.att_src, c0.att_dst, c1.lin.weight, c1.att_src, c1.att_dst]
+        return _gat_weights(self.model)
 
     def _refresh_gat(self, T):
-        """a0s / a0d = T att0 per table row (fitgnn_gat_scores_f32); u = W1^T att1, formed in float64 and rounded once."""
-        from . import _lib
-        W0, as0, ad0, W1, as1, ad1 = ws = self._gat_weights()
-        n, H = T.shape
-        with torch.no_grad():
-            a0s = torch.empty(n, dtype=torch.float32, device=T.device)
-            a0d = torch.empty(n, dtype=torch.float32, device=T.device)
-            as0, ad0 = as0.detach().reshape(-1).contiguous(), ad0.detach().reshape(-1).contiguous()
-            _lib.check(_lib.lib().fitgnn_gat_scores_f32(_lib.dptr(T), T.stride(0), n, H, _lib.dptr(as0), _lib.dptr(ad0), _lib.dptr(a0s),
-                                                        _lib.dptr(a0d), _lib.stream_ptr(T.device)), "fitgnn_gat_scores_f32")
-            W1d = W1.detach().double()
-            u_s = (as1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
-            u_d = (ad1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
-        self._gat = ([(w, w._version) for w in ws], a0s, a0d, u_s, u_d)
+        """a0s / a0d = T att0 per table row; u = W1^T att1 (gat_prepared_state)."""
+        self._gat = gat_prepared_state(T, self._gat_weights())
 
     def _gat_state(self):
         """(T, a0s, a0d, u_s, u_d), remade when the storage or version of any of the six weights has changed."""
@@ -371,13 +398,14 @@ class GraphQueryEngine:
     row: they do not take "gs").  max_window_rows: graphs with more rows than this -- or than the hops kernel's LDS window holds at the
     model's hidden size -- are answered through the per-row gather inside the same call.  gin_kernels: a model of two GINConv layers
     with the reference's two-Linear ReLU MLP is answered by the GIN graph-query pair (off by default, as QueryEngine's switch is); it
-    changes nothing for any other model.
+    changes nothing for any other model.  gat_kernels: the same switch for a model of two GATConv layers (heads = 1): the attention
+    window launch in front of the GCN graph tail.
 
-    The view's CSR, the per-graph pointers and the index of pooled rows are built here, once.  Any model the two kernels do not
-    take (ops.graph_query_supported, ops.gin_graph_query_supported behind gin_kernels) is answered by its own forward on
-    gset.batch_ids(the unique ids, view)."""
+    The view's CSR, the per-graph pointers and the index of pooled rows are built here, once.  Any model the kernels do not
+    take (ops.graph_query_supported, ops.gin_graph_query_supported behind gin_kernels, ops.gat_graph_query_supported behind
+    gat_kernels) is answered by its own forward on gset.batch_ids(the unique ids, view)."""
 
-    def __init__(self, model, gset, view=None, max_window_rows=None, gin_kernels=False):
+    def __init__(self, model, gset, view=None, max_window_rows=None, gin_kernels=False, gat_kernels=False):
         from . import network
         gs_cls = (network.Classify_graph_gs, network.Regress_graph_gs)
         gc_cls = (network.Classify_graph_gc, network.Regress_graph_gc)
@@ -396,6 +424,7 @@ class GraphQueryEngine:
         self.classify = isinstance(model, (network.Classify_graph_gs, network.Classify_graph_gc))
         self.max_window_rows = None if max_window_rows is None else int(max_window_rows)
         self.gin_kernels = bool(gin_kernels)
+        self.gat_kernels = bool(gat_kernels)
         ptr, x, mask = {"gs": (gset.gs_ptr, gset.gs_x, gset.gs_mask), "gc": (gset.cluster_ptr, gset.gc_x, None),
                         "orig": (gset.node_ptr, gset.x, None)}[view]
         ptr = np.asarray(ptr, dtype=np.int64)
@@ -411,15 +440,19 @@ class GraphQueryEngine:
         self._prow, self._pp = prow, pp
         self._prow_host = prow.cpu().numpy()
         self._T = None          # (W0, W0._version, T): W0 = conv[0].lin.weight, on the GIN path conv[0].nn[0].weight
-        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gin" | None: the kernels that answer)
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "gin" | None: the kernels that answer)
         self._sum = None        # the view's sum CSR (the GIN path's pattern), looked up once
+        self._gat = None        # the GAT path's prepared state: ([(tensor, version)] of the six weights, a0s, a0d, u_s, u_d)
+        self._gat_graph = None  # the view's "gat" CSR (existing self loops removed, one added per row), looked up once
 
     def _kind(self):
-        """"gcn" (ops.graph_query_supported), "gin" (gin_kernels and ops.gin_graph_query_supported) or None, re-evaluated only when a
-        layer or a parameter's storage, type or shape has changed."""
+        """"gcn" (ops.graph_query_supported), "gat" (gat_kernels and ops.gat_graph_query_supported), "gin" (gin_kernels and
+        ops.gin_graph_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
+        if self.gat_kernels:
+            params += [getattr(c, a, None) for c in m.conv for a in ("att_src", "att_dst")]
         if self.gin_kernels:
             mlps = [getattr(c, "nn", None) for c in m.conv]
             subs = [list(n) if isinstance(n, torch.nn.Sequential) else [] for n in mlps]
@@ -427,7 +460,7 @@ class GraphQueryEngine:
             params += [type(l) for n in subs for l in n]     # an activation swapped in place changes no parameter
         key = tuple(type(c) for c in m.conv) + tuple((p.data_ptr(), p.dtype, p.shape) if torch.is_tensor(p) else p for p in params)
         if self._fused is None or self._fused[0] != key:
-            kind = "gcn" if ops.graph_query_supported(m) else None
+            kind = "gcn" if ops.graph_query_supported(m) else ("gat" if self.gat_kernels and ops.gat_graph_query_supported(m) else None)
             if kind is None and self.gin_kernels and ops.gin_graph_query_supported(m):
                 kind = "gin"
             self._fused = (key, kind)
@@ -443,14 +476,30 @@ class GraphQueryEngine:
         return conv0.nn[0].weight if self._kind() == "gin" else conv0.lin.weight
 
     def refresh(self):
-        """Remake T = X W0^T (on the GIN path X W0a^T, without the bias: the kernel adds it behind the aggregation) from the model's
-        current weights (done automatically when that weight's storage or version changes)."""
+        """Remake T = X W0^T (on the GIN path X W0a^T, without the bias: the kernel adds it behind the aggregation) and, on the GAT
+        path, the score vectors and W1^T att from the model's current weights (done automatically when the storage or version of a
+        weight they are made from changes)."""
         if self.fused:
             W0 = self._w0()
             with torch.no_grad():
                 T = ops.Linear.apply(self.x.float(), W0, self.model.op_config).contiguous()
             self._T = (W0, W0._version, T)
+            if self._kind() == "gat":
+                self._gat = gat_prepared_state(T, _gat_weights(self.model))
         return self
+
+    def _gat_state(self):
+        """(T, a0s, a0d, u_s, u_d), remade when the storage or version of any of the six weights has changed."""
+        ws = _gat_weights(self.model)
+        if self._gat is None or not all(ops._same_index(e, w) for e, w in zip(self._gat[0], ws)) or not ops._same_index(self._T, ws[0]):
+            self.refresh()
+        return (self._T[2],) + tuple(self._gat[1:])
+
+    def _gat_csr(self):
+        """The view's "gat" CSR (rows = targets, existing self loops removed, one added per row): nn.GATConv.forward's own lookup."""
+        if self._gat_graph is None:
+            self._gat_graph = csr_for(self._whole["edge_index"], self.n_rows, "gat")
+        return self._gat_graph
 
     def _table(self):
         if not ops._same_index(self._T, self._w0()):
@@ -465,9 +514,13 @@ class GraphQueryEngine:
 
     @property
     def table_bytes(self):
-        """Bytes of T -- [n_rows, Ha] on the GIN path -- (0 when the model's own forward answers: it keeps none)."""
+        """Bytes of T -- [n_rows, Ha] on the GIN path -- and of the two score vectors on the GAT path (0 when the model's own forward
+        answers: it keeps none)."""
         if not self.fused:
             return 0
+        if self._kind() == "gat":
+            T, a0s, a0d = self._gat_state()[:3]
+            return int(T.numel()) * T.element_size() + int(a0s.numel() + a0d.numel()) * a0s.element_size()
         T = self._table()
         return int(T.numel()) * T.element_size()
 
@@ -491,12 +544,15 @@ class GraphQueryEngine:
 
     def _predict_fused(self, ids, cnt):
         m, dev = self.model, self.x.device
-        gin = self._kind() == "gin"
-        f = self._sum_csr().f if gin else self.graph.f
+        gin, gat = self._kind() == "gin", self._kind() == "gat"
+        f = self._sum_csr().f if gin else self._gat_csr().f if gat else self.graph.f
         C = int(m.lt1.weight.shape[0])
         if ids.size == 0:
             return torch.empty((0, C), dtype=torch.float32, device=dev)
-        T = self._table()
+        if gat:
+            T, a0s, a0d, u_s, u_d = self._gat_state()
+        else:
+            T = self._table()
         Q = int(ids.size)
         # the launch's index arrays are made on the host, where the ids and the pointers are, and go up in ONE copy: no device glue
         pptr_h = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
@@ -515,8 +571,9 @@ class GraphQueryEngine:
             limit = ops.gin_graph_query_max_rows(int(T.shape[1]), Hg)
         else:
             Hg = int(T.shape[1])
-            limit = ops.graph_query_max_rows(Hg)
+            limit = ops.gat_graph_query_max_rows(Hg) if gat else ops.graph_query_max_rows(Hg)
             b0 = m.conv[0].bias
+            slopes = dict(slope0=m.conv[0].negative_slope, slope1=m.conv[1].negative_slope) if gat else None
         if self.max_window_rows is not None:
             limit = min(limit, self.max_window_rows)
         large = n_rows > limit
@@ -527,6 +584,8 @@ class GraphQueryEngine:
             if gin:
                 ops.gin_graph_query_hops(f.rowptr, f.col, f.val, T, eps0, l0b.weight, l0b.bias, eps1, seg, prow, pptr, window,
                                          b0a=l0a.bias, out=G)
+            elif gat:
+                ops.gat_graph_query_hops(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, seg, prow, pptr, window, b0=b0, out=G, **slopes)
             else:
                 ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, window, b0=b0, out=G)
         if large.any():   # the per-row kernel: correct for any size, the view being block-diagonal
@@ -534,6 +593,8 @@ class GraphQueryEngine:
             rows = prow.index_select(0, pos)
             if gin:
                 G.index_copy_(0, pos, ops.gin_query_hops(f.rowptr, f.col, f.val, T, eps0, l0b.weight, l0b.bias, eps1, rows, b0a=l0a.bias))
+            elif gat:
+                G.index_copy_(0, pos, ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, rows, b0=b0, **slopes))
             else:
                 G.index_copy_(0, pos, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, b0=b0))
         if gin:

@@ -11,7 +11,8 @@ bracketed by a device synchronisation (the reference's time() around an asynchro
 Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN in its Net1, inference.py:22-50), --query_engine
 (opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows -- each sampled graph of the graph-level tasks by
 fitgnn_amd.serve.GraphQueryEngine.predict -- inside the same timing bracket; same CSV row),
---query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel), --query_sage (with
+--query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel; on graph_cls / graph_reg
+by the GAT graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_sage (with
 --query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel), --query_gin (with --query_engine: a
 two-layer GINConv model is answered by the GIN query kernels; on graph_cls / graph_reg by the GIN graph-query kernels, the baseline
 under --baseline included).
@@ -80,7 +81,9 @@ def build_parser():
                         "on the graph cut out of the set -- the FIT-GNN model and, with --baseline, the baseline on the uncoarsened graphs")
     p.add_argument('--query_attention', action='store_true',
                    help="with --query_engine: a --layer_name GATConv model of two layers is answered by the attention query kernel "
-                        "(QueryEngine(gat_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
+                        "(QueryEngine(gat_kernels=True)) instead of the per-subgraph forward; graph_cls / graph_reg: by the GAT graph-query "
+                        "kernel (GraphQueryEngine(gat_kernels=True): every attention row of a graph and its two score dots formed once, in "
+                        "LDS) instead of the model's own forward, the baseline under --baseline included; ignored without --query_engine")
     p.add_argument('--query_sage', action='store_true',
                    help="with --query_engine: a --layer_name SAGEConv model of two layers is answered by the mean-aggregation query kernel "
                         "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
@@ -140,7 +143,7 @@ def graph_inference(args, mol):
         engine = None
         if args.query_engine:   # built outside the timed region, as the per-graph CSR is below; T = X W0^T is made here too
             from fitgnn_amd.serve import GraphQueryEngine
-            engine = GraphQueryEngine(model, gset, view=kind, gin_kernels=args.query_gin).refresh()
+            engine = GraphQueryEngine(model, gset, view=kind, gin_kernels=args.query_gin, gat_kernels=args.query_attention).refresh()
         with torch.no_grad():
             for g in ids:
                 if engine is not None:

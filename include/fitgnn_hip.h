@@ -758,6 +758,32 @@ int fitgnn_gin_graph_query_tail_f32(const float *G, int64_t ldg, const int64_t *
                                     const float *W1b, const float *b1b, const float *Wl, const float *bl, int32_t K, int32_t H2a,
                                     int32_t H2b, int32_t C, int32_t pool, int32_t softmax, float *out, int64_t ldo, void *stream);
 
+/* Two GATConv layers (heads = 1) have a first launch of their own in front of fitgnn_gcn_graph_query_tail_f32, unchanged (sum beta = 1,
+ * so W1 (sum beta h) + b1 is conv1's output).  G[j][:] = g_{prow[j]} for every pooled row of every queried graph, over
+ * T = X W0^T [n_table x H] (row stride ldt), t(r) = xrow ? xrow[r] : r:
+ *   h_r  = ELU(sum_k alpha_rk T[t(k)] + b0),  alpha_r. = softmax over CSR row r of LeakyReLU(a_src0[t(k)] + a_dst0[t(r)], slope0)
+ *   ds_r = u_src . h_r,  dd_r = u_dst . h_r                                          for EVERY row r of graph i's range [seg[i][0], seg[i][1]),
+ *   g_r  = sum_j beta_j h_j,  beta = softmax over CSR row r of LeakyReLU(ds_j + dd_r, slope1)     for r = prow[j], pptr[i] <= j < pptr[i + 1],
+ * with a_src0 / a_dst0 the layer-0 score dots per TABLE row (fitgnn_gat_scores_f32 on T) and u_src = W1^T att_src1, u_dst = W1^T att_dst1
+ * [H].  fitgnn_gat_query_gather_f32 on the same rows forms h_j (and its dot) once per entry that reaches j: sum_r (deg(r) + 1) layer-0
+ * rows instead of seg[i][1] - seg[i][0].  One workgroup of four waves per graph, a wave on whole rows (H <= 512, no column slabs).
+ * Phase 1: the graph's rows dealt round-robin to the waves, each h_r (bit-equal to fitgnn_gat_query_gather_f32's) into an LDS window
+ * of row stride H, its two dots into two float arrays behind the window.  After one barrier the graph's pooled rows are dealt
+ * round-robin to the waves: a two-pass max-subtracted softmax with expf over the row's entries, the weighted sum ONE fmaf chain in CSR
+ * order, scaled once by 1 / l.  No atomics: two launches give the same bits (operation order: csrc/query.hip).  A row without entries
+ * gives h_r = ELU(b0); a pooled row without entries zeros.  seg (int64 [Q][2]) may repeat graphs and needs no order; prow (int64, rows
+ * of the view) lists graph i's pooled rows inside its range; pptr is int64 [Q + 1].  The kernel cannot check that prow and col stay
+ * inside the graph's range: the caller does.  max_rows: the host-known largest seg[i][1] - seg[i][0] (a graph with more rows is
+ * skipped: its rows of G are not written).  Dynamic LDS: fitgnn_gat_graph_query_hops_lds_bytes(max_rows, H) = max_rows * (H + 2) * 4
+ * bytes (79 rows at H = 512, 620 at H = 64).  xrow, b0 may be NULL.  Writes G[0..pptr[Q]) x [0..H) only.  Requires 4 <= H <= 512,
+ * H % 4 == 0, max_rows >= 0, ldt, ldg >= H and the LDS at most 160 KiB (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G, u_src,
+ * u_dst 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_gat_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H);
+int fitgnn_gat_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                    const float *a_src0, const float *a_dst0, const float *b0, float slope0, const float *u_src,
+                                    const float *u_dst, float slope1, const int64_t *seg, const int64_t *prow, const int64_t *pptr,
+                                    int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg, void *stream);
+
 /* =====================================================================================
  * Coarsen half: one contraction level of variation_neighborhoods
  * replaces: graph_coarsening/coarsening_utils.py contract_variation_linear :530-650,

@@ -23,15 +23,16 @@ Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>
                          fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded).
 
-    python tools/query_latency.py --task graph_reg | graph_cls [--layer GINConv] [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512]
+    python tools/query_latency.py --task graph_reg | graph_cls [--layer GINConv | GATConv] [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512]
                                   [--samples 256] [--rounds 5] [--batch 1024] [--out FILE]
 
 --task graph_reg / graph_cls: one GRAPH query through fitgnn_amd.serve.GraphQueryEngine (fitgnn_gcn_graph_query_hops_f32 and
 fitgnn_gcn_graph_query_tail_f32) against the per-graph forward inference.py times without --query_engine, on a GraphSet of
 graph_data.synthetic_molecules (graph_reg: Regress_graph_gs / _gc) or synthetic_graph_classes (graph_cls: Classify_graph_gs / _gc),
 extra-node layout.  --layer GINConv: a two-layer GIN model through GraphQueryEngine(gin_kernels=True)
-(fitgnn_gin_graph_query_hops_f32 over the sum CSR and fitgnn_gin_graph_query_tail_f32).  Writes
-profiles/query_latency_<task>_<view>.json (profiles/query_latency_<task>_<view>_GINConv.json with --layer GINConv; or --out):
+(fitgnn_gin_graph_query_hops_f32 over the sum CSR and fitgnn_gin_graph_query_tail_f32).  --layer GATConv: a two-layer GAT model through
+GraphQueryEngine(gat_kernels=True) (fitgnn_gat_graph_query_hops_f32 over the "gat" CSR and fitgnn_gcn_graph_query_tail_f32).  Writes
+profiles/query_latency_<task>_<view>.json (profiles/query_latency_<task>_<view>_<layer>.json with --layer GINConv / GATConv; or --out):
   (a) engine_single      predict([g]) per sampled graph, bracketed as above;
   (b) graph_forward      the model on the graph cut out of the set (gset.batch(g, g + 1, view), its CSR and pool index pre-built),
                          measured twice per graph around the engine's turn, after one untimed pass;
@@ -41,7 +42,11 @@ profiles/query_latency_<task>_<view>.json (profiles/query_latency_<task>_<view>_
                          row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio;
   dense_rows             --layer GINConv, counted, not timed: the layer-0 rows that take the dense Hb x Ha product -- every row of the
                          view once (the window path) against sum over the pooled rows r of deg(r) + 1 (fitgnn_gin_query_hops_f32 on
-                         every pooled row), and their ratio."""
+                         every pooled row), and their ratio;
+  attention_rows         --layer GATConv, counted, not timed: the layer-0 attention rows formed (a softmax, a gather and two score dots
+                         each) -- every row of the view once (the window path) against sum over the pooled rows r of deg(r) + 1
+                         (fitgnn_gat_query_gather_f32 on every pooled row, with one h_q per wave that has entries counted once), and
+                         their ratio."""
 import argparse
 import json
 import os
@@ -250,14 +255,15 @@ def graph_main(a):
     gs = a.view == "gs"
     cls = ("Regress_graph_" if reg else "Classify_graph_") + ("gs" if gs else "gc")
     C = 1 if reg else int(mol["y"].max()) + 1
-    if a.layer not in ("GCNConv", "GINConv"):
-        raise SystemExit("--task graph_reg / graph_cls takes --layer GCNConv or GINConv")
-    gin = a.layer == "GINConv"
+    if a.layer not in ("GCNConv", "GINConv", "GATConv"):
+        raise SystemExit("--task graph_reg / graph_cls takes --layer GCNConv, GINConv or GATConv")
+    gin, gat = a.layer == "GINConv", a.layer == "GATConv"
     margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=int(gset.x.shape[1]), hidden=a.hidden, num_classes=C)
     torch.manual_seed(2)
     model = getattr(network, cls)(margs).to(dev).eval()
-    engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin)
-    assert engine.fused and (ops.gin_graph_query_supported(model) if gin else ops.graph_query_supported(model))
+    engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin, gat_kernels=gat)
+    assert engine.fused and (ops.gin_graph_query_supported(model) if gin else ops.gat_graph_query_supported(model) if gat
+                             else ops.graph_query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -322,7 +328,7 @@ def graph_main(a):
         t_whole = timed(lambda: call(whole))
 
     # counted: table rows read by the per-row gather on every pooled row against every layer-0 row formed once
-    f = engine._sum_csr().f if gin else engine.graph.f
+    f = engine._sum_csr().f if gin else engine._gat_csr().f if gat else engine.graph.f
     deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
     csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
     csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)
@@ -353,7 +359,13 @@ def graph_main(a):
                                  ratio=round(per_row_dense / max(int(engine.n_rows), 1), 3),
                                  window_rows=int(ops.gin_graph_query_max_rows(a.hidden, a.hidden)),
                                  largest_graph_rows=int(np.diff(engine._ptr).max()))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_GINConv' if gin else ''}.json")
+    if gat:
+        per_row_att = int(deg[prow].sum()) + int(prow.numel())
+        res["attention_rows"] = dict(per_row_gather=per_row_att, each_row_once=int(engine.n_rows),
+                                     ratio=round(per_row_att / max(int(engine.n_rows), 1), 3),
+                                     window_rows=int(ops.gat_graph_query_max_rows(a.hidden)),
+                                     largest_graph_rows=int(np.diff(engine._ptr).max()))
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_' + a.layer if gin or gat else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
