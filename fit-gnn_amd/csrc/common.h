@@ -32,6 +32,29 @@ __host__ __device__ __forceinline__ bool dropout_keep(uint64_t bits, int sub, ui
     return (uint32_t)((bits >> (16 * sub)) & 0xFFFFull) >= thresh;
 }
 
+// The keep decision of ONE element idx = row*H + col, for a thread that owns a single element of the group of four: only the 32-bit
+// half of dropout_bits(seed, idx >> 2) that holds the element's 16 bits is hashed.  Same decision as dropout_keep on the whole hash.
+__host__ __device__ __forceinline__ bool dropout_keep_elem(uint64_t seed, uint64_t idx, uint32_t thresh) {
+    const uint64_t group = idx >> 2;
+    const int sub = (int)(idx & 3);
+    const uint32_t g = (uint32_t)group * 0x9E3779B1u + (uint32_t)(group >> 32) * 0x85EBCA77u;
+    const uint32_t half = (sub & 2) ? fmix32((g + 0x7F4A7C15u) ^ (uint32_t)(seed >> 32) ^ 0x68E31DA4u) : fmix32(g ^ (uint32_t)seed);
+    return ((half >> (16 * (sub & 1))) & 0xFFFFu) >= thresh;
+}
+
+// The forward store epilogue of one element (spmm.hip finish_row, gcn_ops.hip epilogue_fwd_rows_kernel: same flags, same arithmetic):
+// dropout(ELU(x + bias)); idx = row*H + col of the element whose dropout hash / mask entry it takes.  epi bits: 1 bias, 2 ELU, 4 dropout.
+__device__ __forceinline__ float finish_elem(float x, float bias, uint32_t epi, float keep_scale, uint32_t thresh, uint64_t seed,
+                                             const uint8_t *__restrict__ mask, uint64_t idx) {
+    float y = x + ((epi & 1u) ? bias : 0.f);
+    if (epi & 2u) y = y > 0.f ? y : __expf(y) - 1.0f;
+    if (epi & 4u) {
+        const bool keep = mask ? (mask[idx] != 0) : dropout_keep_elem(seed, idx, thresh);
+        y = keep ? y * keep_scale : 0.f;
+    }
+    return y;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 // Cache policy of the GCN step's once-touched HBM streams: a stream whose bit is set in FITGNN_NT_STREAMS is loaded / stored with the

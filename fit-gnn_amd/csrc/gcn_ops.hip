@@ -136,6 +136,49 @@ __global__ __launch_bounds__(256) void epilogue_bwd_kernel(const float *__restri
                     if (!HEAD) g[u][0] = dOut[base];
                 }
             }
+            if (HEAD) {
+                // dOut = dy @ Wl for the U rows together: the class loop outside, so one LDS read of s_w[c] feeds all U rows (a
+                // ds_read_b128 per class and U rows instead of one per class and row).  Each element's chain is still
+                // g = fmaf(d_c, w_c, g) from 0 over ascending c: the same bits.  Rows that are skipped (all-zero dy) or past the
+                // chunk get a value that is never used; a group of U skipped rows forms no products at all.
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) g[u][i] = 0.f;
+                bool any = false;
+#pragma unroll
+                for (int u = 0; u < U; ++u) any = any || nz[u];
+                if (any) {  // wave-uniform
+                    constexpr int CB = 4;   // classes per step: their LDS reads are in flight together, ahead of the products
+                    int c = 0;
+                    for (; c + CB <= C; c += CB) {
+                        float w[CB][VEC];
+#pragma unroll
+                        for (int k = 0; k < CB; ++k)
+#pragma unroll
+                            for (int i = 0; i < VEC; ++i) w[k][i] = s_w[(c + k) * SLAB + lane * VEC + i];
+#pragma unroll
+                        for (int k = 0; k < CB; ++k)
+#pragma unroll
+                            for (int u = 0; u < U; ++u) {
+                                const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dyl[u]), c + k));
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) g[u][i] = fmaf(d, w[k][i], g[u][i]);
+                            }
+                    }
+                    for (; c < C; ++c) {
+                        float w[VEC];
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) w[i] = s_w[c * SLAB + lane * VEC + i];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dyl[u]), c));
+#pragma unroll
+                            for (int i = 0; i < VEC; ++i) g[u][i] = fmaf(d, w[i], g[u][i]);
+                        }
+                    }
+                }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int row = row0 + 4 * u;
@@ -151,13 +194,6 @@ __global__ __launch_bounds__(256) void epilogue_bwd_kernel(const float *__restri
                     continue;
                 }
                 if (HEAD) {
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) g[u][i] = 0.f;
-                    for (int c = 0; c < C; ++c) {
-                        const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dyl[u]), c));
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) g[u][i] = fmaf(d, s_w[c * SLAB + lane * VEC + i], g[u][i]);
-                    }
                     if (CW > 0) {
 #pragma unroll
                         for (int c = 0; c < (CW > 0 ? CW : 1); ++c) {
@@ -283,20 +319,82 @@ __global__ __launch_bounds__(256) void sum_leading_kernel(const float4 *__restri
 // Column sums of a tall matrix with a few columns (the head's bias gradient, sum over rows of dy [rows x classes]):
 // block b sums rows [b * rows_per_block, ...) -- thread t takes rows t, t + 256, ... of the range, then a fixed tree
 // over the 256 threads -- into partial[b][C]; colsum_partials_kernel adds the blocks.  C <= kNarrowMaxC (ogbn-products: 47).
+//
+// A thread that walks its own 4 C-byte row makes every load instruction of a wavefront touch 64 rows; so the rows travel in tiles of
+// 256 through LDS (row_tile_* below): the tile's elements are loaded in flat order -- consecutive lanes, consecutive addresses --
+// into rows of an odd pitch, and thread t then reads row t of the tile from LDS (odd pitch: 64 lanes, 64 banks).  The sums and their
+// order are those of the row-walking form.
 constexpr int kNarrowMaxC = 64;
+constexpr int kRowTile = 256;      // rows of an LDS row tile = threads of the workgroups that use one
+constexpr int kRowTileBatch = 8;   // loads a thread has in flight while staging
+
+__host__ __device__ __forceinline__ int row_tile_pitch(int C) { return C | 1; }
+
+// e / C for 0 <= e < 2^23 and 1 <= C (inv = 1.0f / C): the float quotient is off by at most one
+__device__ __forceinline__ int row_tile_div(int e, int C, float inv) {
+    int q = (int)((float)e * inv);
+    q -= (q * C > e) ? 1 : 0;
+    q += ((q + 1) * C <= e) ? 1 : 0;
+    return q;
+}
+
+// tile[r * pitch + c] = src(r)[c] for r < nrows, c < C; src(r) is the address of row r's first element
+template <typename RowPtr>
+__device__ __forceinline__ void row_tile_load(float *tile, int nrows, int C, RowPtr src) {
+    const int P = row_tile_pitch(C), total = nrows * C;
+    const float inv = 1.0f / (float)C;
+    for (int e0 = threadIdx.x; e0 < total; e0 += kRowTile * kRowTileBatch) {
+        float v[kRowTileBatch];
+        int off[kRowTileBatch];
+#pragma unroll
+        for (int k = 0; k < kRowTileBatch; ++k) {
+            const int e = e0 + k * kRowTile;
+            if (e < total) {
+                const int r = row_tile_div(e, C, inv), c = e - r * C;
+                off[k] = r * P + c;
+                v[k] = src(r)[c];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kRowTileBatch; ++k)
+            if (e0 + k * kRowTile < total) tile[off[k]] = v[k];
+    }
+}
+
+// dst(r)[c] = tile[r * pitch + c]
+template <typename RowPtr>
+__device__ __forceinline__ void row_tile_store(const float *tile, int nrows, int C, RowPtr dst) {
+    const int P = row_tile_pitch(C), total = nrows * C;
+    const float inv = 1.0f / (float)C;
+    for (int e = threadIdx.x; e < total; e += kRowTile) {
+        const int r = row_tile_div(e, C, inv), c = e - r * C;
+        dst(r)[c] = tile[r * P + c];
+    }
+}
+
+// dynamic LDS: a row tile, then the 256 floats of the reduction tree
 __global__ __launch_bounds__(256) void narrow_colsum_kernel(const float *__restrict__ x, int64_t ldx, int32_t n_rows, int32_t C,
                                                             int32_t rows_per_block, float *__restrict__ partial) {
-    __shared__ float red[256];
+    extern __shared__ float narrow_lds[];
+    const int P = row_tile_pitch(C);
+    float *tile = narrow_lds, *red = narrow_lds + kRowTile * P;
     float acc[kNarrowMaxC];
 #pragma unroll
     for (int c = 0; c < kNarrowMaxC; ++c) acc[c] = 0.f;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(r0 + rows_per_block, n_rows);
-    for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) {
-        const float *xr = x + (int64_t)r * ldx;
+    for (int rt = r0; rt < r1; rt += kRowTile) {   // thread t: rows r0 + t, r0 + t + 256, ... in ascending order
+        const int nrows = min(kRowTile, r1 - rt);
+        const float *xt = x + (int64_t)rt * ldx;
+        row_tile_load(tile, nrows, C, [&](int r) { return xt + (int64_t)r * ldx; });
+        __syncthreads();
+        if ((int)threadIdx.x < nrows) {
+            const float *xr = tile + threadIdx.x * P;
 #pragma unroll
-        for (int c = 0; c < kNarrowMaxC; ++c)
-            if (c < C) acc[c] += xr[c];
+            for (int c = 0; c < kNarrowMaxC; ++c)
+                if (c < C) acc[c] += xr[c];
+        }
+        __syncthreads();
     }
     for (int c = 0; c < C; ++c) {
         float v = 0.f;
@@ -398,6 +496,23 @@ __global__ __launch_bounds__(256) void adam_flat_acc_kernel(float4 *__restrict__
 // NLLLoss(log_softmax(z)[idx], labels) (network.py:35 + run.py:341) and its gradient in one pass over the selected rows:
 //   part[block] = sum over the block's rows of (logsumexp(z_r) - z_r[label]) * scale,  dz[r] = (softmax(z_r) - onehot) * scale
 // dz is zero elsewhere (cleared by the launcher).  One thread per selected row; fixed-order block and grid reductions.
+// One selected row's arithmetic: zr -> the row's loss term; dr[c] (may be zr: every element is read before it is written)
+__device__ __forceinline__ float softmax_nll_row(const float *zr, float *dr, int C, int lab, float scale) {
+    float m = zr[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, zr[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(zr[c] - m);
+    const float lse = m + logf(se);
+    const float loss = (lse - zr[lab]) * scale;
+    for (int c = 0; c < C; ++c) dr[c] = (expf(zr[c] - lse) - (c == lab ? 1.f : 0.f)) * scale;
+    return loss;
+}
+
+// TILE: the workgroup's 256 rows are staged in an LDS row tile (row_tile_load: coalesced loads; a contiguous span when the selected
+// rows are consecutive and ldz == C), a thread works on its row there, in place, and the tile is written out the same way.
+// !TILE (C wider than kNllTileMaxC): every thread walks its row in global memory.
+constexpr int kNllTileMaxC = 128;   // 256 x 129 floats = 129 KB of LDS
+template <bool TILE>
 __global__ __launch_bounds__(256) void softmax_nll_kernel(const float *__restrict__ z, int64_t ldz, int32_t C,
                                                           const int64_t *__restrict__ idx, const int64_t *__restrict__ labels,
                                                           int32_t n, float scale, float *__restrict__ dz,
@@ -405,18 +520,23 @@ __global__ __launch_bounds__(256) void softmax_nll_kernel(const float *__restric
     __shared__ float red[256];
     const int t = blockIdx.x * 256 + threadIdx.x;
     float loss = 0.f;
-    if (t < n) {
+    if constexpr (TILE) {
+        extern __shared__ float nll_tile[];
+        __shared__ int64_t s_row[kRowTile];   // element offset of each selected row
+        const int nrows = min(kRowTile, n - (int)blockIdx.x * kRowTile);
+        if (t < n) s_row[threadIdx.x] = idx[t] * ldz;
+        __syncthreads();
+        row_tile_load(nll_tile, nrows, C, [&](int r) { return z + s_row[r]; });
+        __syncthreads();
+        if (t < n) {
+            float *zr = nll_tile + threadIdx.x * row_tile_pitch(C);
+            loss = softmax_nll_row(zr, zr, C, (int)labels[t], scale);
+        }
+        __syncthreads();
+        row_tile_store(nll_tile, nrows, C, [&](int r) { return dz + s_row[r]; });
+    } else if (t < n) {
         const int64_t r = idx[t];
-        const float *zr = z + r * ldz;
-        float m = zr[0];
-        for (int c = 1; c < C; ++c) m = fmaxf(m, zr[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(zr[c] - m);
-        const float lse = m + logf(se);
-        const int lab = (int)labels[t];
-        loss = (lse - zr[lab]) * scale;
-        float *dr = dz + r * ldz;
-        for (int c = 0; c < C; ++c) dr[c] = (expf(zr[c] - lse) - (c == lab ? 1.f : 0.f)) * scale;
+        loss = softmax_nll_row(z + r * ldz, dz + r * ldz, C, (int)labels[t], scale);
     }
     red[threadIdx.x] = loss;
     __syncthreads();
@@ -817,7 +937,14 @@ extern "C" int fitgnn_softmax_nll_f32(const float *z, int64_t ldz, int32_t n_row
     if (!z || !idx || !labels || !dz || !work) return FITGNN_E_BADARG;
     if (work_bytes < fitgnn_softmax_nll_workspace_bytes(n)) return FITGNN_E_WORKSPACE;
     const int blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(softmax_nll_kernel, dim3(blocks), dim3(256), 0, s, z, ldz, C, idx, labels, n, scale, dz, (float *)work);
+    if (C <= kNllTileMaxC) {
+        static std::atomic<uint64_t> lds_done{0};
+        if (const int rc = fitgnn_lds_limit_once((const void *)softmax_nll_kernel<true>, kRowTile * row_tile_pitch(kNllTileMaxC) * (int)sizeof(float), lds_done)) return rc;
+        hipLaunchKernelGGL(softmax_nll_kernel<true>, dim3(blocks), dim3(256), kRowTile * row_tile_pitch(C) * sizeof(float), s, z, ldz, C, idx,
+                           labels, n, scale, dz, (float *)work);
+    } else {
+        hipLaunchKernelGGL(softmax_nll_kernel<false>, dim3(blocks), dim3(256), 0, s, z, ldz, C, idx, labels, n, scale, dz, (float *)work);
+    }
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const float *)work, blocks, loss);
     return (int)hipGetLastError();
 }
@@ -891,7 +1018,10 @@ extern "C" int fitgnn_colsum_narrow_f32(const float *x, int64_t ldx, int32_t n_r
     if (work_bytes < fitgnn_colsum_narrow_workspace_bytes(n_rows, C)) return FITGNN_E_WORKSPACE;
     const int blocks = std::min(256, (n_rows + 255) / 256);
     const int rows_per_block = (n_rows + blocks - 1) / blocks;
-    hipLaunchKernelGGL(narrow_colsum_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, n_rows, C, rows_per_block, (float *)work);
+    const int lds = (kRowTile * row_tile_pitch(C) + 256) * (int)sizeof(float);   // at most 66 KB (C = 64)
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)narrow_colsum_kernel, (kRowTile * row_tile_pitch(kNarrowMaxC) + 256) * (int)sizeof(float), lds_done)) return rc;
+    hipLaunchKernelGGL(narrow_colsum_kernel, dim3(blocks), dim3(256), lds, s, x, ldx, n_rows, C, rows_per_block, (float *)work);
     hipLaunchKernelGGL(colsum_partials_kernel, dim3((C + kColsumCols - 1) / kColsumCols), dim3(kColsumPhases * kColsumCols), 0, s,
                        (const float *)work, blocks, C, out);
     return (int)hipGetLastError();

@@ -102,12 +102,26 @@ __device__ __forceinline__ void frag(float (&f)[4], const float *lds, int o, int
     }
 }
 
+// The forward store epilogue fused into the product's store (fitgnn_gemm_exact_epi_f32): c[i][j] <- dropout(ELU(c[i][j] + bias[j]))
+// with the dropout hash / mask entry of element (ORIGINAL row, j), the original row of c's row i being rows[i], or row0 + i without
+// `rows`.  fitgnn::finish_elem: the arithmetic of epilogue_fwd_rows_kernel (gcn_ops.hip), which this saves a pass over c.
+struct StoreEpi {
+    const int64_t *rows;
+    const float *bias;
+    const uint8_t *mask;
+    uint64_t seed;
+    long row0;
+    uint32_t epi;
+    float p_drop;
+};
+
 // nchunks > 1: split over k.  Workgroup (chunk, tile) reduces k in [chunk * chunk_k, +chunk_k) and stores its tile into
 // partial[chunk] (an [I x J] matrix each); sum_chunks_kernel adds them in a fixed order.
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM>
+// EPI (nchunks == 1 only): the accumulators pass through `se` on their way out.
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb,
                                                                    long I, int J, long K, float *__restrict__ C, long ldc, int tiles_i,
-                                                                   int tiles_j, int nchunks, long chunk_k) {
+                                                                   int tiles_j, int nchunks, long chunk_k, StoreEpi se) {
     using G = Geo<WM, WN, MI, NJ, AKM, BKM>;
     extern __shared__ __attribute__((aligned(16))) float lds_f[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -201,6 +215,35 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
     // C/D layout of the 32 x 32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     float *out = nchunks > 1 ? C + (long)chunk * I * J : C;
     const long ldo = nchunks > 1 ? (long)J : ldc;
+    if constexpr (EPI) {
+        // a lane owns one column of a block and 16 of its rows: the bias value once per block, the original rows once per block row
+        const uint64_t seed = fitgnn::resolve_seed(se.seed, se.epi);
+        const float keep_scale = (se.epi & FITGNN_EPI_DROPOUT) ? 1.0f / (1.0f - se.p_drop) : 1.0f;
+        const uint32_t thresh = fitgnn::dropout_threshold(se.p_drop);
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const long row0 = i0 + wm * (32 * MI) + i * 32 + 4 * (lane >> 5);
+            long orow[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long row = row0 + (r & 3) + 8 * (r >> 2);
+                orow[r] = row < I ? (se.rows ? (long)se.rows[row] : se.row0 + row) : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const long col = j0 + wn * (32 * NJ) + j * 32 + (lane & 31);
+                const float bias = ((se.epi & FITGNN_EPI_BIAS) && col < J) ? se.bias[col] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const long row = row0 + (r & 3) + 8 * (r >> 2);
+                    if (row < I && col < J)
+                        out[row * ldo + col] = fitgnn::finish_elem(acc[i][j][r], bias, se.epi, keep_scale, thresh, seed, se.mask,
+                                                                   (uint64_t)orow[r] * (uint64_t)J + (uint64_t)col);
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -216,9 +259,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
     }
 }
 
-// out = sum over chunks of partial[chunk] in a fixed order (eight running sums: eight loads in flight per lane)
+// out = sum over chunks of partial[chunk] in a fixed order (eight running sums: eight loads in flight per lane); EPI: the sums pass
+// through `se` (the tail rows of a fused forward: se.rows / se.row0 are those of the FIRST tail row)
+template <bool EPI>
 __global__ __launch_bounds__(256) void sum_chunks_kernel(const float *__restrict__ partial, int nchunks, long IJ, float *__restrict__ out, int J,
-                                                         long ldc) {
+                                                         long ldc, StoreEpi se) {
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= IJ) return;
     float part[8];
@@ -235,7 +280,15 @@ __global__ __launch_bounds__(256) void sum_chunks_kernel(const float *__restrict
     float acc = part[0];
 #pragma unroll
     for (int u = 1; u < 8; ++u) acc += part[u];
-    out[(q / J) * ldc + (q % J)] = acc;
+    const long row = q / J, col = q % J;
+    if constexpr (EPI) {
+        const uint64_t seed = fitgnn::resolve_seed(se.seed, se.epi);
+        const float keep_scale = (se.epi & FITGNN_EPI_DROPOUT) ? 1.0f / (1.0f - se.p_drop) : 1.0f;
+        const long orow = se.rows ? (long)se.rows[row] : se.row0 + row;
+        acc = fitgnn::finish_elem(acc, (se.epi & FITGNN_EPI_BIAS) ? se.bias[col] : 0.f, se.epi, keep_scale, fitgnn::dropout_threshold(se.p_drop),
+                                  seed, se.mask, (uint64_t)orow * (uint64_t)J + (uint64_t)col);
+    }
+    out[row * ldc + col] = acc;
 }
 
 // Tile shapes.  256 x 256 (8 waves of 64 x 128) is the full-grid shape: one workgroup per CU (147 KB of LDS), 64 flop per operand
@@ -334,31 +387,33 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
     return p;
 }
 
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM>
-int launch(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s) {
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI>
+int launch(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
+           const StoreEpi &se) {
     using G = Geo<WM, WN, MI, NJ, AKM, BKM>;
     static std::atomic<uint64_t> lds_done{0};
-    if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM>, G::LDS_BYTES, lds_done)) return rc;
+    if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>, G::LDS_BYTES, lds_done)) return rc;
     unsigned grid;
     if (p.nchunks > 1) grid = (unsigned)(p.tiles_i * p.tiles_j * ((p.nchunks + 7) / 8 * 8));   // chunk = xcd + 8 * (slot / tiles)
     else grid = (unsigned)((p.tiles_i + 7) / 8 * 8 * p.tiles_j);
-    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J, K,
-                       c, ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k);
+    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J,
+                       K, c, ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k, se);
     return (int)hipGetLastError();
 }
 
-template <bool AKM, bool BKM>
-int launch_shape(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s) {
+template <bool AKM, bool BKM, bool EPI = false>
+int launch_shape(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
+                 const StoreEpi &se = StoreEpi{}) {
     if constexpr (AKM && BKM) {   // make_plan picks the 64 x 512 tile for this pair only (its k-minor LDS image would not fit)
-        if (p.shape == S64x512) return launch<1, 4, 2, 4, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        if (p.shape == S64x512) return launch<1, 4, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
     }
     switch (p.shape) {
-        case S256x128: return launch<4, 1, 2, 4, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S128: return launch<2, 2, 2, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S64x128: return launch<2, 2, 1, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S128x64: return launch<4, 1, 1, 2, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        case S64x64: return launch<2, 2, 1, 1, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
-        default: return launch<4, 2, 2, 4, AKM, BKM>(p, a, lda, b, ldb, I, J, K, c, ldc, s);
+        case S256x128: return launch<4, 1, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        case S128: return launch<2, 2, 2, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        case S64x128: return launch<2, 2, 1, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        case S128x64: return launch<4, 1, 1, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        case S64x64: return launch<2, 2, 1, 1, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        default: return launch<4, 2, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
     }
 }
 
@@ -411,8 +466,8 @@ extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmaj
         }
         if (rc) return rc;
         const long IJ = rem_rows * J;
-        hipLaunchKernelGGL(sum_chunks_kernel, dim3((unsigned)((IJ + 255) / 256)), dim3(256), 0, s, (const float *)workspace, pr.nchunks, IJ,
-                           c + p.main_rows * (long)ldc, J, (long)ldc);
+        hipLaunchKernelGGL(sum_chunks_kernel<false>, dim3((unsigned)((IJ + 255) / 256)), dim3(256), 0, s, (const float *)workspace, pr.nchunks,
+                           IJ, c + p.main_rows * (long)ldc, J, (long)ldc, StoreEpi{});
         return (int)hipGetLastError();
     }
     float *dst = c;
@@ -428,9 +483,44 @@ extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmaj
     if (rc) return rc;
     if (p.nchunks > 1) {
         const long IJ = (long)I * J;
-        hipLaunchKernelGGL(sum_chunks_kernel, dim3((unsigned)((IJ + 255) / 256)), dim3(256), 0, s, (const float *)workspace, p.nchunks, IJ, c, J,
-                           (long)ldc);
+        hipLaunchKernelGGL(sum_chunks_kernel<false>, dim3((unsigned)((IJ + 255) / 256)), dim3(256), 0, s, (const float *)workspace, p.nchunks, IJ, c,
+                           J, (long)ldc, StoreEpi{});
         return (int)hipGetLastError();
     }
     return 0;
+}
+
+// c = dropout(ELU(a b^T + bias)): the forward of a Linear (both operands k-minor) with the layer's store epilogue applied to the
+// accumulators before they are stored -- no second pass over c.  A plan with a tail launch applies the epilogue where the tail's
+// partial sums are added; a plan split over k is refused (the caller runs the product and fitgnn_epilogue_fwd_rows_f32).
+extern "C" int fitgnn_gemm_exact_epi_f32(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t I, int32_t J, int64_t K, float *c,
+                                         int64_t ldc, const int64_t *rows, const float *bias, uint32_t epilogue, float p_drop, uint64_t seed,
+                                         const uint8_t *mask, void *workspace, void *stream) {
+    if (I <= 0 || J <= 0 || K <= 0 || ldc < J) return FITGNN_E_BADARG;
+    if (!a || !b || !c) return FITGNN_E_BADARG;
+    if (K < 4 || (K % 4) != 0 || lda < K || ldb < K || (lda % 4) != 0 || (ldb % 4) != 0) return FITGNN_E_BADARG;
+    if ((((uintptr_t)a | (uintptr_t)b) % 16) != 0) return FITGNN_E_ALIGN;
+    if (epilogue & ~(FITGNN_EPI_BIAS | FITGNN_EPI_ELU | FITGNN_EPI_DROPOUT | FITGNN_EPI_SEED_DEVICE)) return FITGNN_E_BADARG;
+    if ((epilogue & (FITGNN_EPI_ELU | FITGNN_EPI_DROPOUT)) && (J % 4) != 0) return FITGNN_E_BADARG;   // (bias alone: any J)
+    if ((epilogue & FITGNN_EPI_BIAS) && !bias) return FITGNN_E_BADARG;
+    if ((epilogue & FITGNN_EPI_DROPOUT) && !(p_drop >= 0.f && p_drop < 1.f)) return FITGNN_E_BADARG;
+    const Plan p = make_plan((long)I, J, (long)K, false, false);
+    if (p.nchunks > 1) return FITGNN_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    StoreEpi se{rows, bias, mask, seed, 0, epilogue, p_drop};
+    if (p.main_rows == 0) return launch_shape<false, false, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, c, (long)ldc, s, se);
+    if (!workspace || ((uintptr_t)workspace % 16) != 0) return FITGNN_E_BADARG;
+    Plan pm = p, pr = p;
+    pm.tiles_i = (int)(p.main_rows / kShape[p.shape].ti);
+    pr.tiles_i = p.rem_tiles_i; pr.nchunks = p.rem_chunks; pr.chunk_k = p.rem_chunk_k;
+    const long rem_rows = (long)I - p.main_rows;
+    int rc = launch_shape<false, false, true>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s, se);
+    if (!rc) rc = launch_shape<false, false>(pr, a + p.main_rows * (long)lda, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s);
+    if (rc) return rc;
+    if (rows) se.rows = rows + p.main_rows;
+    se.row0 = p.main_rows;
+    const long IJ = rem_rows * J;
+    hipLaunchKernelGGL(sum_chunks_kernel<true>, dim3((unsigned)((IJ + 255) / 256)), dim3(256), 0, s, (const float *)workspace, pr.nchunks, IJ,
+                       c + p.main_rows * (long)ldc, J, (long)ldc, se);
+    return (int)hipGetLastError();
 }

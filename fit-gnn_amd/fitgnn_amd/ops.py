@@ -75,6 +75,9 @@ class OpConfig:
                      one slice at a time (a 2 000-row subgraph of a 47-class signal does); off = the whole-signal units kernel (A/B).
     appnp_blocks     with appnp_in_lds: the larger subgraphs (<= 4 096 rows) one workgroup each, all K steps in ONE launch between two
                      scratch signals that stay in L2, CSR slice in LDS (fitgnn_appnp_blocks_f32); off = the per-step kernel on them (A/B).
+    fused_gemm_epilogue  the store epilogue of a dense part evaluated on kept rows (bias, ELU, dropout of _dense_rows; the head's bias of
+                     _head_rows_fwd) in the exact fp32 product's own store (fitgnn_gemm_exact_epi_f32) instead of a pass over the
+                     product's output (fitgnn_epilogue_fwd_rows_f32 / a broadcast add) after it (A/B switch; identical bits).
     fused_pool_head  lt1(global_mean_pool(x[rows])) of the graph-level regression models as one launch each way (MeanPoolHead) instead
                      of pool, scale, library product and bias add (A/B switch).
     grad_sink        None, or an object with `.view(data_ptr)` -> the slice of a "fresh gradients" buffer that belongs to the parameter stored at
@@ -86,12 +89,12 @@ class OpConfig:
     seed_bank        None, or a SeedBank supplying device-resident dropout seeds (steps captured in a hipGraph)."""
     __slots__ = ("gemm_precision", "atb_kernel", "nt_kernel", "nt_presplit", "fuse_dx_epilogue", "fold_backward",
                  "dedup_gather", "pad_table_min_k", "split_large_blocks", "compact_head_backward", "last_layer_on_loss_rows",
-                 "compact_rows_kernel", "stream_kernel", "two_hop_backward", "narrow_input_first", "fused_pool_head", "pooled_rows_last_layer", "rows_kernel_min_rows", "appnp_in_lds", "appnp_blocks", "appnp_sliced", "grad_sink", "profile", "profile_gemm",
+                 "compact_rows_kernel", "stream_kernel", "two_hop_backward", "narrow_input_first", "fused_pool_head", "fused_gemm_epilogue", "pooled_rows_last_layer", "rows_kernel_min_rows", "appnp_in_lds", "appnp_blocks", "appnp_sliced", "grad_sink", "profile", "profile_gemm",
                  "profile_fused", "seed_bank")
 
     def __init__(self, gemm_precision="exact", atb_kernel=True, nt_kernel=True, nt_presplit=True, fuse_dx_epilogue=True,
                  fold_backward=False, dedup_gather=True, pad_table_min_k=0, split_large_blocks=True, compact_head_backward=True,
-                 last_layer_on_loss_rows=True, compact_rows_kernel=True, stream_kernel=False, two_hop_backward=True, narrow_input_first=True, fused_pool_head=True, pooled_rows_last_layer=True, rows_kernel_min_rows=32768, appnp_in_lds=True, appnp_blocks=True, appnp_sliced=True, grad_sink=None,
+                 last_layer_on_loss_rows=True, compact_rows_kernel=True, stream_kernel=False, two_hop_backward=True, narrow_input_first=True, fused_pool_head=True, fused_gemm_epilogue=True, pooled_rows_last_layer=True, rows_kernel_min_rows=32768, appnp_in_lds=True, appnp_blocks=True, appnp_sliced=True, grad_sink=None,
                  profile=None, profile_gemm=None, profile_fused=None, seed_bank=None):
         if gemm_precision not in ("exact", "high", "highest"):
             raise ValueError(f"gemm_precision {gemm_precision!r}: 'exact', 'high' or 'highest'")
@@ -101,6 +104,7 @@ class OpConfig:
         self.compact_head_backward, self.last_layer_on_loss_rows = compact_head_backward, last_layer_on_loss_rows
         self.compact_rows_kernel, self.stream_kernel, self.two_hop_backward = compact_rows_kernel, stream_kernel, two_hop_backward
         self.narrow_input_first, self.fused_pool_head, self.grad_sink = narrow_input_first, fused_pool_head, grad_sink
+        self.fused_gemm_epilogue = fused_gemm_epilogue
         self.pooled_rows_last_layer, self.rows_kernel_min_rows = pooled_rows_last_layer, int(rows_kernel_min_rows)
         self.appnp_in_lds, self.appnp_blocks, self.appnp_sliced = appnp_in_lds, appnp_blocks, appnp_sliced
         self.profile, self.profile_gemm, self.profile_fused, self.seed_bank = profile, profile_gemm, profile_fused, seed_bank
@@ -195,6 +199,35 @@ def gemm_exact(a, b, form, cfg=DEFAULT, out=None):
                                  _lib.dptr(ws), _lib.stream_ptr(a.device))
     _gemm_done(cfg, ev)
     _lib.check(rc, "fitgnn_gemm_exact_f32")
+    return out
+
+
+def gemm_exact_epi(a, b, rows, bias, epilogue, p=0.0, seed=0, mask=None, cfg=DEFAULT):
+    """dropout(ELU(a [I, K] @ b [J, K]^T + bias)) with the epilogue in the exact product's store (fitgnn_gemm_exact_epi_f32): row i
+    takes the dropout pattern of original row rows[i] (rows None: i).  Bit for bit gemm_exact(a, b, "nt") followed by
+    epilogue_fwd_rows_.  None when the product's plan splits k (the kernel has no single store to put the epilogue in): the caller
+    runs the two launches."""
+    L = _lib.lib()
+    (I, K), J = a.shape, b.shape[0]
+    assert b.shape[1] == K
+    shape, nchunks, main_rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    _lib.check(L.fitgnn_gemm_exact_plan(I, J, K, 0, 0, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows)),
+               "fitgnn_gemm_exact_plan")
+    if nchunks.value > 1:
+        return None
+    _lib.require_cuda(a, b, rows, bias, mask)
+    seed, epilogue = _seed_arg(seed, epilogue)
+    if rows is not None:
+        rows = (rows if rows.dtype == torch.int64 else rows.long()).contiguous()
+    out = torch.empty((I, J), dtype=torch.float32, device=a.device)
+    wb = int(L.fitgnn_gemm_exact_workspace_bytes(I, J, K, 0, 0))
+    ws = torch.empty(wb // 4, dtype=torch.float32, device=a.device) if wb else None
+    ev = _gemm_events(cfg, "gemm_f32_kernel[nt+epi]", 2.0 * I * J * K)
+    rc = L.fitgnn_gemm_exact_epi_f32(_lib.dptr(a), a.stride(0), _lib.dptr(b), b.stride(0), I, J, K, _lib.dptr(out), out.stride(0),
+                                     _lib.dptr(rows), _lib.dptr(None if bias is None else _f32c(bias)), epilogue, float(p), seed,
+                                     _lib.dptr(mask), _lib.dptr(ws), _lib.stream_ptr(a.device))
+    _gemm_done(cfg, ev)
+    _lib.check(rc, "fitgnn_gemm_exact_epi_f32")
     return out
 
 
@@ -1975,6 +2008,10 @@ def _arange_rows(g, n, device):
 def _dense_rows(AHc, W, b, rows, ep, cfg):
     """The dense part of an aggregate-first layer on its kept rows: dropout(ELU(AHc W^T + b)) [n, H], row i with the dropout pattern of
     original row rows[i]."""
+    if cfg.fused_gemm_epilogue and _exact(cfg, AHc, W) and W.shape[0] % 4 == 0:
+        outc = gemm_exact_epi(AHc, W, rows, b, ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg)
+        if outc is not None:
+            return outc
     outc = mm_xwt(AHc, W, cfg)                                       # [n, H]
     if not outc.is_contiguous():
         outc = outc.contiguous()
@@ -1987,11 +2024,14 @@ def _head_rows_fwd(outc, Wl, bl, rows, n_total, compact_out, g, cfg):
     if _exact(cfg, outc, Wl) and Wl.shape[0] >= 16:
         # (a head of a few classes stays on head_rows_kernel: a 128-column MFMA tile for 3 columns is slower than its LDS-resident weights)
         # the head on the kept rows as one more exact-fp32 product: [n, H] @ [C, H]^T on the fp32 MFMA (a 256 x 128 tile of which C
-        # columns are stored: 0.2 ms at S-products against 0.68 ms for head_rows_kernel's LDS-resident weights), bias added after;
+        # columns are stored: 0.2 ms at S-products against 0.68 ms for head_rows_kernel's LDS-resident weights), the bias added in the
+        # product's store (fitgnn_gemm_exact_epi_f32 with FITGNN_EPI_BIAS alone; cfg.fused_gemm_epilogue off: a broadcast add after it);
         # the [R, C] form is the same values scattered into zeros
-        y = gemm_exact(outc, Wl, "nt", cfg)
-        if bl is not None:
-            y = y + bl
+        y = gemm_exact_epi(outc, Wl, None, bl, EPI_BIAS, cfg=cfg) if (cfg.fused_gemm_epilogue and bl is not None) else None
+        if y is None:
+            y = gemm_exact(outc, Wl, "nt", cfg)
+            if bl is not None:
+                y = y + bl
         if not compact_out:
             y = torch.zeros((n_total, y.shape[1]), dtype=torch.float32, device=y.device).index_copy_(0, rows, y)
         return y

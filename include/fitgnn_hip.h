@@ -340,6 +340,18 @@ int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmajor, const f
  * split over k (0 = no such tail launch). */
 int fitgnn_gemm_exact_plan(int64_t I, int32_t J, int64_t K, int32_t a_kmajor, int32_t b_kmajor, int32_t *shape, int32_t *nchunks,
                            int64_t *main_rows);
+/* The forward form (0, 0) with the layer's store epilogue in the product's own store:
+ *     c[i][j] = dropout(ELU(sum_k a[i][k] b[j][k] + bias[j]))
+ * -- the flags, p_drop, seed (a device pointer with FITGNN_EPI_SEED_DEVICE) and mask of fitgnn_epilogue_fwd_rows_f32, row i of c
+ * standing for ORIGINAL row rows[i] (rows == NULL: i) whose dropout hash / mask entry (original row * J + j) it takes.  Bit for bit
+ * what fitgnn_gemm_exact_f32 followed by fitgnn_epilogue_fwd_rows_f32 (H = J) leaves in c, without the second pass over c.
+ * epilogue == FITGNN_EPI_BIAS alone (a head's y = x Wl^T + bl) takes any J; with ELU or dropout J % 4 == 0 (FITGNN_E_BADARG).
+ * Operand requirements and workspace (fitgnn_gemm_exact_workspace_bytes(I, J, K, 0, 0)) as fitgnn_gemm_exact_f32.  A plan with a
+ * tail launch (fitgnn_gemm_exact_plan: main_rows > 0) applies the epilogue where the tail's partial sums are added; a plan that
+ * splits k (nchunks > 1) is refused with FITGNN_E_BADARG: run the two calls instead. */
+int fitgnn_gemm_exact_epi_f32(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t I, int32_t J, int64_t K, float *c,
+                              int64_t ldc, const int64_t *rows, const float *bias, uint32_t epilogue, float p_drop, uint64_t seed,
+                              const uint8_t *mask, void *workspace, void *stream);
 
 /* Pre-split b operand for the tall-GEMM kernels: b [N x K] given by element strides (b[n * stride_n + k * stride_k]; so
  * b = W^T needs no transposed copy) is converted ONCE per call into bf16 hi/lo fragments laid out as the kernel's LDS image,
