@@ -511,8 +511,10 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
         p_rp = 0;
         if ((int)threadIdx.x <= r1 - r0) p_rp = rowptr[r0 + threadIdx.x];
         // the slice's end is not known yet (it is rowptr[r1], in flight above): stage the next kBlkMeta entries of the block,
-        // clamped to the block's last entry; entries past the piece's end are ignored by the row loop
-        if ((int)threadIdx.x < kBlkMeta) {
+        // clamped to the block's last entry; entries past the piece's end are ignored by the row loop.  A block without entries
+        // stages nothing: its "last entry" nnz_end - 1 would lie before the block, at row 0 before the arrays
+        p_c = 0; p_cx = 0; p_v = 0.f;
+        if ((int)threadIdx.x < kBlkMeta && blk.nnz_end > blk.nnz_begin) {
             const int e = min(E0 + (int)threadIdx.x, blk.nnz_end - 1);
             p_c = col[e];
             p_cx = (TWO || (XROW && xcol)) ? xcol[e] : p_c;
@@ -1539,6 +1541,14 @@ int spmm_rows_impl(const int32_t *rowptr, const int32_t *xcol, const float *val,
     if (bwd && (!prev || ((uintptr_t)prev % 16) != 0 || (epilogue & FITGNN_EPI_BIAS))) return FITGNN_E_BADARG;
     int32_t per, n_ranges;
     rows_plan(n_rows, &per, &n_ranges);
+    if (nnz == 0) {
+        // a matrix without entries (xcol / val may be NULL): the streaming kernel loads xcol[0] / val[0] whatever the row lengths,
+        // so it is not launched -- the H columns of every row of Y are 0 (columns H .. ldy untouched), and so is every col_part row
+        hipError_t e = hipMemset2DAsync(Y, (size_t)ldy * sizeof(float), 0, (size_t)H * sizeof(float), (size_t)n_rows, (hipStream_t)stream);
+        if (e == hipSuccess && bwd && col_part)
+            e = hipMemsetAsync(col_part, 0, (size_t)n_ranges * (size_t)H * sizeof(float), (hipStream_t)stream);
+        return (int)e;
+    }
     const int n_slabs = (H + 255) / 256;
     const dim3 grid((unsigned)(((int64_t)n_ranges * n_slabs + kWaves - 1) / kWaves));
     if (bwd)

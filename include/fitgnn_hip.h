@@ -92,7 +92,7 @@ int fitgnn_split_blocks_host(const int64_t *ptr, int64_t n_blocks, const int32_t
  * mostly self-contained segment of one (a star: a centre row and the rows that reference it) -- handled whole by one
  * workgroup per column slab (fitgnn_spmm_csr_blocks_f32): every operand row inside the run is read once; columns outside it
  * are gathered.  long_rows[long_off .. long_off + n_long) are the run's rows with many non-zeros (ascending row ids; the
- * first 8 are carried, see spmm.hip). */
+ * first 4 are carried, see spmm.hip). */
 typedef struct fitgnn_block {
     int32_t row_begin, row_end; /* rows of the run */
     int32_t nnz_begin, nnz_end; /* = rowptr[row_begin], rowptr[row_end] */
@@ -182,7 +182,9 @@ int fitgnn_spmm_csr_stream_dz_f32(const int32_t *rowptr, const int32_t *col, con
  * order (same bits as the kernels above), zero rows from registers; each wave streams a contiguous range of rows, no LDS.
  * _dz_: the store applies the previous layer's ELU' / dropout' as fitgnn_spmm_csr_dz_f32 does; col_part (may be NULL) receives
  * fitgnn_spmm_rows_compact_parts(n_rows) partial rows [parts x H] of column sums of dZ (every element written: no zeroing needed),
- * to be folded by fitgnn_colsum_partials_f32.  H, ldx, ldy multiples of 4; X, Y, prev 16-byte aligned. */
+ * to be folded by fitgnn_colsum_partials_f32.  H, ldx, ldy multiples of 4; X, Y, prev 16-byte aligned.
+ * nnz == 0 (xcol / val may then be NULL and are not read): no kernel is launched; the H columns of every row of Y are set to 0
+ * (columns H .. ldy are left alone) and, in the _dz_ form, every element of col_part. */
 int32_t fitgnn_spmm_rows_compact_parts(int32_t n_rows);
 int fitgnn_spmm_rows_compact_f32(const int32_t *rowptr, const int32_t *xcol, const float *val, int64_t nnz, const float *X, int64_t ldx,
                                  int32_t zero_from, float *Y, int64_t ldy, int32_t n_rows, int32_t H, void *stream);
