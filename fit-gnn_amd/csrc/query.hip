@@ -15,7 +15,9 @@
 // fitgnn_gcn_graph_query_tail_f32: a graph's layer-0 rows are formed once, in LDS (see graph_query_hops_kernel).  Two GINConv layers
 // have fitgnn_gin_graph_query_hops_f32 and fitgnn_gin_graph_query_tail_f32: the dense product behind layer 0's ReLU runs once per
 // row of the graph (see gin_graph_query_hops_kernel).  Two GATConv layers have fitgnn_gat_graph_query_hops_f32 in front of the GCN graph
-// tail: a graph's attention rows and their two score dots are formed once, in LDS (see gat_graph_query_hops_kernel).
+// tail: a graph's attention rows and their two score dots are formed once, in LDS (see gat_graph_query_hops_kernel).  Two SAGEConv
+// layers have fitgnn_sage_graph_query_hops_f32 in front of the same tail: a graph's mean-plus-root rows are formed once, in LDS, and
+// a pooled row's own h is copied from there (see sage_graph_query_hops_kernel).
 //
 // Operation order (tests/query_reference.py mirrors it):
 //   gather  a = 0; a = fmaf(val[e'], T[.][c], a) over row j's entries in CSR order; h = ELU(a + b0[c]), ELU(x) = x > 0 ? x : expm1f(x);
@@ -1274,6 +1276,80 @@ __global__ __launch_bounds__(256) void gat_graph_query_hops_kernel(const int32_t
     }
 }
 
+// ---- graph queries for two SAGEConv layers ----
+// The view's MEAN CSR (no self loops, val = 1 / max(deg, 1)) and the table T = X [W_l0 ; W_r0]^T of sage_query_gather_kernel.  The
+// per-row gather forms a layer-0 row once per entry that reaches it and once more for the row itself; here each is formed ONCE
+// per (graph, slab), in the LDS window, and a pooled row's own h is a copy from there.
+//   h_r  = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b_l0)       r in [r0, r1)
+//   g_r  = sum_{e in row r} val[e] h_{col[e]}                                           r among the graph's pooled rows
+//   G[j] = [g_r | h_r]: graph_query_tail_kernel with K = 2H, W1 = [W_l1 | W_r1], b1 = b_l1 finishes (pool, head, softmax).
+// Operation order (tests/sage_graph_query_reference.py mirrors it):
+//   phase 1  row r by sage_row, unchanged: a = 0; a = fmaf(val[e'], T[t(col[e'])][c], a) over row r's entries in CSR order;
+//            h_r[c] = ELU((a + T[t(r)][H + c]) + b0[c]) (b0 == NULL: the second add is absent); a row without entries:
+//            ELU(T[t(r)][H + c] + b0[c]).  The same bits as the node kernel's h, on any wave and any slab.
+//   phase 2  g = 0; g = fmaf(val[e], h_{col[e]}[c], g) over the pooled row's entries in CSR order, ONE chain (no wave partials);
+//            G[j][c] = g, G[j][H + c] = h_r[c] from the window.  A pooled row without entries gives g = 0 and still its h_r.
+
+// One workgroup of four waves per (graph, 256-column slab), the slab fastest.  The graph's rows are dealt round-robin to the waves,
+// which form them (sage_row) into the LDS window hs [r1 - r0][min(H, 256)]: a wave writes and later reads 64 consecutive float4,
+// every bank once, so the window needs no padding.  After the one barrier the graph's pooled rows are dealt round-robin to the waves;
+// a wave fetches the row's entries 64 at a time and broadcasts (window row, value) by v_readlane.  A graph beyond max_rows returns
+// before it touches anything; a graph without pooled rows writes nothing.
+__global__ __launch_bounds__(256) void sage_graph_query_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                                    const float *__restrict__ val, const float *__restrict__ T,
+                                                                    int64_t ldt, const int32_t *__restrict__ xrow,
+                                                                    const float *__restrict__ b0, const int64_t *__restrict__ seg,
+                                                                    const int64_t *__restrict__ prow, const int64_t *__restrict__ pptr,
+                                                                    int32_t H, int32_t max_rows, float *__restrict__ G, int64_t ldg,
+                                                                    int32_t n_slabs) {
+    extern __shared__ float4 hs[];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gi = blockIdx.x / n_slabs, c0 = (blockIdx.x % n_slabs) * 256;
+    const int r0 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi]), r1 = __builtin_amdgcn_readfirstlane((int)seg[2 * (int64_t)gi + 1]);
+    if (r1 - r0 > max_rows) return;  // workgroup-uniform: the window was sized for max_rows
+    const int w4 = min(H, 256) >> 2;  // float4 per window row
+    const int c = c0 + lane * 4;
+    const bool live = c < H;  // H % 4 == 0: a live lane owns four whole columns
+    const float *Tc = T + (live ? c : 0);
+    const bool has_bias = b0 != nullptr;
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has_bias && live) bias = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+    for (int r = r0 + w; r < r1; r += kGatherWaves) {
+        const float4 h = sage_row(rowptr, col, val, Tc, ldt, H, xrow, has_bias, bias, r, lane);
+        if (live) hs[(r - r0) * w4 + lane] = h;
+    }
+    __syncthreads();
+    const int64_t p1 = pptr[gi + 1];
+    for (int64_t j = pptr[gi] + w; j < p1; j += kGatherWaves) {
+        const int r = __builtin_amdgcn_readfirstlane((int)prow[j]);
+        const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = n0; base < n1; base += 64) {
+            const int cnt = min(64, n1 - base);
+            int my = 0, mv = 0;
+            if (lane < cnt) {
+                my = col[base + lane] - r0;
+                mv = __float_as_int(val[base + lane]);
+            }
+            for (int k = 0; k < cnt; ++k) {
+                const int node = __builtin_amdgcn_readlane(my, k);
+                const float wv = __int_as_float(__builtin_amdgcn_readlane(mv, k));
+                if (live) {
+                    const float4 h = hs[node * w4 + lane];
+                    g.x = fmaf(wv, h.x, g.x);
+                    g.y = fmaf(wv, h.y, g.y);
+                    g.z = fmaf(wv, h.z, g.z);
+                    g.w = fmaf(wv, h.w, g.w);
+                }
+            }
+        }
+        if (live) {
+            *reinterpret_cast<float4 *>(G + j * ldg + c) = g;
+            *reinterpret_cast<float4 *>(G + j * ldg + H + c) = hs[(r - r0) * w4 + lane];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int fitgnn_gcn_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
@@ -1543,4 +1619,29 @@ extern "C" int fitgnn_gat_graph_query_hops_f32(const int32_t *rowptr, const int3
                                                max_rows, G, ldg, lds, st)
                     : launch_gat_graph_hops<2>(rowptr, col, T, ldt, xrow, a_src0, a_dst0, b0, slope0, u_src, u_dst, slope1, seg, prow, pptr, Q, H,
                                                max_rows, G, ldg, lds, st);
+}
+
+extern "C" size_t fitgnn_sage_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H) {
+    if (max_rows < 0 || H < 4) return 0;
+    return (size_t)max_rows * (size_t)std::min(H, 256) * sizeof(float);
+}
+
+extern "C" int fitgnn_sage_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                                const int32_t *xrow, const float *b0, const int64_t *seg, const int64_t *prow,
+                                                const int64_t *pptr, int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg,
+                                                void *stream) {
+    if (Q < 0 || H < 4 || (H % 4) != 0 || max_rows < 0 || ldt < 2 * (int64_t)H || ldg < 2 * (int64_t)H) return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_sage_graph_query_hops_lds_bytes(max_rows, H);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // the largest graph's layer-0 rows do not fit LDS
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !val || !T || !seg || !prow || !pptr || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G) % 16) != 0) return FITGNN_E_ALIGN;
+    const int n_slabs = (H + 255) / 256;
+    if ((int64_t)Q * n_slabs > 0x7fffffffLL) return FITGNN_E_BADARG;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)sage_graph_query_hops_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(sage_graph_query_hops_kernel, dim3((unsigned)(Q * n_slabs)), dim3(256), lds, (hipStream_t)stream, rowptr, col, val, T,
+                       ldt, xrow, b0, seg, prow, pptr, H, max_rows, G, ldg, n_slabs);
+    return (int)hipGetLastError();
 }

@@ -154,6 +154,8 @@ SIGNATURES = {
     "fitgnn_gat_graph_query_hops_lds_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_gat_graph_query_hops_f32": (ctypes.c_int, [ptr, ptr, ptr, c_i64, ptr, ptr, ptr, ptr, c_f32, ptr, ptr, c_f32, ptr, ptr, ptr, c_i32,
                                                        c_i32, c_i32, ptr, c_i64, ptr]),
+    "fitgnn_sage_graph_query_hops_lds_bytes": (c_size, [c_i32, c_i32]),
+    "fitgnn_sage_graph_query_hops_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, ptr, ptr, c_i32, c_i32, c_i32, ptr, c_i64, ptr]),
     "fitgnn_csr_row_sum_f32": (ctypes.c_int, [ptr, ptr, c_i32, ptr, ptr]),
     "fitgnn_induced_edges_count": (ctypes.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_i64, ptr, ptr]),
     "fitgnn_induced_edges_fill": (ctypes.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, ptr]),

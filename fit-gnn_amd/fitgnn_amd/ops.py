@@ -1383,22 +1383,60 @@ def sage_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
     return G
 
 
-def sage_query_supported(model):
-    """fitgnn_sage_query_gather_f32 and the tail answer for `model`: exactly two SAGEConv layers and a head, hidden sizes multiples
-    of 16, a head the tail's LDS holds, contiguous float32 parameters on the GPU (lin_l.bias may be None)."""
+def _sage_query_shapes(model):
+    """(H2, C) when `model` is exactly two SAGEConv layers and a head with hidden sizes multiples of 16 and contiguous float32
+    parameters on the GPU (lin_l.bias may be None); None otherwise.  The callers add their tail's LDS bound."""
     from . import nn as fnn
     convs = list(getattr(model, "conv", ()))
     lt1 = getattr(model, "lt1", None)
     if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.SAGEConv for c in convs):
-        return False
+        return None
     Wl0, Wr0, Wl1, Wr1, Wl = convs[0].lin_l.weight, convs[0].lin_r.weight, convs[1].lin_l.weight, convs[1].lin_r.weight, lt1.weight
     params = [Wl0, Wr0, Wl1, Wr1, Wl, convs[0].lin_l.bias, convs[1].lin_l.bias, lt1.bias]
     if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
-        return False
+        return None
     H, H2, C = int(Wl0.shape[0]), int(Wl1.shape[0]), int(Wl.shape[0])
-    return (H % 16 == 0 and H2 % 16 == 0 and tuple(Wr0.shape) == tuple(Wl0.shape) and tuple(Wl1.shape) == (H2, H)
-            and tuple(Wr1.shape) == (H2, H) and int(Wl.shape[1]) == H2
-            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+    ok = (H % 16 == 0 and H2 % 16 == 0 and tuple(Wr0.shape) == tuple(Wl0.shape) and tuple(Wl1.shape) == (H2, H)
+          and tuple(Wr1.shape) == (H2, H) and int(Wl.shape[1]) == H2)
+    return (H2, C) if ok else None
+
+
+def sage_query_supported(model):
+    """fitgnn_sage_query_gather_f32 and the tail answer for `model`: exactly two SAGEConv layers and a head, hidden sizes multiples
+    of 16, a head the tail's LDS holds, contiguous float32 parameters on the GPU (lin_l.bias may be None)."""
+    shapes = _sage_query_shapes(model)
+    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes) <= 160 * 1024
+
+
+def sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=None, b0=None, out=None):
+    """G [P, 2H]: row j = [g_r | h_r] for view row r = prow[j] -- the layer-1 mean aggregation over its graph's layer-0 SAGE rows, each
+    formed once in LDS from T = X [W_l0 ; W_r0]^T [n_table, 2H] over the mean CSR, and r's own layer-0 row copied from there
+    (fitgnn_sage_graph_query_hops_f32).  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled rows, graph
+    i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int, at most sage_graph_query_max_rows(H)).
+    The caller checks that prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
+    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)
+    Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1]) // 2
+    G = out if out is not None else torch.empty((P, 2 * H), dtype=torch.float32, device=T.device)
+    if P == 0:
+        return G
+    _lib.check(_lib.lib().fitgnn_sage_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
+                                                           _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q,
+                                                           H, int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
+               "fitgnn_sage_graph_query_hops_f32")
+    return G
+
+
+def sage_graph_query_max_rows(H):
+    """The largest graph (rows) whose layer-0 rows fitgnn_sage_graph_query_hops_f32 holds in LDS at hidden size H."""
+    per_row = int(_lib.lib().fitgnn_sage_graph_query_hops_lds_bytes(1, int(H)))
+    return (160 * 1024) // per_row if per_row > 0 else 0
+
+
+def sage_graph_query_supported(model):
+    """fitgnn_sage_graph_query_hops_f32 and the graph tail answer for `model`: sage_query_supported's conditions with the graph tail's
+    LDS bound in place of the node tail's."""
+    shapes = _sage_query_shapes(model)
+    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes) <= 160 * 1024
 
 
 def gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow=None, b0a=None, out=None):

@@ -86,6 +86,20 @@ layer-1 score is two LDS scalar reads and an add:
 A wave holds a whole row (a score is a dot over all of H), so the window's row is H floats: ops.gat_graph_query_max_rows(H) rows, 79 at
 hidden 512 and 620 at 64.  A larger graph's pooled rows take ops.gat_query_gather (the same g_r up to the summation order), into the
 same G in front of the one tail.  Opt-in, as the node engine's switch is.
+
+With sage_kernels=True a model of two SAGEConv layers takes one launch of its own over the view's mean CSR (no self loops added,
+val = 1 / max(deg, 1)) in front of the GCN graph tail, unchanged, called with K = 2H.  The per-row kernel (ops.sage_query_gather)
+re-forms h_c -- a gather of deg(c) + 1 table half-rows -- once per entry that reaches c and once more for c itself,
+sum_r (deg(r) + 1) layer-0 rows per graph; the window forms each ONCE, and a pooled row's own h is a copy from it:
+
+    T     = X [W_l0 ; W_r0]^T    [n_rows, 2H]                           once per set of the four weights (one ops.Linear)
+    h_r   = ELU(sum_{k in row r} val[k] T[col[k]][0:H] + T[r][H:2H] + b_l0)     EVERY row r of the graph, formed once, in LDS
+    G_r   = [sum_{e in row r} val[e] h_{col[e]} | h_r]                  r among the graph's pooled rows     ops.sage_graph_query_hops
+    out   = Wl pool_r ELU([W_l1 | W_r1] G_r + b_l1) + bl   (softmax)                                        ops.gcn_graph_query_tail
+
+The columns of h are independent, so the window's row is one 256-column slab: ops.sage_graph_query_max_rows(H) rows, 160 at hidden 512
+and 640 at 64, as on the GCN path.  A larger graph's pooled rows take ops.sage_query_gather (the same [g | h] layout; g up to the
+summation order), into the same G in front of the one tail.  Opt-in, as the node engine's switch is.
 """
 import numpy as np
 import torch
@@ -140,6 +154,21 @@ def gat_prepared_state(T, ws):
 def _gat_weights(model):
     c0, c1 = model.conv
     return [c0.lin.weight, c0.att_src, c0.att_dst, c1.lin.weight, c1.att_src, c1.att_dst]
+
+
+def sage_prepared_state(X, ws, op_config):
+    """The SAGE paths' state made from the table operand X and the four weights ws = [W_l0, W_r0, W_l1, W_r1]:
+    ([(tensor, version)] of ws, T = X [W_l0 ; W_r0]^T [n_table, 2H] (one product), W1cat = [W_l1 | W_r1] [H2, 2H]).  Both engines call it."""
+    Wl0, Wr0, Wl1, Wr1 = ws
+    with torch.no_grad():
+        T = ops.Linear.apply(X.float(), torch.cat([Wl0.detach(), Wr0.detach()], 0).contiguous(), op_config).contiguous()
+        W1cat = torch.cat([Wl1.detach(), Wr1.detach()], 1).contiguous()
+    return ([(w, w._version) for w in ws], T, W1cat)
+
+
+def _sage_weights(model):
+    c0, c1 = model.conv
+    return [c0.lin_l.weight, c0.lin_r.weight, c1.lin_l.weight, c1.lin_r.weight]
 
 
 class QueryEngine:
@@ -244,17 +273,11 @@ class QueryEngine:
         return (self._T[2],) + tuple(self._gat[1:])
 
     def _sage_weights(self):
-        c0, c1 = self.model.conv
-        return [c0.lin_l.weight, c0.lin_r.weight, c1.lin_l.weight, c1.lin_r.weight]
+        return _sage_weights(self.model)
 
     def _refresh_sage(self):
-        """T = X [W_l0 ; W_r0]^T [n_table, 2H] (one product) and W1cat = [W_l1 | W_r1] [H2, 2H]."""
-        Wl0, Wr0, Wl1, Wr1 = ws = self._sage_weights()
-        X, _ = self._operand()
-        with torch.no_grad():
-            T = ops.Linear.apply(X.float(), torch.cat([Wl0.detach(), Wr0.detach()], 0).contiguous(), self.model.op_config).contiguous()
-            W1cat = torch.cat([Wl1.detach(), Wr1.detach()], 1).contiguous()
-        self._sage = ([(w, w._version) for w in ws], T, W1cat)
+        """T = X [W_l0 ; W_r0]^T [n_table, 2H] (one product) and W1cat = [W_l1 | W_r1] [H2, 2H] (sage_prepared_state)."""
+        self._sage = sage_prepared_state(self._operand()[0], self._sage_weights(), self.model.op_config)
         return self
 
     def _sage_state(self):
@@ -399,13 +422,14 @@ class GraphQueryEngine:
     model's hidden size -- are answered through the per-row gather inside the same call.  gin_kernels: a model of two GINConv layers
     with the reference's two-Linear ReLU MLP is answered by the GIN graph-query pair (off by default, as QueryEngine's switch is); it
     changes nothing for any other model.  gat_kernels: the same switch for a model of two GATConv layers (heads = 1): the attention
-    window launch in front of the GCN graph tail.
+    window launch in front of the GCN graph tail.  sage_kernels: the same switch for a model of two SAGEConv layers: the
+    mean-plus-root window launch over the view's mean CSR in front of the GCN graph tail with K = 2H.
 
     The view's CSR, the per-graph pointers and the index of pooled rows are built here, once.  Any model the kernels do not
     take (ops.graph_query_supported, ops.gin_graph_query_supported behind gin_kernels, ops.gat_graph_query_supported behind
-    gat_kernels) is answered by its own forward on gset.batch_ids(the unique ids, view)."""
+    gat_kernels, ops.sage_graph_query_supported behind sage_kernels) is answered by its own forward on gset.batch_ids(the unique ids, view)."""
 
-    def __init__(self, model, gset, view=None, max_window_rows=None, gin_kernels=False, gat_kernels=False):
+    def __init__(self, model, gset, view=None, max_window_rows=None, gin_kernels=False, gat_kernels=False, sage_kernels=False):
         from . import network
         gs_cls = (network.Classify_graph_gs, network.Regress_graph_gs)
         gc_cls = (network.Classify_graph_gc, network.Regress_graph_gc)
@@ -425,6 +449,7 @@ class GraphQueryEngine:
         self.max_window_rows = None if max_window_rows is None else int(max_window_rows)
         self.gin_kernels = bool(gin_kernels)
         self.gat_kernels = bool(gat_kernels)
+        self.sage_kernels = bool(sage_kernels)
         ptr, x, mask = {"gs": (gset.gs_ptr, gset.gs_x, gset.gs_mask), "gc": (gset.cluster_ptr, gset.gc_x, None),
                         "orig": (gset.node_ptr, gset.x, None)}[view]
         ptr = np.asarray(ptr, dtype=np.int64)
@@ -440,19 +465,23 @@ class GraphQueryEngine:
         self._prow, self._pp = prow, pp
         self._prow_host = prow.cpu().numpy()
         self._T = None          # (W0, W0._version, T): W0 = conv[0].lin.weight, on the GIN path conv[0].nn[0].weight
-        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "gin" | None: the kernels that answer)
+        self._fused = None      # (key of the model's layers and parameters, "gcn" | "gat" | "sage" | "gin" | None: the kernels that answer)
         self._sum = None        # the view's sum CSR (the GIN path's pattern), looked up once
         self._gat = None        # the GAT path's prepared state: ([(tensor, version)] of the six weights, a0s, a0d, u_s, u_d)
         self._gat_graph = None  # the view's "gat" CSR (existing self loops removed, one added per row), looked up once
+        self._sage = None       # the SAGE path's prepared state: ([(tensor, version)] of the four weights, T [n_rows, 2H], W1cat)
+        self._mean = None       # the view's mean CSR (the SAGE path's pattern), looked up once
 
     def _kind(self):
-        """"gcn" (ops.graph_query_supported), "gat" (gat_kernels and ops.gat_graph_query_supported), "gin" (gin_kernels and
-        ops.gin_graph_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
+        """"gcn" (ops.graph_query_supported), "gat" (gat_kernels and ops.gat_graph_query_supported), "sage" (sage_kernels and
+        ops.sage_graph_query_supported), "gin" (gin_kernels and ops.gin_graph_query_supported) or None, re-evaluated only when a layer or a parameter's storage, type or shape has changed."""
         m = self.model
         params = [p for c in m.conv for p in (getattr(getattr(c, "lin", None), "weight", None), getattr(c, "bias", None))]
         params += [m.lt1.weight, m.lt1.bias]
         if self.gat_kernels:
             params += [getattr(c, a, None) for c in m.conv for a in ("att_src", "att_dst")]
+        if self.sage_kernels:
+            params += [getattr(getattr(c, l, None), a, None) for c in m.conv for l in ("lin_l", "lin_r") for a in ("weight", "bias")]
         if self.gin_kernels:
             mlps = [getattr(c, "nn", None) for c in m.conv]
             subs = [list(n) if isinstance(n, torch.nn.Sequential) else [] for n in mlps]
@@ -461,6 +490,8 @@ class GraphQueryEngine:
         key = tuple(type(c) for c in m.conv) + tuple((p.data_ptr(), p.dtype, p.shape) if torch.is_tensor(p) else p for p in params)
         if self._fused is None or self._fused[0] != key:
             kind = "gcn" if ops.graph_query_supported(m) else ("gat" if self.gat_kernels and ops.gat_graph_query_supported(m) else None)
+            if kind is None and self.sage_kernels and ops.sage_graph_query_supported(m):
+                kind = "sage"
             if kind is None and self.gin_kernels and ops.gin_graph_query_supported(m):
                 kind = "gin"
             self._fused = (key, kind)
@@ -477,9 +508,11 @@ class GraphQueryEngine:
 
     def refresh(self):
         """Remake T = X W0^T (on the GIN path X W0a^T, without the bias: the kernel adds it behind the aggregation) and, on the GAT
-        path, the score vectors and W1^T att from the model's current weights (done automatically when the storage or version of a
-        weight they are made from changes)."""
-        if self.fused:
+        path, the score vectors and W1^T att; on the SAGE path T = X [W_l0 ; W_r0]^T and [W_l1 | W_r1] -- from the model's current
+        weights (done automatically when the storage or version of a weight they are made from changes)."""
+        if self._kind() == "sage":
+            self._sage = sage_prepared_state(self.x, _sage_weights(self.model), self.model.op_config)
+        elif self.fused:
             W0 = self._w0()
             with torch.no_grad():
                 T = ops.Linear.apply(self.x.float(), W0, self.model.op_config).contiguous()
@@ -494,6 +527,19 @@ class GraphQueryEngine:
         if self._gat is None or not all(ops._same_index(e, w) for e, w in zip(self._gat[0], ws)) or not ops._same_index(self._T, ws[0]):
             self.refresh()
         return (self._T[2],) + tuple(self._gat[1:])
+
+    def _sage_state(self):
+        """(T, W1cat), remade when the storage or version of any of the four weights has changed."""
+        ws = _sage_weights(self.model)
+        if self._sage is None or not all(ops._same_index(e, w) for e, w in zip(self._sage[0], ws)):
+            self.refresh()
+        return self._sage[1], self._sage[2]
+
+    def _mean_csr(self):
+        """The view's mean CSR (rows = targets, no self loops added, val = 1 / max(deg, 1)): nn.SAGEConv.forward's own lookup."""
+        if self._mean is None:
+            self._mean = csr_for(self._whole["edge_index"], self.n_rows, "mean")
+        return self._mean
 
     def _gat_csr(self):
         """The view's "gat" CSR (rows = targets, existing self loops removed, one added per row): nn.GATConv.forward's own lookup."""
@@ -514,10 +560,13 @@ class GraphQueryEngine:
 
     @property
     def table_bytes(self):
-        """Bytes of T -- [n_rows, Ha] on the GIN path -- and of the two score vectors on the GAT path (0 when the model's own forward
-        answers: it keeps none)."""
+        """Bytes of T -- [n_rows, Ha] on the GIN path, [n_rows, 2H] on the SAGE path -- and of the two score vectors on the GAT path (0
+        when the model's own forward answers: it keeps none)."""
         if not self.fused:
             return 0
+        if self._kind() == "sage":
+            T = self._sage_state()[0]
+            return int(T.numel()) * T.element_size()
         if self._kind() == "gat":
             T, a0s, a0d = self._gat_state()[:3]
             return int(T.numel()) * T.element_size() + int(a0s.numel() + a0d.numel()) * a0s.element_size()
@@ -544,13 +593,15 @@ class GraphQueryEngine:
 
     def _predict_fused(self, ids, cnt):
         m, dev = self.model, self.x.device
-        gin, gat = self._kind() == "gin", self._kind() == "gat"
-        f = self._sum_csr().f if gin else self._gat_csr().f if gat else self.graph.f
+        gin, gat, sage = self._kind() == "gin", self._kind() == "gat", self._kind() == "sage"
+        f = self._sum_csr().f if gin else self._gat_csr().f if gat else self._mean_csr().f if sage else self.graph.f
         C = int(m.lt1.weight.shape[0])
         if ids.size == 0:
             return torch.empty((0, C), dtype=torch.float32, device=dev)
         if gat:
             T, a0s, a0d, u_s, u_d = self._gat_state()
+        elif sage:
+            T, W1cat = self._sage_state()
         else:
             T = self._table()
         Q = int(ids.size)
@@ -569,6 +620,10 @@ class GraphQueryEngine:
             eps0, eps1 = m.conv[0].eps.detach(), m.conv[1].eps.detach()
             Hg = int(l0b.weight.shape[0])
             limit = ops.gin_graph_query_max_rows(int(T.shape[1]), Hg)
+        elif sage:   # G = [g_r | h_r]: the tail's K is 2H
+            Hg = int(T.shape[1])
+            limit = ops.sage_graph_query_max_rows(Hg // 2)
+            b0 = m.conv[0].lin_l.bias
         else:
             Hg = int(T.shape[1])
             limit = ops.gat_graph_query_max_rows(Hg) if gat else ops.graph_query_max_rows(Hg)
@@ -586,6 +641,8 @@ class GraphQueryEngine:
                                          b0a=l0a.bias, out=G)
             elif gat:
                 ops.gat_graph_query_hops(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, seg, prow, pptr, window, b0=b0, out=G, **slopes)
+            elif sage:
+                ops.sage_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, window, b0=b0, out=G)
             else:
                 ops.gcn_graph_query_hops(f.rowptr, f.col, f.val, T, seg, prow, pptr, window, b0=b0, out=G)
         if large.any():   # the per-row kernel: correct for any size, the view being block-diagonal
@@ -595,11 +652,15 @@ class GraphQueryEngine:
                 G.index_copy_(0, pos, ops.gin_query_hops(f.rowptr, f.col, f.val, T, eps0, l0b.weight, l0b.bias, eps1, rows, b0a=l0a.bias))
             elif gat:
                 G.index_copy_(0, pos, ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, rows, b0=b0, **slopes))
+            elif sage:
+                G.index_copy_(0, pos, ops.sage_query_gather(f.rowptr, f.col, f.val, T, rows, b0=b0))
             else:
                 G.index_copy_(0, pos, ops.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, b0=b0))
         if gin:
             return ops.gin_graph_query_tail(G, pptr, l1a.weight, l1a.bias, l1b.weight, l1b.bias, m.lt1.weight, m.lt1.bias, pool=pool,
                                             softmax=self.classify)
+        if sage:
+            return ops.gcn_graph_query_tail(G, pptr, W1cat, m.conv[1].lin_l.bias, m.lt1.weight, m.lt1.bias, pool=pool, softmax=self.classify)
         return ops.gcn_graph_query_tail(G, pptr, m.conv[1].lin.weight, m.conv[1].bias, m.lt1.weight, m.lt1.bias, pool=pool,
                                         softmax=self.classify)
 

@@ -21,6 +21,7 @@ as PyTorch-ROCm custom ops").  Importing this module registers
     fitgnn::gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b?, eps1, seg, prow, pptr, max_rows, xrow?, b0a?) -> G [P, Hb]     their GIN
     fitgnn::gin_graph_query_tail(G, pptr, W1a, b1a?, W1b, b1b?, Wl, bl?, pool (0 max, 1 mean), softmax) -> out [Q, C]                 counterparts
     fitgnn::gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, max_rows, xrow?, b0?, slope0, slope1) -> G [P, H]     the GAT first launch (then gcn_graph_query_tail)
+    fitgnn::sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow?, b0?) -> G [P, 2H] = [g_r | h_r]     the SAGE first launch (T [n_table, 2H], the mean CSR; then gcn_graph_query_tail with K = 2H)
                                               (rows: int64 union rows inside the CSR -- not checked here, the kernel cannot; serve.QueryEngine checks)
 
 for the CUDA (HIP) dispatch key only -- there is no CPU kernel, a CPU tensor fails in the dispatcher -- with fake
@@ -59,6 +60,8 @@ _LIB.define("gin_graph_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor 
             "Tensor seg, Tensor prow, Tensor pptr, int max_rows, Tensor? xrow, Tensor? b0a) -> Tensor")
 _LIB.define("gat_graph_query_hops(Tensor rowptr, Tensor col, Tensor T, Tensor a_src0, Tensor a_dst0, Tensor u_src, Tensor u_dst, Tensor seg, "
             "Tensor prow, Tensor pptr, int max_rows, Tensor? xrow, Tensor? b0, float slope0, float slope1) -> Tensor")
+_LIB.define("sage_graph_query_hops(Tensor rowptr, Tensor col, Tensor val, Tensor T, Tensor seg, Tensor prow, Tensor pptr, int max_rows, "
+            "Tensor? xrow, Tensor? b0) -> Tensor")
 _LIB.define("gin_graph_query_tail(Tensor G, Tensor pptr, Tensor W1a, Tensor? b1a, Tensor W1b, Tensor? b1b, Tensor Wl, Tensor? bl, int pool, "
             "bool softmax) -> Tensor")
 
@@ -167,7 +170,11 @@ def _gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, pro
                                     slope1=slope1)
 
 
-for _name, _fn in (("gat_graph_query_hops", _gat_graph_query_hops), ("gcn_graph_query_hops", _gcn_graph_query_hops), ("gcn_graph_query_tail", _gcn_graph_query_tail),
+def _sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow, b0):
+    return ops.sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=xrow, b0=b0)
+
+
+for _name, _fn in (("gat_graph_query_hops", _gat_graph_query_hops), ("sage_graph_query_hops", _sage_graph_query_hops), ("gcn_graph_query_hops", _gcn_graph_query_hops), ("gcn_graph_query_tail", _gcn_graph_query_tail),
                    ("gin_graph_query_hops", _gin_graph_query_hops), ("gin_graph_query_tail", _gin_graph_query_tail),
                    ("gcn_query_gather", _gcn_query_gather), ("gat_query_gather", _gat_query_gather), ("sage_query_gather", _sage_query_gather), ("gin_query_hops", _gin_query_hops), ("gin_query_tail", _gin_query_tail), ("gcn_query_tail", _gcn_query_tail), ("gemm_nt", _gemm_nt), ("gemm_atb", _gemm_atb), ("linear", _gemm_nt), ("spmm_csr", _spmm_csr), ("spmm_csr_pair", _spmm_csr_pair), ("gcn_norm_csr", _gcn_norm_csr),
                    ("epilogue_bwd", _epilogue_bwd), ("pool_rows", _pool_rows), ("variation_costs", _variation_costs),
@@ -268,6 +275,11 @@ def _(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow
 
 @torch.library.register_fake("fitgnn::gat_graph_query_hops")
 def _(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, max_rows, xrow, b0, slope0, slope1):
+    return T.new_empty((prow.shape[0], T.shape[1]))
+
+
+@torch.library.register_fake("fitgnn::sage_graph_query_hops")
+def _(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow, b0):
     return T.new_empty((prow.shape[0], T.shape[1]))
 
 

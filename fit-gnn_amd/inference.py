@@ -13,7 +13,8 @@ Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN i
 fitgnn_amd.serve.GraphQueryEngine.predict -- inside the same timing bracket; same CSV row),
 --query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel; on graph_cls / graph_reg
 by the GAT graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_sage (with
---query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel), --query_gin (with --query_engine: a
+--query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel; on graph_cls / graph_reg by the SAGE
+graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_gin (with --query_engine: a
 two-layer GINConv model is answered by the GIN query kernels; on graph_cls / graph_reg by the GIN graph-query kernels, the baseline
 under --baseline included).
 """
@@ -86,7 +87,9 @@ def build_parser():
                         "LDS) instead of the model's own forward, the baseline under --baseline included; ignored without --query_engine")
     p.add_argument('--query_sage', action='store_true',
                    help="with --query_engine: a --layer_name SAGEConv model of two layers is answered by the mean-aggregation query kernel "
-                        "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; ignored without --query_engine")
+                        "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; graph_cls / graph_reg: by the SAGE graph-query "
+                        "kernel (GraphQueryEngine(sage_kernels=True): every mean-plus-root row of a graph formed once, in LDS) instead of "
+                        "the model's own forward, the baseline under --baseline included; ignored without --query_engine")
     p.add_argument('--query_gin', action='store_true',
                    help="with --query_engine: a --layer_name GINConv model of two layers is answered by the GIN query kernels "
                         "(QueryEngine(gin_kernels=True)) instead of the per-subgraph forward; graph_cls / graph_reg: by the GIN graph-query "
@@ -143,7 +146,8 @@ def graph_inference(args, mol):
         engine = None
         if args.query_engine:   # built outside the timed region, as the per-graph CSR is below; T = X W0^T is made here too
             from fitgnn_amd.serve import GraphQueryEngine
-            engine = GraphQueryEngine(model, gset, view=kind, gin_kernels=args.query_gin, gat_kernels=args.query_attention).refresh()
+            engine = GraphQueryEngine(model, gset, view=kind, gin_kernels=args.query_gin, gat_kernels=args.query_attention,
+                                      sage_kernels=args.query_sage).refresh()
         with torch.no_grad():
             for g in ids:
                 if engine is not None:

@@ -798,6 +798,30 @@ int fitgnn_gat_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, c
                                     const float *u_dst, float slope1, const int64_t *seg, const int64_t *prow, const int64_t *pptr,
                                     int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg, void *stream);
 
+/* Two SAGEConv layers (aggr = mean, root weight) have a first launch of their own in front of fitgnn_gcn_graph_query_tail_f32, unchanged,
+ * called with K = 2H, W1 = [W_l1 | W_r1] and b1 = b_l1.  G[j][0:H) = g_r and G[j][H:2H) = h_r for r = prow[j], every pooled row of every
+ * queried graph, over T = X [W_l0 ; W_r0]^T [n_table x 2H] (row stride ldt; columns [0, H) = X W_l0^T, [H, 2H) = X W_r0^T) and the view's
+ * mean CSR (all rows of all graphs, block-diagonal per graph; no self loops added, val = 1 / max(deg, 1)), t(r) = xrow ? xrow[r] : r:
+ *   h_r = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b0)        for EVERY row r of graph i's range [seg[i][0], seg[i][1]),
+ *   g_r = sum_{e in row r} val[e] h_{col[e]}                                          for r = prow[j], pptr[i] <= j < pptr[i + 1].
+ * fitgnn_sage_query_gather_f32 on the same rows forms h_c once per entry that reaches c and once for c itself: sum_r (deg(r) + 1) layer-0
+ * rows instead of seg[i][1] - seg[i][0].  One workgroup of four waves per graph and 256-column slab of H.  Phase 1: the graph's rows dealt
+ * round-robin to the waves, each h_r (bit-equal to fitgnn_sage_query_gather_f32's) into an LDS window of row stride min(H, 256).  After
+ * one barrier the graph's pooled rows are dealt round-robin to the waves: g_r is ONE fmaf chain over the row's entries in CSR order (no
+ * wave partials: its last bits may differ from fitgnn_sage_query_gather_f32's), h_r is copied from the window.  No atomics: two launches
+ * give the same bits (operation order: csrc/query.hip).  A row without entries gives h_r = ELU(T[t(r)][H:2H] + b0); a pooled row without
+ * entries g_r = 0 and still its h_r.  seg (int64 [Q][2]) may repeat graphs and needs no order; prow (int64, rows of the view) lists graph
+ * i's pooled rows inside its range; pptr is int64 [Q + 1].  The kernel cannot check that prow and col stay inside the graph's range: the
+ * caller does.  max_rows: the host-known largest seg[i][1] - seg[i][0] (a graph with more rows is skipped: its rows of G are not
+ * written).  Dynamic LDS: fitgnn_sage_graph_query_hops_lds_bytes(max_rows, H) = max_rows * min(H, 256) * 4 bytes (640 rows at H = 64, 160
+ * at H >= 256; 0 for max_rows < 0 or H < 4).  xrow, b0 may be NULL.  Writes G[0..pptr[Q]) x [0..2H) only.  Requires H >= 4, H % 4 == 0 (H
+ * is not limited), max_rows >= 0, ldt, ldg >= 2H and the LDS at most 160 KiB (FITGNN_E_BADARG), ldt, ldg multiples of 4 and T, G 16-byte
+ * aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_sage_graph_query_hops_lds_bytes(int32_t max_rows, int32_t H);
+int fitgnn_sage_graph_query_hops_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *T, int64_t ldt,
+                                     const int32_t *xrow, const float *b0, const int64_t *seg, const int64_t *prow, const int64_t *pptr,
+                                     int32_t Q, int32_t H, int32_t max_rows, float *G, int64_t ldg, void *stream);
+
 /* =====================================================================================
  * Coarsen half: one contraction level of variation_neighborhoods
  * replaces: graph_coarsening/coarsening_utils.py contract_variation_linear :530-650,

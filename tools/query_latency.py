@@ -23,7 +23,7 @@ Writes profiles/query_latency_<workload>.json (profiles/query_latency_<workload>
                          fitgnn_stream_copy_f32's rate in the same process.
 The engine's answers are compared with the per-subgraph forward's on every sampled row (max relative difference is recorded).
 
-    python tools/query_latency.py --task graph_reg | graph_cls [--layer GINConv | GATConv] [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512]
+    python tools/query_latency.py --task graph_reg | graph_cls [--layer GINConv | GATConv | SAGEConv] [--n_graphs 2000] [--view gs | gc | orig] [--hidden 512]
                                   [--samples 256] [--rounds 5] [--batch 1024] [--out FILE]
 
 --task graph_reg / graph_cls: one GRAPH query through fitgnn_amd.serve.GraphQueryEngine (fitgnn_gcn_graph_query_hops_f32 and
@@ -31,22 +31,28 @@ fitgnn_gcn_graph_query_tail_f32) against the per-graph forward inference.py time
 graph_data.synthetic_molecules (graph_reg: Regress_graph_gs / _gc) or synthetic_graph_classes (graph_cls: Classify_graph_gs / _gc),
 extra-node layout.  --layer GINConv: a two-layer GIN model through GraphQueryEngine(gin_kernels=True)
 (fitgnn_gin_graph_query_hops_f32 over the sum CSR and fitgnn_gin_graph_query_tail_f32).  --layer GATConv: a two-layer GAT model through
-GraphQueryEngine(gat_kernels=True) (fitgnn_gat_graph_query_hops_f32 over the "gat" CSR and fitgnn_gcn_graph_query_tail_f32).  Writes
-profiles/query_latency_<task>_<view>.json (profiles/query_latency_<task>_<view>_<layer>.json with --layer GINConv / GATConv; or --out):
+GraphQueryEngine(gat_kernels=True) (fitgnn_gat_graph_query_hops_f32 over the "gat" CSR and fitgnn_gcn_graph_query_tail_f32).
+--layer SAGEConv: a two-layer SAGE model through GraphQueryEngine(sage_kernels=True) (fitgnn_sage_graph_query_hops_f32 over the mean CSR
+and fitgnn_gcn_graph_query_tail_f32 with K = 2H).  Writes profiles/query_latency_<task>_<view>.json
+(profiles/query_latency_<task>_<view>_<layer>.json with --layer GINConv / GATConv / SAGEConv; or --out):
   (a) engine_single      predict([g]) per sampled graph, bracketed as above;
   (b) graph_forward      the model on the graph cut out of the set (gset.batch(g, g + 1, view), its CSR and pool index pre-built),
                          measured twice per graph around the engine's turn, after one untimed pass;
   (c) engine_batch       predict(ids) at Q = --batch (ids drawn with repeats) against the same graphs one forward each (the loop (b)
                          runs) and against ONE forward of the model on gset.batch_ids(the unique ids) pre-built;
   table_row_reads        counted, not timed: sum over the pooled rows r of sum_{c in row r} deg(c) (the per-row gather on every pooled
-                         row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio;
+                         row) against sum over every row of the queried graphs of deg(r) (each layer-0 row formed once), and their ratio
+                         (--layer GINConv / SAGEConv: plus the root row of every layer-0 row formed, on both sides);
   dense_rows             --layer GINConv, counted, not timed: the layer-0 rows that take the dense Hb x Ha product -- every row of the
                          view once (the window path) against sum over the pooled rows r of deg(r) + 1 (fitgnn_gin_query_hops_f32 on
                          every pooled row), and their ratio;
   attention_rows         --layer GATConv, counted, not timed: the layer-0 attention rows formed (a softmax, a gather and two score dots
                          each) -- every row of the view once (the window path) against sum over the pooled rows r of deg(r) + 1
                          (fitgnn_gat_query_gather_f32 on every pooled row, with one h_q per wave that has entries counted once), and
-                         their ratio."""
+                         their ratio;
+  sage_rows              --layer SAGEConv, counted, not timed: the layer-0 rows formed (a gather of deg + 1 table half-rows each) -- every
+                         row of the view once (the window path) against sum over the pooled rows r of deg(r) + 1
+                         (fitgnn_sage_query_gather_f32 on every pooled row), and their ratio."""
 import argparse
 import json
 import os
@@ -255,15 +261,13 @@ def graph_main(a):
     gs = a.view == "gs"
     cls = ("Regress_graph_" if reg else "Classify_graph_") + ("gs" if gs else "gc")
     C = 1 if reg else int(mol["y"].max()) + 1
-    if a.layer not in ("GCNConv", "GINConv", "GATConv"):
-        raise SystemExit("--task graph_reg / graph_cls takes --layer GCNConv, GINConv or GATConv")
-    gin, gat = a.layer == "GINConv", a.layer == "GATConv"
+    gin, gat, sage = a.layer == "GINConv", a.layer == "GATConv", a.layer == "SAGEConv"
     margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=int(gset.x.shape[1]), hidden=a.hidden, num_classes=C)
     torch.manual_seed(2)
     model = getattr(network, cls)(margs).to(dev).eval()
-    engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin, gat_kernels=gat)
+    engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin, gat_kernels=gat, sage_kernels=sage)
     assert engine.fused and (ops.gin_graph_query_supported(model) if gin else ops.gat_graph_query_supported(model) if gat
-                             else ops.graph_query_supported(model))
+                             else ops.sage_graph_query_supported(model) if sage else ops.graph_query_supported(model))
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -328,7 +332,7 @@ def graph_main(a):
         t_whole = timed(lambda: call(whole))
 
     # counted: table rows read by the per-row gather on every pooled row against every layer-0 row formed once
-    f = engine._sum_csr().f if gin else engine._gat_csr().f if gat else engine.graph.f
+    f = engine._sum_csr().f if gin else engine._gat_csr().f if gat else engine._mean_csr().f if sage else engine.graph.f
     deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
     csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
     csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)
@@ -336,7 +340,7 @@ def graph_main(a):
     prow = engine._prow
     per_row = int((csum[rp[prow + 1]] - csum[rp[prow]]).sum())
     once = int(deg.sum())
-    if gin:   # every layer-0 row formed also reads its own table row
+    if gin or sage:   # every layer-0 row formed also reads its own table row (SAGEConv: its root half-row)
         per_row += int(deg[prow].sum()) + int(prow.numel())
         once += int(engine.n_rows)
 
@@ -365,7 +369,13 @@ def graph_main(a):
                                      ratio=round(per_row_att / max(int(engine.n_rows), 1), 3),
                                      window_rows=int(ops.gat_graph_query_max_rows(a.hidden)),
                                      largest_graph_rows=int(np.diff(engine._ptr).max()))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_' + a.layer if gin or gat else ''}.json")
+    if sage:
+        per_row_sage = int(deg[prow].sum()) + int(prow.numel())
+        res["sage_rows"] = dict(per_row_gather=per_row_sage, each_row_once=int(engine.n_rows),
+                                ratio=round(per_row_sage / max(int(engine.n_rows), 1), 3),
+                                window_rows=int(ops.sage_graph_query_max_rows(a.hidden)),
+                                largest_graph_rows=int(np.diff(engine._ptr).max()))
+    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_' + a.layer if gin or gat or sage else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
