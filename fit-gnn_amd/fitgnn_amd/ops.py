@@ -1201,6 +1201,25 @@ def head_rows(out, rows, Wl, bl, n_total=None):
     return y
 
 
+_LDS_BYTES = 160 * 1024    # what one workgroup of a query kernel may hold
+
+
+def _fits_lds(nbytes):
+    """An *_lds_bytes answer is a size the launcher takes: not 0 (refused shapes) and within _LDS_BYTES."""
+    return 0 < nbytes <= _LDS_BYTES
+
+
+def _lds_rows(lds_bytes, H):
+    """The rows that fit _LDS_BYTES at hidden size H, given the window kernel's *_lds_bytes(rows, H) entry point."""
+    per_row = int(lds_bytes(1, int(H)))
+    return _LDS_BYTES // per_row if per_row > 0 else 0
+
+
+def _f32_on_gpu(params):
+    """Every parameter that is there is float32, contiguous and on the GPU."""
+    return all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params)
+
+
 def gcn_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
     """G [Q, H]: row i = the layer-1 aggregation of union row rows[i] over layer-0 rows made from T = X W0^T on the fly
     (fitgnn_gcn_query_gather_f32).  rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
@@ -1225,21 +1244,27 @@ def gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=False, out=None):
     return y
 
 
-def query_supported(model):
-    """The two query kernels answer for `model`: exactly two GCNConv layers, hidden size a multiple of 16, a head the tail's LDS
-    holds, contiguous float32 parameters on the GPU."""
+def _gcn_query_shapes(model):
+    """(H2, C) when `model` is exactly two GCNConv layers and a head with hidden sizes multiples of 16 and contiguous float32
+    parameters on the GPU; None otherwise.  The callers add their tail's LDS bound."""
     from . import nn as fnn
     convs = list(getattr(model, "conv", ()))
     lt1 = getattr(model, "lt1", None)
     if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GCNConv for c in convs):
-        return False
+        return None
     W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
-    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias]
-    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
-        return False
+    if not _f32_on_gpu([W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias]):
+        return None
     H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
-    return (H % 16 == 0 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
-            and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+    ok = H % 16 == 0 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+    return (H2, C) if ok else None
+
+
+def query_supported(model):
+    """The two query kernels answer for `model`: exactly two GCNConv layers, hidden size a multiple of 16, a head the tail's LDS
+    holds, contiguous float32 parameters on the GPU."""
+    shapes = _gcn_query_shapes(model)
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes))
 
 
 def gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=None, b0=None, out=None):
@@ -1275,25 +1300,14 @@ def gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool="max", softmax=False, out
 
 def graph_query_max_rows(H):
     """The largest graph (rows) whose layer-0 rows fitgnn_gcn_graph_query_hops_f32 holds in LDS at hidden size H."""
-    per_row = int(_lib.lib().fitgnn_gcn_graph_query_hops_lds_bytes(1, int(H)))
-    return (160 * 1024) // per_row if per_row > 0 else 0
+    return _lds_rows(_lib.lib().fitgnn_gcn_graph_query_hops_lds_bytes, H)
 
 
 def graph_query_supported(model):
     """The two graph-query kernels answer for `model`: query_supported's conditions (exactly two GCNConv layers, hidden sizes
     multiples of 16, contiguous float32 parameters on the GPU) with the graph tail's LDS bound in place of the node tail's."""
-    from . import nn as fnn
-    convs = list(getattr(model, "conv", ()))
-    lt1 = getattr(model, "lt1", None)
-    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GCNConv for c in convs):
-        return False
-    W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
-    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias]
-    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
-        return False
-    H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
-    return (H % 16 == 0 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
-            and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(H2, C) <= 160 * 1024)
+    shapes = _gcn_query_shapes(model)
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes))
 
 
 def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=None, b0=None, slope0=0.2, slope1=0.2, out=None):
@@ -1320,8 +1334,7 @@ def _gat_query_shapes(model):
         return None
     W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
     att = [convs[0].att_src, convs[0].att_dst, convs[1].att_src, convs[1].att_dst]
-    params = [W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias] + att
-    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+    if not _f32_on_gpu([W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias] + att):
         return None
     H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
     ok = (H % 16 == 0 and H <= 512 and H2 % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
@@ -1334,7 +1347,7 @@ def gat_query_supported(model):
     16 with the first at most 512 (a wave holds a whole layer-0 row), a head the tail's LDS holds, contiguous float32 parameters on
     the GPU."""
     shapes = _gat_query_shapes(model)
-    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes) <= 160 * 1024
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes))
 
 
 def gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, max_rows, xrow=None, b0=None, slope0=0.2,
@@ -1359,15 +1372,14 @@ def gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow
 
 def gat_graph_query_max_rows(H):
     """The largest graph (rows) whose layer-0 rows and score dots fitgnn_gat_graph_query_hops_f32 holds in LDS at hidden size H."""
-    per_row = int(_lib.lib().fitgnn_gat_graph_query_hops_lds_bytes(1, int(H)))
-    return (160 * 1024) // per_row if per_row > 0 else 0
+    return _lds_rows(_lib.lib().fitgnn_gat_graph_query_hops_lds_bytes, H)
 
 
 def gat_graph_query_supported(model):
     """fitgnn_gat_graph_query_hops_f32 and the graph tail answer for `model`: gat_query_supported's conditions with the graph tail's
     LDS bound in place of the node tail's."""
     shapes = _gat_query_shapes(model)
-    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes) <= 160 * 1024
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes))
 
 
 def sage_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
@@ -1392,8 +1404,7 @@ def _sage_query_shapes(model):
     if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.SAGEConv for c in convs):
         return None
     Wl0, Wr0, Wl1, Wr1, Wl = convs[0].lin_l.weight, convs[0].lin_r.weight, convs[1].lin_l.weight, convs[1].lin_r.weight, lt1.weight
-    params = [Wl0, Wr0, Wl1, Wr1, Wl, convs[0].lin_l.bias, convs[1].lin_l.bias, lt1.bias]
-    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+    if not _f32_on_gpu([Wl0, Wr0, Wl1, Wr1, Wl, convs[0].lin_l.bias, convs[1].lin_l.bias, lt1.bias]):
         return None
     H, H2, C = int(Wl0.shape[0]), int(Wl1.shape[0]), int(Wl.shape[0])
     ok = (H % 16 == 0 and H2 % 16 == 0 and tuple(Wr0.shape) == tuple(Wl0.shape) and tuple(Wl1.shape) == (H2, H)
@@ -1405,7 +1416,7 @@ def sage_query_supported(model):
     """fitgnn_sage_query_gather_f32 and the tail answer for `model`: exactly two SAGEConv layers and a head, hidden sizes multiples
     of 16, a head the tail's LDS holds, contiguous float32 parameters on the GPU (lin_l.bias may be None)."""
     shapes = _sage_query_shapes(model)
-    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes) <= 160 * 1024
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes))
 
 
 def sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=None, b0=None, out=None):
@@ -1428,15 +1439,14 @@ def sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=N
 
 def sage_graph_query_max_rows(H):
     """The largest graph (rows) whose layer-0 rows fitgnn_sage_graph_query_hops_f32 holds in LDS at hidden size H."""
-    per_row = int(_lib.lib().fitgnn_sage_graph_query_hops_lds_bytes(1, int(H)))
-    return (160 * 1024) // per_row if per_row > 0 else 0
+    return _lds_rows(_lib.lib().fitgnn_sage_graph_query_hops_lds_bytes, H)
 
 
 def sage_graph_query_supported(model):
     """fitgnn_sage_graph_query_hops_f32 and the graph tail answer for `model`: sage_query_supported's conditions with the graph tail's
     LDS bound in place of the node tail's."""
     shapes = _sage_query_shapes(model)
-    return shapes is not None and 0 < _lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes) <= 160 * 1024
+    return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_graph_query_tail_lds_bytes(*shapes))
 
 
 def gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow=None, b0a=None, out=None):
@@ -1484,8 +1494,7 @@ def gin_query_supported(model):
             return False
     lins = [convs[0].nn[0], convs[0].nn[2], convs[1].nn[0], convs[1].nn[2]]
     eps = [getattr(c, "eps", None) for c in convs]
-    params = [w for l in lins for w in (l.weight, l.bias)] + [lt1.weight, lt1.bias]
-    if not all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+    if not _f32_on_gpu([w for l in lins for w in (l.weight, l.bias)] + [lt1.weight, lt1.bias]):
         return False
     if not all(torch.is_tensor(e) and e.is_cuda and e.dtype == torch.float32 and e.numel() == 1 and e.is_contiguous() for e in eps):
         return False
@@ -1493,7 +1502,7 @@ def gin_query_supported(model):
     chain = all(int(b.weight.shape[1]) == h for b, h in zip(lins[1:] + [lt1], hidden))
     C = int(lt1.weight.shape[0])
     return (chain and all(h % 16 == 0 and h <= 512 for h in hidden)
-            and 0 < _lib.lib().fitgnn_gin_query_tail_lds_bytes(hidden[2], hidden[3], C) <= 160 * 1024)
+            and _fits_lds(_lib.lib().fitgnn_gin_query_tail_lds_bytes(hidden[2], hidden[3], C)))
 
 
 def gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, max_rows, xrow=None, b0a=None, out=None):
@@ -1535,7 +1544,7 @@ def gin_graph_query_max_rows(Ha, Hb):
     Ha, Hb (0 for widths it does not take)."""
     L = _lib.lib()
     base, one = int(L.fitgnn_gin_graph_query_hops_lds_bytes(0, int(Ha), int(Hb))), int(L.fitgnn_gin_graph_query_hops_lds_bytes(1, int(Ha), int(Hb)))
-    return max(0, (160 * 1024 - base) // (one - base)) if one > base > 0 else 0
+    return max(0, (_LDS_BYTES - base) // (one - base)) if one > base > 0 else 0
 
 
 def gin_graph_query_supported(model):
@@ -1544,8 +1553,8 @@ def gin_graph_query_supported(model):
     if not gin_query_supported(model):
         return False
     lins = [model.conv[1].nn[0], model.conv[1].nn[2]]
-    return 0 < _lib.lib().fitgnn_gin_graph_query_tail_lds_bytes(int(lins[0].weight.shape[0]), int(lins[1].weight.shape[0]),
-                                                                int(model.lt1.weight.shape[0])) <= 160 * 1024
+    return _fits_lds(_lib.lib().fitgnn_gin_graph_query_tail_lds_bytes(int(lins[0].weight.shape[0]), int(lins[1].weight.shape[0]),
+                                                                      int(model.lt1.weight.shape[0])))
 
 
 def segment_sum(seg_off, members, X, n_seg):

@@ -197,8 +197,8 @@ def test_torch_ops_hold_the_launcher(mods):
     gset = _gset(graph_data, "cls", extra_node=True)
     model = _gat_model(network, "Classify_graph_gs", gset.x.shape[1], 64)
     eng = serve.GraphQueryEngine(model, gset, gat_kernels=True)
-    f = eng._gat_csr().f
-    T, a0s, a0d, u_s, u_d = eng._gat_state()
+    f = eng.csr().f
+    T, a0s, a0d, u_s, u_d = eng.state()
     assert T.shape == (eng.n_rows, 64) and T.is_contiguous() and a0s.shape == a0d.shape == (eng.n_rows,) and u_s.shape == u_d.shape == (64,)
     ids = np.asarray(IDS)
     seg = torch.from_numpy(np.stack([eng._ptr[ids], eng._ptr[ids + 1]], 1)).cuda()

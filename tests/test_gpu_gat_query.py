@@ -155,7 +155,7 @@ def test_torch_op_holds_the_launcher(mods):
     model = _gat_model(network, 12, 64)
     eng = serve.QueryEngine(model, batch, gat_kernels=True)
     f = batch.graph.f
-    T, a0s, a0d, u_s, u_d = eng._gat_state()
+    T, a0s, a0d, u_s, u_d = eng.state()
     rows = torch.nonzero(batch.core).flatten()
     xrow, b0 = batch.row_index.index, model.conv[0].bias
     G = torch.ops.fitgnn.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, rows, xrow, b0, 0.2, SLOPE1)

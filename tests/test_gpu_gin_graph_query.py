@@ -218,7 +218,7 @@ def test_torch_ops_hold_the_two_launchers(mods):
     gset = _gset(graph_data, "cls", extra_node=True)
     model = _gin_model(network, "Classify_graph_gs", gset.x.shape[1], 64)
     eng = serve.GraphQueryEngine(model, gset, gin_kernels=True)
-    f, T = eng._sum_csr().f, eng._table()
+    f, T = eng.csr().f, eng.state()[0]
     assert T.shape == (eng.n_rows, 64) and T.is_contiguous() and bool((f.val == 1).all())
     ids = np.asarray(IDS)
     seg = torch.from_numpy(np.stack([eng._ptr[ids], eng._ptr[ids + 1]], 1)).cuda()

@@ -185,8 +185,8 @@ def test_torch_ops_hold_the_launchers(mods):
     batch = _union(fdata, "extra", 12)
     model = _gin_model(network, 12, 64)
     eng = serve.QueryEngine(model, batch, gin_kernels=True)
-    f = eng._sum_csr().f
-    T = eng._gin_state()
+    f = eng.csr().f
+    T = eng.state()[0]
     assert T.shape == (batch.x_table.shape[0], 64) and T.is_contiguous() and bool((f.val == 1).all())
     rows = torch.nonzero(batch.core).flatten()
     c0, c1 = model.conv

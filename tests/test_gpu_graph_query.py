@@ -234,7 +234,7 @@ def test_torch_ops_hold_the_two_launchers(mods):
     gset = _gset(graph_data, "cls", extra_node=True)
     model = _model(network, "Classify_graph_gs", gset.x.shape[1], 64)
     eng = serve.GraphQueryEngine(model, gset)
-    f, T = eng.graph.f, eng._table()
+    f, T = eng.graph.f, eng.state()[0]
     ids = np.asarray(IDS)
     seg = torch.from_numpy(np.stack([eng._ptr[ids], eng._ptr[ids + 1]], 1)).cuda()
     cnt = torch.from_numpy(eng._pp[ids + 1] - eng._pp[ids]).cuda()

@@ -179,7 +179,7 @@ def test_torch_ops_hold_the_two_launchers(mods):
     batch = _union(fdata, "extra", 12)
     model = _model(network, 12, 64)
     eng = serve.QueryEngine(model, batch)
-    f, T = batch.graph.f, eng._table()
+    f, T = batch.graph.f, eng.state()[0]
     rows = torch.nonzero(batch.core).flatten()
     xrow, b0 = batch.row_index.index, model.conv[0].bias
     G = torch.ops.fitgnn.gcn_query_gather(f.rowptr, f.col, f.val, T, rows, xrow, b0)

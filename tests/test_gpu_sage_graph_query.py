@@ -225,8 +225,8 @@ def test_torch_ops_hold_the_launcher(mods):
     gset = _gset(graph_data, "cls", extra_node=True)
     model = _sage_model(network, "Classify_graph_gs", gset.x.shape[1], 64)
     eng = serve.GraphQueryEngine(model, gset, sage_kernels=True)
-    f = eng._mean_csr().f
-    T, W1cat = eng._sage_state()
+    f = eng.csr().f
+    T, W1cat = eng.state()
     assert T.shape == (eng.n_rows, 128) and T.is_contiguous() and W1cat.shape == (64, 128) and W1cat.is_contiguous()
     ids = np.asarray(IDS)
     seg = torch.from_numpy(np.stack([eng._ptr[ids], eng._ptr[ids + 1]], 1)).cuda()

@@ -157,8 +157,8 @@ def test_torch_op_holds_the_launcher(mods):
     batch = _union(fdata, "extra", 12)
     model = _sage_model(network, 12, 64)
     eng = serve.QueryEngine(model, batch, sage_kernels=True)
-    f = eng._mean_csr().f
-    T, W1cat = eng._sage_state()
+    f = eng.csr().f
+    T, W1cat = eng.state()
     assert T.shape == (batch.x_table.shape[0], 128) and W1cat.shape == (64, 128) and W1cat.is_contiguous()
     rows = torch.nonzero(batch.core).flatten()
     xrow, b0 = batch.row_index.index, model.conv[0].lin_l.bias

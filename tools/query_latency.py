@@ -94,7 +94,7 @@ def main():
     import torch
 
     import inference
-    from fitgnn_amd import _lib, network, ops, serve, workloads
+    from fitgnn_amd import _lib, network, serve, workloads
     from fitgnn_amd.csr import csr_for
 
     assert torch.cuda.is_available(), "query_latency.py measures on the GPU only"
@@ -112,8 +112,8 @@ def main():
     sage = a.layer == "SAGEConv"
     gin = a.layer == "GINConv"
     engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage, gin_kernels=gin)
-    assert engine.fused and (ops.gat_query_supported(model) if gat else ops.sage_query_supported(model) if sage
-                             else ops.gin_query_supported(model) if gin else ops.query_supported(model))
+    path = engine.path()
+    assert path is not None and path.name == a.layer[:-4].lower()
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -129,7 +129,7 @@ def main():
         r0, r1 = int(ptr[s]), int(ptr[s + 1])
         m = (ei[0] >= r0) & (ei[0] < r1)
         cache[int(s)] = (batch.x[r0:r1].contiguous(), (ei[:, m] - r0).contiguous(), r0)
-        csr_for(cache[int(s)][1], r1 - r0, "gat" if gat else "mean" if sage else "sum" if gin else "gcn")
+        csr_for(cache[int(s)][1], r1 - r0, serve._layer_mode(model))
 
     def engine_once(row):
         torch.cuda.synchronize(dev)
@@ -172,25 +172,14 @@ def main():
             engine.predict_rows(qrows)
         torch.cuda.synchronize()
         t_batch = (time.time() - t) / reps
-        f = engine._mean_csr().f if sage else engine._sum_csr().f if gin else batch.graph.f
-        T = engine._gat_state()[0] if gat else engine._sage_state()[0] if sage else engine._gin_state() if gin else engine._table()
+        f, state = engine.csr().f, engine.state()
+        T = state[0]
         xrow = batch.row_index.index if batch.row_index is not None else None
-        G = torch.empty((a.batch, 2 * a.hidden if sage else a.hidden), dtype=torch.float32, device=dev)
+        G = torch.empty((a.batch, path.g_width(state, model)), dtype=torch.float32, device=dev)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
         for e0, e1 in ev:
             e0.record()
-            if gat:
-                _, a0s, a0d, u_s, u_d = engine._gat_state()
-                ops.gat_query_gather(f.rowptr, f.col, T, a0s, a0d, u_s, u_d, qrows, xrow=xrow, b0=model.conv[0].bias,
-                                     slope0=model.conv[0].negative_slope, slope1=model.conv[1].negative_slope, out=G)
-            elif sage:
-                ops.sage_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].lin_l.bias, out=G)
-            elif gin:
-                l0a, l0b = model.conv[0].nn[0], model.conv[0].nn[2]
-                ops.gin_query_hops(f.rowptr, f.col, f.val, T, model.conv[0].eps.detach(), l0b.weight, l0b.bias, model.conv[1].eps.detach(),
-                                   qrows, xrow=xrow, b0a=l0a.bias, out=G)
-            else:
-                ops.gcn_query_gather(f.rowptr, f.col, f.val, T, qrows, xrow=xrow, b0=model.conv[0].bias, out=G)
+            path.rows_hops(f, state, model, qrows, xrow=xrow, out=G)
             e1.record()
         torch.cuda.synchronize()
         t_gather = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e-3
@@ -250,7 +239,7 @@ def graph_main(a):
     import numpy as np
     import torch
 
-    from fitgnn_amd import graph_data, network, ops, serve
+    from fitgnn_amd import graph_data, network, serve
     from fitgnn_amd.train import _cat_pieces
 
     assert torch.cuda.is_available(), "query_latency.py measures on the GPU only"
@@ -266,8 +255,8 @@ def graph_main(a):
     torch.manual_seed(2)
     model = getattr(network, cls)(margs).to(dev).eval()
     engine = serve.GraphQueryEngine(model, gset, view=a.view, gin_kernels=gin, gat_kernels=gat, sage_kernels=sage)
-    assert engine.fused and (ops.gin_graph_query_supported(model) if gin else ops.gat_graph_query_supported(model) if gat
-                             else ops.sage_graph_query_supported(model) if sage else ops.graph_query_supported(model))
+    path = engine.path()
+    assert path is not None and path.name == a.layer[:-4].lower()
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -332,7 +321,7 @@ def graph_main(a):
         t_whole = timed(lambda: call(whole))
 
     # counted: table rows read by the per-row gather on every pooled row against every layer-0 row formed once
-    f = engine._sum_csr().f if gin else engine._gat_csr().f if gat else engine._mean_csr().f if sage else engine.graph.f
+    f = engine.csr().f
     deg = (f.rowptr[1:] - f.rowptr[:-1]).long()
     csum = torch.zeros(f.col.numel() + 1, dtype=torch.int64, device=dev)
     csum[1:] = torch.cumsum(deg.index_select(0, f.col.long()), 0)
@@ -357,24 +346,12 @@ def graph_main(a):
                                  one_forward_per_graph_s=round(a.batch * base * 1e-6, 6),
                                  one_forward_on_the_unique_graphs_s=round(t_whole, 6)),
                table_row_reads=dict(per_row_gather=per_row, each_row_once=once, ratio=round(per_row / max(once, 1), 3)))
-    if gin:
-        per_row_dense = int(deg[prow].sum()) + int(prow.numel())
-        res["dense_rows"] = dict(per_row_hops=per_row_dense, each_row_once=int(engine.n_rows),
-                                 ratio=round(per_row_dense / max(int(engine.n_rows), 1), 3),
-                                 window_rows=int(ops.gin_graph_query_max_rows(a.hidden, a.hidden)),
-                                 largest_graph_rows=int(np.diff(engine._ptr).max()))
-    if gat:
-        per_row_att = int(deg[prow].sum()) + int(prow.numel())
-        res["attention_rows"] = dict(per_row_gather=per_row_att, each_row_once=int(engine.n_rows),
-                                     ratio=round(per_row_att / max(int(engine.n_rows), 1), 3),
-                                     window_rows=int(ops.gat_graph_query_max_rows(a.hidden)),
-                                     largest_graph_rows=int(np.diff(engine._ptr).max()))
-    if sage:
-        per_row_sage = int(deg[prow].sum()) + int(prow.numel())
-        res["sage_rows"] = dict(per_row_gather=per_row_sage, each_row_once=int(engine.n_rows),
-                                ratio=round(per_row_sage / max(int(engine.n_rows), 1), 3),
-                                window_rows=int(ops.sage_graph_query_max_rows(a.hidden)),
-                                largest_graph_rows=int(np.diff(engine._ptr).max()))
+    if gin or gat or sage:   # the layer-0 rows formed by the per-row kernel on every pooled row, against every row of the view once
+        block, per_row_key = {"gin": ("dense_rows", "per_row_hops"), "gat": ("attention_rows", "per_row_gather"),
+                              "sage": ("sage_rows", "per_row_gather")}[path.name]
+        formed = int(deg[prow].sum()) + int(prow.numel())
+        res[block] = {per_row_key: formed, "each_row_once": int(engine.n_rows), "ratio": round(formed / max(int(engine.n_rows), 1), 3),
+                      "window_rows": int(path.window_limit(engine.state(), model)), "largest_graph_rows": int(np.diff(engine._ptr).max())}
     out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.task}_{a.view}{'_' + a.layer if gin or gat or sage else ''}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
