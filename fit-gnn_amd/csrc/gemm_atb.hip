@@ -6,7 +6,7 @@
 // shape poorly (one call: 541 us at R = 90 549, M = N = 512; batched split-K through bmm: 201 us); its floor is the
 // one pass over both operands (371 MB, ~75 us).
 //
-// Arithmetic: each fp32 operand x is split into hi = its upper 16 bits as a bf16 (truncation, so x - hi is exact) and
+// Arithmetic: each fp32 operand x is split into hi = bf16_rne(x) (pack_bf16_rne below; x - hi is exact in fp32) and
 // lo = bf16_rne(x - hi); the product is hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the
 // same three-product scheme as the library's "high" fp32 GEMM; measured ~5e-6 relative error against fp64).
 //
