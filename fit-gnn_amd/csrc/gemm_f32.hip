@@ -71,6 +71,63 @@ __device__ __forceinline__ void load_slab(float4 (&r)[NV], const float *__restri
     }
 }
 
+// Row lists (the *_rows_* entry points): an operand's rows are read where they lie in a taller matrix, a_rows[i] for row i of a
+// k-minor a, b_rows[k] for row k of a k-major b -- the same 16-byte accesses at the same row stride as on a gathered copy, which is
+// then never made.  Kernels instantiated with IDX take them; either list may be NULL (the plain row).
+struct RowLists {
+    const int64_t *a_rows, *b_rows;
+};
+
+// k-minor slab through a list: a thread's rows are the same in every stage, so their places (element offsets) are looked up once
+// per tile.  A row past `lim` clamps its POSITION in the list to the last valid one, never the index read there.
+template <int NV, int THREADS>
+__device__ __forceinline__ void slab_row_offsets(long (&ro)[NV], const int64_t *__restrict__ list, long ld, long t0, long lim) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        long i = t0 + ((tid + p * THREADS) >> 3);
+        i = i < lim ? i : lim - 1;
+        ro[p] = (list ? (long)list[i] : i) * ld;
+    }
+}
+
+template <int NV, int THREADS>
+__device__ __forceinline__ void load_slab_rows(float4 (&r)[NV], const float *__restrict__ P, const long (&ro)[NV], long k0, long klim) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        const long k = k0 + 4 * ((tid + p * THREADS) & 7);
+        r[p] = k < klim ? *reinterpret_cast<const float4 *>(P + ro[p] + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// k-major slab through a list: the rows of the stage at k0, one per float4 of a thread (-1 for a k >= klim, which reads no entry of
+// the list).  A row of the slab is T / 4 float4 wide: from T = 256 on a wavefront holds one row, and its index is one scalar load.
+// (The row's element offset is formed at the load: formed here, 512 x 512 x 165 000 took 730 us against 707.)
+template <int T, int NV, int THREADS>
+__device__ __forceinline__ void slab_k_rows(long (&kx)[NV], const int64_t *__restrict__ list, long k0, long klim) {
+    constexpr int Q = T / 4;
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        long k;
+        if constexpr (Q % 64 == 0) k = k0 + (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 64 + p * THREADS) / Q;
+        else k = k0 + ((int)threadIdx.x + p * THREADS) / Q;
+        kx[p] = k < klim ? (list ? (long)list[k] : k) : -1;
+    }
+}
+
+template <int T, int NV, int THREADS>
+__device__ __forceinline__ void load_slab_k_rows(float4 (&r)[NV], const float *__restrict__ P, long ld, long t0, long lim, const long (&kx)[NV]) {
+    constexpr int Q = T / 4;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        long i = t0 + 4 * ((tid + p * THREADS) % Q);
+        i = i + 4 <= lim ? i : lim - 4;
+        r[p] = kx[p] >= 0 ? *reinterpret_cast<const float4 *>(P + kx[p] * ld + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 template <bool KM, int T, int NV, int THREADS>
 __device__ __forceinline__ void store_slab(const float4 (&r)[NV], float *lds) {
     const int tid = threadIdx.x;
@@ -113,15 +170,41 @@ struct StoreEpi {
     long row0;
     uint32_t epi;
     float p_drop;
+    int vec;   // J, ldc and c allow 16-byte stores of whole dropout groups: the store runs on rows (below)
 };
+
+// finish_elem on the four elements of one dropout group (idx a multiple of 4): the same arithmetic per element, ONE hash for the group
+// (dropout_keep_elem is dropout_keep on the half of that hash that holds the element's bits).
+__device__ __forceinline__ float4 finish_group(float4 x, const float (&bias)[4], uint32_t epi, float keep_scale, uint32_t thresh, uint64_t seed,
+                                               const uint8_t *__restrict__ mask, uint64_t idx) {
+    float y[4] = {x.x, x.y, x.z, x.w};
+    uint64_t bits = 0;
+    if ((epi & 4u) && !mask) bits = fitgnn::dropout_bits(seed, idx >> 2);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        y[q] = y[q] + ((epi & 1u) ? bias[q] : 0.f);
+        if (epi & 2u) y[q] = y[q] > 0.f ? y[q] : __expf(y[q]) - 1.0f;
+        if (epi & 4u) {
+            const bool keep = mask ? (mask[idx + q] != 0) : fitgnn::dropout_keep(bits, q, thresh);
+            y[q] = keep ? y[q] * keep_scale : 0.f;
+        }
+    }
+    return make_float4(y[0], y[1], y[2], y[3]);
+}
 
 // nchunks > 1: split over k.  Workgroup (chunk, tile) reduces k in [chunk * chunk_k, +chunk_k) and stores its tile into
 // partial[chunk] (an [I x J] matrix each); sum_chunks_kernel adds them in a fixed order.
 // EPI (nchunks == 1 only): the accumulators pass through `se` on their way out.
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb,
-                                                                   long I, int J, long K, float *__restrict__ C, long ldc, int tiles_i,
-                                                                   int tiles_j, int nchunks, long chunk_k, StoreEpi se) {
+// IDX: operand rows through `rl` (instantiations of their own: a launch without a list runs the code it ran before there were lists).
+// (Measured out: a bound on the octet loop that skips the k-octets of a last stage that hold no k < k_end -- K = 100: three of
+// four.  As a branch in the stage loop it costs every full-stage product 1-6 %, because hipcc then no longer reads an octet's
+// fragments under the previous octet's products; as code of its own beside the loop the 256 x 256 kernels spill; as a
+// launcher-selected instantiation the 165 000 x 512 x 100 table product went 255 -> 239 us, less than that launch's own 18-us
+// spread between calls.)
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI, bool IDX>
+__device__ __forceinline__ void gemm_f32_tile(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb, long I, int J, long K,
+                                              float *__restrict__ C, long ldc, int tiles_i, int tiles_j, int nchunks, long chunk_k,
+                                              const StoreEpi &se, const RowLists &rl) {
     using G = Geo<WM, WN, MI, NJ, AKM, BKM>;
     extern __shared__ __attribute__((aligned(16))) float lds_f[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -156,9 +239,26 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     float4 ra[G::NA], rb[G::NB];
+    // IDX: the places of a's rows (k-minor a: once per tile); the rows of b's next slab (k-major b: fetched one stage before the slab)
+    constexpr bool AIDX = IDX && !AKM, BIDX = IDX && BKM;
+    long a_ro[AIDX ? G::NA : 1], b_kx[BIDX ? G::NB : 1];
+    auto load_a = [&](long k0) {
+        if constexpr (AIDX) load_slab_rows<G::NA, G::THREADS>(ra, A, a_ro, k0, k_end);
+        else load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k0, k_end);
+    };
+    auto load_b = [&](long k0) {   // BIDX: b_kx holds the rows of the slab at k0
+        if constexpr (BIDX) {
+            load_slab_k_rows<G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, b_kx);
+        } else {
+            load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k0, k_end);
+        }
+    };
     if (nstage > 0) {
-        load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k_begin, k_end);
-        load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k_begin, k_end);
+        if constexpr (AIDX) slab_row_offsets<G::NA, G::THREADS>(a_ro, rl.a_rows, lda, i0, I);
+        if constexpr (BIDX) slab_k_rows<G::TJ, G::NB, G::THREADS>(b_kx, rl.b_rows, k_begin, k_end);
+        load_a(k_begin);
+        load_b(k_begin);
+        if constexpr (BIDX) slab_k_rows<G::TJ, G::NB, G::THREADS>(b_kx, rl.b_rows, k_begin + kBK, k_end);
         store_slab<AKM, G::TI, G::NA, G::THREADS>(ra, lds_f);
         store_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, lds_f + G::A_DW);
     }
@@ -194,14 +294,20 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
             float fa[MI][4], fb[NJ][4];
             read_frags(fa, fb, sa, sb, kk);
             multiply(fa, fb);
+            if constexpr (BIDX) {
+                // the rows of the slab after the one just requested, fetched HERE, behind the first octet's queued products: after a
+                // stage's barrier every wave of the workgroup issues its loads at once and the matrix pipe idles meanwhile, so what
+                // can wait (index arithmetic, the scalar loads and their lgkmcnt(0)) does not belong there
+                if (kk == 0) slab_k_rows<G::TJ, G::NB, G::THREADS>(b_kx, rl.b_rows, k_begin + (long)(s + 2) * kBK, k_end);
+            }
         }
     };
     for (int s = 0; s < nstage; ++s) {
         const bool more = s + 1 < nstage;   // workgroup-uniform
         if (more) {
             const long k0 = k_begin + (long)(s + 1) * kBK;
-            load_slab<AKM, G::TI, G::NA, G::THREADS>(ra, A, lda, i0, I, k0, k_end);
-            load_slab<BKM, G::TJ, G::NB, G::THREADS>(rb, B, ldb, j0, (long)J, k0, k_end);
+            load_a(k0);
+            load_b(k0);
         }
         products(s);
         if (more) {
@@ -220,6 +326,51 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
         const uint64_t seed = fitgnn::resolve_seed(se.seed, se.epi);
         const float keep_scale = (se.epi & FITGNN_EPI_DROPOUT) ? 1.0f / (1.0f - se.p_drop) : 1.0f;
         const uint32_t thresh = fitgnn::dropout_threshold(se.p_drop);
+        if (se.vec) {
+            // The store on rows.  A lane of the MFMA's C layout owns one column and 16 rows: stored from there, every element is a
+            // dword store with a 64-bit index and (by hash) a hash of its own.  The operand LDS is free after the last stage's
+            // barrier: per block row each wave passes its 32 x (32 NJ) accumulators through a region of its own (pitch + 8 dwords:
+            // the two half-waves of a write, four rows apart, land on different banks) and reads them back as float4 along the
+            // rows -- one original row per row, one hash and one 16-byte store per dropout group.  No barrier: a wave's LDS
+            // accesses execute in order and no other wave touches its region.
+            constexpr int W = 32 * NJ, P = W + 8, RPP = 256 / W, NP = 32 / RPP;   // rows per pass of 64 float4, passes per block row
+            static_assert(WM * WN * 32 * P * 4 <= G::LDS_BYTES, "the store regions fit the operand LDS");
+            float *reg = lds_f + wave * (32 * P);
+            const int c4 = lane % (W / 4), rsub = lane / (W / 4);
+            const long col = j0 + wn * W + 4 * c4;
+            const bool col_ok = col < J;   // (J % 4 == 0: the whole group)
+            float bv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bv[q] = ((se.epi & FITGNN_EPI_BIAS) && col_ok) ? se.bias[col + q] : 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(bv[q]));   // (waited for here, once: see the element store below)
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                const long rbase = i0 + wm * (32 * MI) + i * 32;
+                long orow[NP];
+#pragma unroll
+                for (int ps = 0; ps < NP; ++ps) {
+                    const long row = rbase + ps * RPP + rsub;
+                    orow[ps] = row < I ? (se.rows ? (long)se.rows[row] : se.row0 + row) : 0;
+                }
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) reg[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * P + j * 32 + (lane & 31)] = acc[i][j][r];
+#pragma unroll
+                for (int ps = 0; ps < NP; ++ps) asm volatile("" ::"v"(orow[ps]));
+#pragma unroll
+                for (int ps = 0; ps < NP; ++ps) {
+                    const int rr = ps * RPP + rsub;
+                    const long row = rbase + rr;
+                    const float4 x = *reinterpret_cast<const float4 *>(reg + rr * P + 4 * c4);
+                    if (row < I && col_ok)
+                        *reinterpret_cast<float4 *>(out + row * ldo + col) =
+                            finish_group(x, bv, se.epi, keep_scale, thresh, seed, se.mask, (uint64_t)orow[ps] * (uint64_t)J + (uint64_t)col);
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const long row0 = i0 + wm * (32 * MI) + i * 32 + 4 * (lane >> 5);
@@ -229,10 +380,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
                 const long row = row0 + (r & 3) + 8 * (r >> 2);
                 orow[r] = row < I ? (se.rows ? (long)se.rows[row] : se.row0 + row) : 0;
             }
+            // (a use outside the masked stores below: the loads above are waited for HERE, once.  Left to the first store that needs
+            // them, which is conditional, hipcc repeats its s_waitcnt vmcnt(0) in front of every later store -- and there it also
+            // waits for the stores before it: 824 -> 870 us on the 165 000 x 512 x 512 product)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(orow[r]));
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const long col = j0 + wn * (32 * NJ) + j * 32 + (lane & 31);
                 const float bias = ((se.epi & FITGNN_EPI_BIAS) && col < J) ? se.bias[col] : 0.f;
+                asm volatile("" ::"v"(bias));   // (as above)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const long row = row0 + (r & 3) + 8 * (r >> 2);
@@ -257,6 +414,23 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__r
             }
         }
     }
+}
+
+// The kernel as every launch without a row list runs it ...
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI>
+__global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb,
+                                                                   long I, int J, long K, float *__restrict__ C, long ldc, int tiles_i,
+                                                                   int tiles_j, int nchunks, long chunk_k, StoreEpi se) {
+    gemm_f32_tile<WM, WN, MI, NJ, AKM, BKM, EPI, false>(A, lda, B, ldb, I, J, K, C, ldc, tiles_i, tiles_j, nchunks, chunk_k, se,
+                                                        RowLists{nullptr, nullptr});
+}
+// ... and with row lists (IDX).  A kernel of its own, so that the instantiations above keep their names (LISTS = 1 always: it
+// keeps the two families' mangled names apart for tests/test_code_objects_*_cpu.py, which count them by pattern).
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI, int LISTS>
+__global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel_rows(const float *__restrict__ A, long lda, const float *__restrict__ B, long ldb,
+                                                                     long I, int J, long K, float *__restrict__ C, long ldc, int tiles_i,
+                                                                     int tiles_j, int nchunks, long chunk_k, StoreEpi se, RowLists rl) {
+    gemm_f32_tile<WM, WN, MI, NJ, AKM, BKM, EPI, true>(A, lda, B, ldb, I, J, K, C, ldc, tiles_i, tiles_j, nchunks, chunk_k, se, rl);
 }
 
 // out = sum over chunks of partial[chunk] in a fixed order (eight running sums: eight loads in flight per lane); EPI: the sums pass
@@ -387,34 +561,50 @@ Plan make_plan(long I, int J, long K, bool akm, bool bkm) {
     return p;
 }
 
-template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI>
+template <int WM, int WN, int MI, int NJ, bool AKM, bool BKM, bool EPI, bool IDX>
 int launch(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
-           const StoreEpi &se) {
+           const StoreEpi &se, const RowLists &rl) {
     using G = Geo<WM, WN, MI, NJ, AKM, BKM>;
     static std::atomic<uint64_t> lds_done{0};
-    if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>, G::LDS_BYTES, lds_done)) return rc;
+    if constexpr (!IDX) {
+        if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>, G::LDS_BYTES, lds_done)) return rc;
+    } else {
+        if (const int rc = fitgnn_lds_limit_once((const void *)gemm_f32_kernel_rows<WM, WN, MI, NJ, AKM, BKM, EPI, 1>, G::LDS_BYTES, lds_done)) return rc;
+    }
     unsigned grid;
     if (p.nchunks > 1) grid = (unsigned)(p.tiles_i * p.tiles_j * ((p.nchunks + 7) / 8 * 8));   // chunk = xcd + 8 * (slot / tiles)
     else grid = (unsigned)((p.tiles_i + 7) / 8 * 8 * p.tiles_j);
-    hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J,
-                       K, c, ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k, se);
+    if constexpr (!IDX)
+        hipLaunchKernelGGL((gemm_f32_kernel<WM, WN, MI, NJ, AKM, BKM, EPI>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I, J, K, c,
+                           ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k, se);
+    else
+        hipLaunchKernelGGL((gemm_f32_kernel_rows<WM, WN, MI, NJ, AKM, BKM, EPI, 1>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, a, lda, b, ldb, I,
+                           J, K, c, ldc, p.tiles_i, p.tiles_j, p.nchunks, p.chunk_k, se, rl);
     return (int)hipGetLastError();
 }
 
-template <bool AKM, bool BKM, bool EPI = false>
-int launch_shape(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
-                 const StoreEpi &se = StoreEpi{}) {
+template <bool AKM, bool BKM, bool EPI, bool IDX>
+int launch_shape_as(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
+                     const StoreEpi &se, const RowLists &rl) {
     if constexpr (AKM && BKM) {   // make_plan picks the 64 x 512 tile for this pair only (its k-minor LDS image would not fit)
-        if (p.shape == S64x512) return launch<1, 4, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        if (p.shape == S64x512) return launch<1, 4, 2, 4, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
     }
     switch (p.shape) {
-        case S256x128: return launch<4, 1, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
-        case S128: return launch<2, 2, 2, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
-        case S64x128: return launch<2, 2, 1, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
-        case S128x64: return launch<4, 1, 1, 2, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
-        case S64x64: return launch<2, 2, 1, 1, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
-        default: return launch<4, 2, 2, 4, AKM, BKM, EPI>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se);
+        case S256x128: return launch<4, 1, 2, 4, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+        case S128: return launch<2, 2, 2, 2, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+        case S64x128: return launch<2, 2, 1, 2, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+        case S128x64: return launch<4, 1, 1, 2, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+        case S64x64: return launch<2, 2, 1, 1, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+        default: return launch<4, 2, 2, 4, AKM, BKM, EPI, IDX>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
     }
+}
+
+// with a row list the IDX instantiation, without one the kernel as it has always been
+template <bool AKM, bool BKM, bool EPI = false>
+int launch_shape(const Plan &p, const float *a, long lda, const float *b, long ldb, long I, int J, long K, float *c, long ldc, hipStream_t s,
+                 const StoreEpi &se = StoreEpi{}, const RowLists &rl = RowLists{nullptr, nullptr}) {
+    if (rl.a_rows || rl.b_rows) return launch_shape_as<AKM, BKM, EPI, true>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
+    return launch_shape_as<AKM, BKM, EPI, false>(p, a, lda, b, ldb, I, J, K, c, ldc, s, se, rl);
 }
 
 }  // namespace
@@ -438,8 +628,18 @@ extern "C" int fitgnn_gemm_exact_plan(int64_t I, int32_t J, int64_t K, int32_t a
 
 extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmajor, const float *b, int64_t ldb, int32_t b_kmajor,
                                      int64_t I, int32_t J, int64_t K, float *c, int64_t ldc, void *workspace, void *stream) {
+    return fitgnn_gemm_exact_rows_f32(a, lda, a_kmajor, nullptr, b, ldb, b_kmajor, nullptr, I, J, K, c, ldc, workspace, stream);
+}
+
+extern "C" int fitgnn_gemm_exact_rows_f32(const float *a, int64_t lda, int32_t a_kmajor, const int64_t *a_rows, const float *b, int64_t ldb,
+                                          int32_t b_kmajor, const int64_t *b_rows, int64_t I, int32_t J, int64_t K, float *c, int64_t ldc,
+                                          void *workspace, void *stream) {
     if (I <= 0 || J <= 0 || K <= 0 || ldc < J) return FITGNN_E_BADARG;
     if (!a || !b || !c) return FITGNN_E_BADARG;
+    if ((a_rows && a_kmajor) || (b_rows && !b_kmajor)) return FITGNN_E_BADARG;   // a list names the rows of a k-minor a / a k-major b
+    if ((((uintptr_t)a_rows | (uintptr_t)b_rows) % 8) != 0) return FITGNN_E_ALIGN;
+    const RowLists rl{a_rows, b_rows};
+    const StoreEpi none{};
     // 16-byte accesses along the contiguous dimension of each operand
     const int64_t a_inner = a_kmajor ? I : K, b_inner = b_kmajor ? (int64_t)J : K;
     if (a_inner < 4 || b_inner < 4 || (a_inner % 4) != 0 || (b_inner % 4) != 0 || lda < a_inner || ldb < b_inner || (lda % 4) != 0 ||
@@ -455,14 +655,16 @@ extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmaj
         pm.tiles_i = (int)(p.main_rows / kShape[p.shape].ti);
         pr.tiles_i = p.rem_tiles_i; pr.nchunks = p.rem_chunks; pr.chunk_k = p.rem_chunk_k;
         const long rem_rows = (long)I - p.main_rows;
-        const float *a_rem = a + p.main_rows * (long)lda;
+        // the tail's rows: a moved forward by main_rows -- or, through a list, the list
+        const float *a_rem = a_rows ? a : a + p.main_rows * (long)lda;
+        const RowLists rl_rem{a_rows ? a_rows + p.main_rows : nullptr, b_rows};
         int rc;
         if (b_kmajor) {
-            rc = launch_shape<false, true>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s);
-            if (!rc) rc = launch_shape<false, true>(pr, a_rem, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s);
+            rc = launch_shape<false, true>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s, none, rl);
+            if (!rc) rc = launch_shape<false, true>(pr, a_rem, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s, none, rl_rem);
         } else {
-            rc = launch_shape<false, false>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s);
-            if (!rc) rc = launch_shape<false, false>(pr, a_rem, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s);
+            rc = launch_shape<false, false>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s, none, rl);
+            if (!rc) rc = launch_shape<false, false>(pr, a_rem, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s, none, rl_rem);
         }
         if (rc) return rc;
         const long IJ = rem_rows * J;
@@ -477,9 +679,9 @@ extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmaj
         dst = (float *)workspace;
     }
     int rc;
-    if (a_kmajor) rc = launch_shape<true, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s);
-    else if (b_kmajor) rc = launch_shape<false, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s);
-    else rc = launch_shape<false, false>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s);
+    if (a_kmajor) rc = launch_shape<true, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s, none, rl);
+    else if (b_kmajor) rc = launch_shape<false, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s, none, rl);
+    else rc = launch_shape<false, false>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, dst, ldd, s, none, rl);
     if (rc) return rc;
     if (p.nchunks > 1) {
         const long IJ = (long)I * J;
@@ -496,10 +698,17 @@ extern "C" int fitgnn_gemm_exact_f32(const float *a, int64_t lda, int32_t a_kmaj
 extern "C" int fitgnn_gemm_exact_epi_f32(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t I, int32_t J, int64_t K, float *c,
                                          int64_t ldc, const int64_t *rows, const float *bias, uint32_t epilogue, float p_drop, uint64_t seed,
                                          const uint8_t *mask, void *workspace, void *stream) {
+    return fitgnn_gemm_exact_epi_rows_f32(a, lda, nullptr, b, ldb, I, J, K, c, ldc, rows, bias, epilogue, p_drop, seed, mask, workspace, stream);
+}
+
+extern "C" int fitgnn_gemm_exact_epi_rows_f32(const float *a, int64_t lda, const int64_t *a_rows, const float *b, int64_t ldb, int64_t I,
+                                              int32_t J, int64_t K, float *c, int64_t ldc, const int64_t *rows, const float *bias,
+                                              uint32_t epilogue, float p_drop, uint64_t seed, const uint8_t *mask, void *workspace,
+                                              void *stream) {
     if (I <= 0 || J <= 0 || K <= 0 || ldc < J) return FITGNN_E_BADARG;
     if (!a || !b || !c) return FITGNN_E_BADARG;
     if (K < 4 || (K % 4) != 0 || lda < K || ldb < K || (lda % 4) != 0 || (ldb % 4) != 0) return FITGNN_E_BADARG;
-    if ((((uintptr_t)a | (uintptr_t)b) % 16) != 0) return FITGNN_E_ALIGN;
+    if ((((uintptr_t)a | (uintptr_t)b) % 16) != 0 || ((uintptr_t)a_rows % 8) != 0) return FITGNN_E_ALIGN;
     if (epilogue & ~(FITGNN_EPI_BIAS | FITGNN_EPI_ELU | FITGNN_EPI_DROPOUT | FITGNN_EPI_SEED_DEVICE)) return FITGNN_E_BADARG;
     if ((epilogue & (FITGNN_EPI_ELU | FITGNN_EPI_DROPOUT)) && (J % 4) != 0) return FITGNN_E_BADARG;   // (bias alone: any J)
     if ((epilogue & FITGNN_EPI_BIAS) && !bias) return FITGNN_E_BADARG;
@@ -507,15 +716,19 @@ extern "C" int fitgnn_gemm_exact_epi_f32(const float *a, int64_t lda, const floa
     const Plan p = make_plan((long)I, J, (long)K, false, false);
     if (p.nchunks > 1) return FITGNN_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    StoreEpi se{rows, bias, mask, seed, 0, epilogue, p_drop};
-    if (p.main_rows == 0) return launch_shape<false, false, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, c, (long)ldc, s, se);
+    // (J % 4 != 0 -- a head's bias-only store -- and a c that cannot take 16-byte stores keep the store by element)
+    const int vec = (J % 4) == 0 && (ldc % 4) == 0 && ((uintptr_t)c % 16) == 0;
+    StoreEpi se{rows, bias, mask, seed, 0, epilogue, p_drop, vec};
+    const RowLists rl{a_rows, nullptr};
+    if (p.main_rows == 0) return launch_shape<false, false, true>(p, a, (long)lda, b, (long)ldb, (long)I, J, (long)K, c, (long)ldc, s, se, rl);
     if (!workspace || ((uintptr_t)workspace % 16) != 0) return FITGNN_E_BADARG;
     Plan pm = p, pr = p;
     pm.tiles_i = (int)(p.main_rows / kShape[p.shape].ti);
     pr.tiles_i = p.rem_tiles_i; pr.nchunks = p.rem_chunks; pr.chunk_k = p.rem_chunk_k;
     const long rem_rows = (long)I - p.main_rows;
-    int rc = launch_shape<false, false, true>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s, se);
-    if (!rc) rc = launch_shape<false, false>(pr, a + p.main_rows * (long)lda, (long)lda, b, (long)ldb, rem_rows, J, (long)K, (float *)workspace, (long)J, s);
+    int rc = launch_shape<false, false, true>(pm, a, (long)lda, b, (long)ldb, p.main_rows, J, (long)K, c, (long)ldc, s, se, rl);
+    if (!rc) rc = launch_shape<false, false>(pr, a_rows ? a : a + p.main_rows * (long)lda, (long)lda, b, (long)ldb, rem_rows, J, (long)K,
+                                             (float *)workspace, (long)J, s, StoreEpi{}, RowLists{a_rows ? a_rows + p.main_rows : nullptr, nullptr});
     if (rc) return rc;
     if (rows) se.rows = rows + p.main_rows;
     se.row0 = p.main_rows;

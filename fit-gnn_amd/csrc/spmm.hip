@@ -433,7 +433,17 @@ __global__ __launch_bounds__(kThreads, BWD ? 4 : TWO ? 6 : XROW ? 7 : 7) void sp
 #endif
     SSTAMP(s_begin);
     const fitgnn_block_t blk = blocks[b];
-    if (blk.row_end <= blk.row_begin) return;
+    if (blk.row_end <= blk.row_begin) {
+        // a padding record stores no row of Y; its row of column sums is zero, written here so that the caller need not fill col_part
+        if ((BWD || TWO) && col_part && threadIdx.x < 64) {
+            const int c0 = slab * 256 + (int)threadIdx.x * 4;
+            if (c0 + 4 <= H) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) col_part[(int64_t)b * H + c0 + i] = 0.f;   // (as write_col_part: no alignment asked of col_part)
+            }
+        }
+        return;
+    }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col0 = slab * 256 + lane * 4;

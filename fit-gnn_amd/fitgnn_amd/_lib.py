@@ -95,6 +95,9 @@ SIGNATURES = {
     "fitgnn_gemm_exact_plan": (ctypes.c_int, [c_i64, c_i32, c_i64, c_i32, c_i32, ptr, ptr, ptr]),
     "fitgnn_gemm_exact_epi_f32": (ctypes.c_int, [ptr, c_i64, ptr, c_i64, c_i64, c_i32, c_i64, ptr, c_i64, ptr, ptr, c_u32, c_f32, c_u64, ptr, ptr,
                                                  ptr]),
+    "fitgnn_gemm_exact_rows_f32": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, ptr, c_i64, c_i32, ptr, c_i64, c_i32, c_i64, ptr, c_i64, ptr, ptr]),
+    "fitgnn_gemm_exact_epi_rows_f32": (ctypes.c_int, [ptr, c_i64, ptr, ptr, c_i64, c_i64, c_i32, c_i64, ptr, c_i64, ptr, ptr, c_u32, c_f32,
+                                                      c_u64, ptr, ptr, ptr]),
     "fitgnn_gemm_nt_presplit_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_gemm_nt_presplit_f32": (ctypes.c_int, [ptr, c_i64, c_i64, c_i32, c_i32, c_i32, ptr, ptr]),
     "fitgnn_gemm_nt_pre_f32": (ctypes.c_int, [ptr, c_i64, ptr, c_i64, c_i32, c_i32, ptr, c_i64, ptr]),

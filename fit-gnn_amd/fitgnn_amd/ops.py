@@ -78,6 +78,10 @@ class OpConfig:
     fused_gemm_epilogue  the store epilogue of a dense part evaluated on kept rows (bias, ELU, dropout of _dense_rows; the head's bias of
                      _head_rows_fwd) in the exact fp32 product's own store (fitgnn_gemm_exact_epi_f32) instead of a pass over the
                      product's output (fitgnn_epilogue_fwd_rows_f32 / a broadcast add) after it (A/B switch; identical bits).
+    rows_in_gemm     the dense part of a layer evaluated on kept rows reads those rows where they lie in the aggregate A_hat X, through the
+                     row list of the exact product (fitgnn_gemm_exact_epi_rows_f32 forward, fitgnn_gemm_exact_rows_f32 for dW), instead
+                     of gathering them into a compact matrix first; the aggregate is then what the backward keeps (A/B switch; identical
+                     bits).  Applies under gemm_precision "exact" with the epilogue fused into the store (fused_gemm_epilogue).
     fused_pool_head  lt1(global_mean_pool(x[rows])) of the graph-level regression models as one launch each way (MeanPoolHead) instead
                      of pool, scale, library product and bias add (A/B switch).
     grad_sink        None, or an object with `.view(data_ptr)` -> the slice of a "fresh gradients" buffer that belongs to the parameter stored at
@@ -89,12 +93,12 @@ class OpConfig:
     seed_bank        None, or a SeedBank supplying device-resident dropout seeds (steps captured in a hipGraph)."""
     __slots__ = ("gemm_precision", "atb_kernel", "nt_kernel", "nt_presplit", "fuse_dx_epilogue", "fold_backward",
                  "dedup_gather", "pad_table_min_k", "split_large_blocks", "compact_head_backward", "last_layer_on_loss_rows",
-                 "compact_rows_kernel", "stream_kernel", "two_hop_backward", "narrow_input_first", "fused_pool_head", "fused_gemm_epilogue", "pooled_rows_last_layer", "rows_kernel_min_rows", "appnp_in_lds", "appnp_blocks", "appnp_sliced", "grad_sink", "profile", "profile_gemm",
+                 "compact_rows_kernel", "stream_kernel", "two_hop_backward", "narrow_input_first", "fused_pool_head", "fused_gemm_epilogue", "rows_in_gemm", "pooled_rows_last_layer", "rows_kernel_min_rows", "appnp_in_lds", "appnp_blocks", "appnp_sliced", "grad_sink", "profile", "profile_gemm",
                  "profile_fused", "seed_bank")
 
     def __init__(self, gemm_precision="exact", atb_kernel=True, nt_kernel=True, nt_presplit=True, fuse_dx_epilogue=True,
                  fold_backward=False, dedup_gather=True, pad_table_min_k=0, split_large_blocks=True, compact_head_backward=True,
-                 last_layer_on_loss_rows=True, compact_rows_kernel=True, stream_kernel=False, two_hop_backward=True, narrow_input_first=True, fused_pool_head=True, fused_gemm_epilogue=True, pooled_rows_last_layer=True, rows_kernel_min_rows=32768, appnp_in_lds=True, appnp_blocks=True, appnp_sliced=True, grad_sink=None,
+                 last_layer_on_loss_rows=True, compact_rows_kernel=True, stream_kernel=False, two_hop_backward=True, narrow_input_first=True, fused_pool_head=True, fused_gemm_epilogue=True, rows_in_gemm=True, pooled_rows_last_layer=True, rows_kernel_min_rows=32768, appnp_in_lds=True, appnp_blocks=True, appnp_sliced=True, grad_sink=None,
                  profile=None, profile_gemm=None, profile_fused=None, seed_bank=None):
         if gemm_precision not in ("exact", "high", "highest"):
             raise ValueError(f"gemm_precision {gemm_precision!r}: 'exact', 'high' or 'highest'")
@@ -104,7 +108,7 @@ class OpConfig:
         self.compact_head_backward, self.last_layer_on_loss_rows = compact_head_backward, last_layer_on_loss_rows
         self.compact_rows_kernel, self.stream_kernel, self.two_hop_backward = compact_rows_kernel, stream_kernel, two_hop_backward
         self.narrow_input_first, self.fused_pool_head, self.grad_sink = narrow_input_first, fused_pool_head, grad_sink
-        self.fused_gemm_epilogue = fused_gemm_epilogue
+        self.fused_gemm_epilogue, self.rows_in_gemm = fused_gemm_epilogue, rows_in_gemm
         self.pooled_rows_last_layer, self.rows_kernel_min_rows = pooled_rows_last_layer, int(rows_kernel_min_rows)
         self.appnp_in_lds, self.appnp_blocks, self.appnp_sliced = appnp_in_lds, appnp_blocks, appnp_sliced
         self.profile, self.profile_gemm, self.profile_fused, self.seed_bank = profile, profile_gemm, profile_fused, seed_bank
@@ -171,23 +175,38 @@ def _exact(cfg, a, b):
     return cfg.gemm_precision == "exact" and _rows_16b(a) and _rows_16b(b)
 
 
-def gemm_exact(a, b, form, cfg=DEFAULT, out=None):
-    """One product of a Linear in exact fp32 on the fp32 MFMA (fitgnn_gemm_exact_f32, csrc/gemm_f32.hip):
+def _row_list(rows):
+    """A row list as the exact product reads it: contiguous int64 on the device."""
+    return (rows if rows.dtype == torch.int64 else rows.long()).contiguous()
+
+
+def gemm_exact(a, b, form, cfg=DEFAULT, out=None, a_rows=None, b_rows=None):
+    """One product of a Linear in exact fp32 on the fp32 MFMA (fitgnn_gemm_exact_rows_f32, csrc/gemm_f32.hip):
         form "nt": a [I, K] @ b [J, K]^T   (forward x W^T)
              "nn": a [I, K] @ b [K, J]     (grad_x = dH W: W is read as it lies, no transposed copy)
-             "tn": a [K, I]^T @ b [K, J]   (grad_W = dH^T x: reduction over the rows, split over k with a fixed-order sum)."""
+             "tn": a [K, I]^T @ b [K, J]   (grad_W = dH^T x: reduction over the rows, split over k with a fixed-order sum).
+    a_rows (int64 [I]; nt, nn): the product's a is a[a_rows], read where its rows lie.  b_rows (int64 [K]; nn, tn): its b is b[b_rows]."""
     L = _lib.lib()
+    if form not in ("nt", "nn", "tn"):
+        raise ValueError(form)
+    akm, bkm = (1 if form == "tn" else 0), (0 if form == "nt" else 1)
+    assert (a_rows is None or not akm) and (b_rows is None or bkm), "a row list names the rows of a k-minor a / a k-major b"
+    if a_rows is not None:
+        a_rows = _row_list(a_rows)
+    if b_rows is not None:
+        b_rows = _row_list(b_rows)
+    _lib.require_cuda(a, b, a_rows, b_rows)
+    a0 = a.shape[0] if a_rows is None else int(a_rows.numel())   # rows of the product's operands
+    b0 = b.shape[0] if b_rows is None else int(b_rows.numel())
     if form == "nt":
-        (I, K), J, akm, bkm = a.shape, b.shape[0], 0, 0
+        I, K, J = a0, a.shape[1], b0
         assert b.shape[1] == K
     elif form == "nn":
-        (I, K), J, akm, bkm = a.shape, b.shape[1], 0, 1
-        assert b.shape[0] == K
-    elif form == "tn":
-        (K, I), J, akm, bkm = a.shape, b.shape[1], 1, 1
-        assert b.shape[0] == K
+        I, K, J = a0, a.shape[1], b.shape[1]
+        assert b0 == K
     else:
-        raise ValueError(form)
+        K, I, J = a0, a.shape[1], b.shape[1]
+        assert b0 == K
     if out is None:
         out = torch.empty((I, J), dtype=torch.float32, device=a.device)
     else:   # the caller's [I, J] buffer (rows may be strided: e.g. the head of a taller matrix)
@@ -195,39 +214,43 @@ def gemm_exact(a, b, form, cfg=DEFAULT, out=None):
     wb = int(L.fitgnn_gemm_exact_workspace_bytes(I, J, K, akm, bkm))
     ws = torch.empty(wb // 4, dtype=torch.float32, device=a.device) if wb else None
     ev = _gemm_events(cfg, "gemm_f32_kernel[%s]" % form, 2.0 * I * J * K)
-    rc = L.fitgnn_gemm_exact_f32(_lib.dptr(a), a.stride(0), akm, _lib.dptr(b), b.stride(0), bkm, I, J, K, _lib.dptr(out), out.stride(0),
-                                 _lib.dptr(ws), _lib.stream_ptr(a.device))
+    rc = L.fitgnn_gemm_exact_rows_f32(_lib.dptr(a), a.stride(0), akm, _lib.dptr(a_rows), _lib.dptr(b), b.stride(0), bkm, _lib.dptr(b_rows),
+                                      I, J, K, _lib.dptr(out), out.stride(0), _lib.dptr(ws), _lib.stream_ptr(a.device))
     _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_exact_f32")
+    _lib.check(rc, "fitgnn_gemm_exact_rows_f32")
     return out
 
 
-def gemm_exact_epi(a, b, rows, bias, epilogue, p=0.0, seed=0, mask=None, cfg=DEFAULT):
-    """dropout(ELU(a [I, K] @ b [J, K]^T + bias)) with the epilogue in the exact product's store (fitgnn_gemm_exact_epi_f32): row i
+def gemm_exact_epi(a, b, rows, bias, epilogue, p=0.0, seed=0, mask=None, cfg=DEFAULT, a_rows=None):
+    """dropout(ELU(a [I, K] @ b [J, K]^T + bias)) with the epilogue in the exact product's store (fitgnn_gemm_exact_epi_rows_f32): row i
     takes the dropout pattern of original row rows[i] (rows None: i).  Bit for bit gemm_exact(a, b, "nt") followed by
-    epilogue_fwd_rows_.  None when the product's plan splits k (the kernel has no single store to put the epilogue in): the caller
-    runs the two launches."""
+    epilogue_fwd_rows_.  a_rows (int64 [I]): the product's a is a[a_rows], read where its rows lie.  None when the product's plan
+    splits k (the kernel has no single store to put the epilogue in): the caller runs the two launches."""
     L = _lib.lib()
-    (I, K), J = a.shape, b.shape[0]
+    K, J = a.shape[1], b.shape[0]
+    I = a.shape[0] if a_rows is None else int(a_rows.numel())
     assert b.shape[1] == K
     shape, nchunks, main_rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
     _lib.check(L.fitgnn_gemm_exact_plan(I, J, K, 0, 0, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows)),
                "fitgnn_gemm_exact_plan")
     if nchunks.value > 1:
         return None
-    _lib.require_cuda(a, b, rows, bias, mask)
     seed, epilogue = _seed_arg(seed, epilogue)
+    same = a_rows is rows
     if rows is not None:
-        rows = (rows if rows.dtype == torch.int64 else rows.long()).contiguous()
+        rows = _row_list(rows)
+    if a_rows is not None:
+        a_rows = rows if same else _row_list(a_rows)
+    _lib.require_cuda(a, b, rows, a_rows, bias, mask)
     out = torch.empty((I, J), dtype=torch.float32, device=a.device)
     wb = int(L.fitgnn_gemm_exact_workspace_bytes(I, J, K, 0, 0))
     ws = torch.empty(wb // 4, dtype=torch.float32, device=a.device) if wb else None
     ev = _gemm_events(cfg, "gemm_f32_kernel[nt+epi]", 2.0 * I * J * K)
-    rc = L.fitgnn_gemm_exact_epi_f32(_lib.dptr(a), a.stride(0), _lib.dptr(b), b.stride(0), I, J, K, _lib.dptr(out), out.stride(0),
-                                     _lib.dptr(rows), _lib.dptr(None if bias is None else _f32c(bias)), epilogue, float(p), seed,
-                                     _lib.dptr(mask), _lib.dptr(ws), _lib.stream_ptr(a.device))
+    rc = L.fitgnn_gemm_exact_epi_rows_f32(_lib.dptr(a), a.stride(0), _lib.dptr(a_rows), _lib.dptr(b), b.stride(0), I, J, K, _lib.dptr(out),
+                                          out.stride(0), _lib.dptr(rows), _lib.dptr(None if bias is None else _f32c(bias)), epilogue,
+                                          float(p), seed, _lib.dptr(mask), _lib.dptr(ws), _lib.stream_ptr(a.device))
     _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_exact_epi_f32")
+    _lib.check(rc, "fitgnn_gemm_exact_epi_rows_f32")
     return out
 
 
@@ -451,12 +474,16 @@ def head_weight_grad_rows(dy_c, out_c, cfg=DEFAULT):
     return mm_at_b(dy_c, out_c, cfg)
 
 
-def mm_at_b(a, b, cfg=DEFAULT, out=None):
+def mm_at_b(a, b, cfg=DEFAULT, out=None, b_rows=None):
     """a^T @ b for tall operands a [R, M], b [R, N] (the weight-gradient product dH^T @ X, reduction over all R
     rows): the hand-written split-K kernel where it applies.  Otherwise the library: hipBLASLt serves this huge-K /
     small-MN shape poorly as one GEMM (541 us for R = 90k, M = N = 512); as a batched GEMM over ~1400-row slices plus
     a sum of the partial products it takes 394 us -- split-K by hand.  The partials are summed in a fixed order:
-    reproducible."""
+    reproducible.  b_rows (int64 [R]): b is b[b_rows] -- read where its rows lie by the exact kernel, gathered for the others."""
+    if b_rows is not None:
+        if _exact(cfg, a, b):
+            return gemm_exact(a, b, "tn", cfg, out=out, b_rows=b_rows)
+        b = b.index_select(0, b_rows)
     R = a.shape[0]
     if out is not None:   # the caller's buffer (a gradient sink): the exact kernel stores there, other paths are copied
         if _exact(cfg, a, b):
@@ -1000,9 +1027,9 @@ def spmm_two_hop_blocks(g, Xc, prev, rows, pos, link, cfg=DEFAULT, profile_kind=
     if side.small_tiles.shape[0]:
         spmm_raw(side.rowptr, side.col, side.val, side.small_tiles, ZT, g.n, window_rows=g.window_rows, out=Y, cfg=quiet, xrow=ix["zrow"])
     n_blocks = int(side.blocks.shape[0])
-    # one partial row of column sums per block + one for the rows outside the blocks (their dZ sits in the table)
-    # (zeros, not uninitialised memory: the two-hop kernel leaves rows of `part` unwritten -- poisoned with NaN, conv.0.bias's gradient is NaN)
-    part = torch.zeros((n_blocks + 1, H), dtype=torch.float32, device=dev) if link.want_db else None
+    # one partial row of column sums per block + one for the rows outside the blocks (their dZ sits in the table).  No fill: the
+    # kernel writes the row of every record, a padding record's as zeros (FITGNN_POISON=1 hands out NaN, which is how the tests check it)
+    part = _scratch((n_blocks + 1, H), dev) if link.want_db else None
     _lib.check(L.fitgnn_spmm_two_hop_blocks_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(ZT), ZT.stride(0),
                                                 _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(side.blocks), n_blocks, _lib.dptr(side.long_rows),
                                                 _lib.dptr(ix["zrow"]), _lib.dptr(ix["zcol"]), _lib.dptr(prev), _lib.dptr(Xc), Xc.stride(0), n_sel,
@@ -1012,6 +1039,8 @@ def spmm_two_hop_blocks(g, Xc, prev, rows, pos, link, cfg=DEFAULT, profile_kind=
     if link.want_db:
         if ix["tile_zt"].numel():
             torch.sum(ZT.index_select(0, ix["tile_zt"]), 0, out=part[n_blocks])
+        else:
+            part[n_blocks].zero_()
         db = _fold_partials(part, dev, st)
     if ev is not None:
         ev[1].record()
@@ -1057,12 +1086,10 @@ def spmm_graph_dz(g, X, prev, epilogue, p=0.0, seed=0, mask=None, want_db=True, 
     n_tiles = int(tiles.shape[0])
     n_blocks = int(side.blocks.shape[0]) if split else 0
     Y = torch.empty((g.n, H), dtype=torch.float32, device=dev)
-    # (zeros, not uninitialised memory: the whole-subgraph kernel writes partial rows for some of its segments only -- with the buffer
-    # poisoned with NaN 17 of 24 block rows of a split test graph stay NaN and 19 GPU tests fail; the tile kernel writes every row.
-    # The fill is a 4.6-us launch of a 180-us batch step at S-qm9)
-    # Tiles only (a batch of small graphs: every S-qm9 step): no fill -- FITGNN_POISON=1 hands out NaN instead, which is how the tests
-    # check that every row is written.
-    part = (_scratch((n_tiles, H), dev) if n_blocks == 0 else torch.zeros((n_tiles + n_blocks, H), dtype=torch.float32, device=dev)) if want_db else None
+    # No fill: the tile kernel writes the partial row of every tile, the whole-subgraph kernel that of every record (a padding
+    # record's, which it otherwise skips, as zeros) -- FITGNN_POISON=1 hands out NaN instead, which is how the tests check that every
+    # row is written.
+    part = _scratch((n_tiles + n_blocks, H), dev) if want_db else None
     st = _lib.stream_ptr(dev)
     ev = None
     if cfg.profile is not None:
@@ -2065,6 +2092,20 @@ def _dense_rows(AHc, W, b, rows, ep, cfg):
     return epilogue_fwd_rows_(outc, rows, b, ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask)
 
 
+def _dense_rows_of(AH, W, b, rows, ep, cfg):
+    """_dense_rows on rows `rows` of the aggregate AH [R, K]: (outc, kept, through).  Under the exact policy with the epilogue in the
+    product's store (OpConfig.rows_in_gemm) the product reads those rows where they lie in AH -- the same 16-byte accesses at the same
+    row stride as on a gathered copy, which is not made: kept = AH, through = True, and the backward's dW = dZc^T AH[rows] reads it the
+    same way (mm_at_b(..., b_rows=rows)).  Otherwise (the other policies; a plan split over k, which runs unfused) the rows are
+    gathered: kept = AH[rows], through = False."""
+    if cfg.rows_in_gemm and cfg.fused_gemm_epilogue and _exact(cfg, AH, W) and W.shape[0] % 4 == 0:
+        outc = gemm_exact_epi(AH, W, rows, b, ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg, a_rows=rows)
+        if outc is not None:
+            return outc, AH, True
+    AHc = AH.index_select(0, rows)                                   # [n, K]
+    return _dense_rows(AHc, W, b, rows, ep, cfg), AHc, False
+
+
 def _head_rows_fwd(outc, Wl, bl, rows, n_total, compact_out, g, cfg):
     """The head y = out Wl^T + bl on the kept rows: [len(rows), C] in the order of `rows` (compact_out), else [n_total, C], zero on every
     other row."""
@@ -2147,20 +2188,20 @@ class FusedGCNLastLayerRows(torch.autograd.Function):
         X = _f32c(X)
         rows = rows if rows.dtype == torch.int64 else rows.long()
         ctx.link_in, ctx.compact_out = link_in, bool(compact_out)
+        ep = _Epilogue(b is not None, p, training, seed, mask)
         if fwd_sub is not None:
             f = fwd_sub.f
             AHc = spmm_raw(f.rowptr, f.col, f.val, f.tiles, X, fwd_sub.m, window_rows=fwd_sub.window_rows, cfg=cfg, profile_kind="rows_fwd")
+            outc, through = _dense_rows(AHc, W, b, rows, ep, cfg), False   # [n, H]
         else:
             AH = spmm_graph(g, X, cfg=cfg)                               # [R, K]
-            AHc = AH.index_select(0, rows)                               # [n, K]
+            outc, AHc, through = _dense_rows_of(AH, W, b, rows, ep, cfg)   # AHc: AH itself (read through `rows`) or AH[rows]
             del AH
-        ep = _Epilogue(b is not None, p, training, seed, mask)
-        outc = _dense_rows(AHc, W, b, rows, ep, cfg)                     # [n, H]
         y = _head_rows_fwd(outc, Wl, bl, rows, g.n, compact_out, g, cfg)
         # X (the previous layer's output) is kept only when that layer's epilogue backward is applied here, in the SpMM's store
         keep_x = link_in is not None and cfg.fuse_dx_epilogue and X.shape[1] % 4 == 0
         ctx.save_for_backward(W, Wl, AHc, outc, rows, ep.mask, X if keep_x else None)
-        ctx.g, ctx.ep, ctx.has_bias, ctx.has_bl, ctx.cfg = g, ep, b is not None, bl is not None, cfg
+        ctx.g, ctx.ep, ctx.has_bias, ctx.has_bl, ctx.cfg, ctx.through = g, ep, b is not None, bl is not None, cfg, through
         ctx.ptrs = _addresses(W, b, Wl, bl)
         return y
 
@@ -2173,7 +2214,7 @@ class FusedGCNLastLayerRows(torch.autograd.Function):
         dZc, db, dWl, dbl = _head_rows_bwd(dy, rows, ctx.compact_out, outc, Wl, ctx.ep, mask, ctx.has_bias, ctx.needs_input_grad[3],
                                            ctx.has_bl and ctx.needs_input_grad[4], cfg, sink, pb=pb if ctx.needs_input_grad[2] else None,
                                            pWl=pWl, pbl=pbl)
-        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW))) if ctx.needs_input_grad[1] else None   # [H, K]
+        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW), b_rows=rows if ctx.through else None)) if ctx.needs_input_grad[1] else None   # [H, K]
         dX = _rows_adjoint(ctx.g, dZc, W, rows, ctx.link_in, Xprev, cfg, zero_tail=True, two_hop=True) if ctx.needs_input_grad[0] else None
         return dX, dW, (db if ctx.has_bias else None), dWl, dbl, None, None, None, None, None, None, None, None, None, None
 
@@ -2192,9 +2233,8 @@ class FusedGCNLayerRows(torch.autograd.Function):
     def forward(ctx, X, W, b, g, p, training, seed, mask, rows, cfg, link_in=None):
         X = _f32c(X)
         rows = rows if rows.dtype == torch.int64 else rows.long()
-        AHc = spmm_graph(g, X, cfg=cfg).index_select(0, rows)          # [n, K]
         ep = _Epilogue(b is not None, p, training, seed, mask)
-        outc = _dense_rows(AHc, W, b, rows, ep, cfg)
+        outc, AHc, ctx.through = _dense_rows_of(spmm_graph(g, X, cfg=cfg), W, b, rows, ep, cfg)   # AHc: [R, K] read through `rows`, or [n, K]
         keep_x = link_in is not None and cfg.fuse_dx_epilogue and X.shape[1] % 4 == 0
         ctx.save_for_backward(W, AHc, outc, rows, ep.mask, X if keep_x else None)
         ctx.g, ctx.ep, ctx.has_bias, ctx.cfg, ctx.link_in = g, ep, b is not None, cfg, link_in
@@ -2208,7 +2248,7 @@ class FusedGCNLayerRows(torch.autograd.Function):
         sink, (pW, pb) = _GradSink(cfg.grad_sink), ctx.ptrs
         sb = sink.slice(pb) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         dZc, db = epilogue_bwd_rows_raw(dOutc, outc, rows, ep.bwd, p=ep.p, seed=ep.seed, mask=mask, want_db=ctx.has_bias, db_out=sb)
-        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW))) if ctx.needs_input_grad[1] else None
+        dW = sink.result(mm_at_b(dZc, AHc, cfg, out=sink.slice(pW), b_rows=rows if ctx.through else None)) if ctx.needs_input_grad[1] else None
         # rows [n, n + ZERO_ROWS) of dAH stand for the rows outside the selection: every kernel that takes zero_from treats them as zeros
         # WITHOUT loading them (staged as zeros / read from a row of zeros in LDS / multiplied from registers), so they are not filled
         dX = _rows_adjoint(ctx.g, dZc, W, rows, ctx.link_in, Xprev, cfg, zero_tail=False) if ctx.needs_input_grad[0] else None

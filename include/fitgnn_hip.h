@@ -354,6 +354,19 @@ int fitgnn_gemm_exact_plan(int64_t I, int32_t J, int64_t K, int32_t a_kmajor, in
 int fitgnn_gemm_exact_epi_f32(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t I, int32_t J, int64_t K, float *c,
                               int64_t ldc, const int64_t *rows, const float *bias, uint32_t epilogue, float p_drop, uint64_t seed,
                               const uint8_t *mask, void *workspace, void *stream);
+/* Both products with operand rows read through a list, where they lie in a taller matrix (no gathered copy):
+ *     a_rows (int64 [I], k-minor a only): row i of the product's a is a[a_rows[i] * lda + ...]
+ *     b_rows (int64 [K], k-major b only): row k of the product's b is b[b_rows[k] * ldb + ...]
+ * Either may be NULL (both NULL: the calls above).  Bit for bit the product of the gathered operand: same plan, same workspace, same
+ * order of every sum.  a_rows with a k-major a, b_rows with a k-minor b: FITGNN_E_BADARG; a list that is not 8-byte aligned:
+ * FITGNN_E_ALIGN.  The entries are not range-checked.  fitgnn_gemm_exact_epi_rows_f32 takes a_rows beside `rows` (the dropout
+ * pattern's original rows): in a layer on kept rows they are the same array. */
+int fitgnn_gemm_exact_rows_f32(const float *a, int64_t lda, int32_t a_kmajor, const int64_t *a_rows, const float *b, int64_t ldb,
+                               int32_t b_kmajor, const int64_t *b_rows, int64_t I, int32_t J, int64_t K, float *c, int64_t ldc,
+                               void *workspace, void *stream);
+int fitgnn_gemm_exact_epi_rows_f32(const float *a, int64_t lda, const int64_t *a_rows, const float *b, int64_t ldb, int64_t I, int32_t J,
+                                   int64_t K, float *c, int64_t ldc, const int64_t *rows, const float *bias, uint32_t epilogue,
+                                   float p_drop, uint64_t seed, const uint8_t *mask, void *workspace, void *stream);
 
 /* Pre-split b operand for the tall-GEMM kernels: b [N x K] given by element strides (b[n * stride_n + k * stride_k]; so
  * b = W^T needs no transposed copy) is converted ONCE per call into bf16 hi/lo fragments laid out as the kernel's LDS image,
