@@ -207,6 +207,12 @@ SIGNATURES = {
                                                  ptr]),
     "fitgnn_cross_atb_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
     "fitgnn_cross_atb_f64": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, c_i64, c_i32, c_i32, ptr, c_i64, ptr, c_size, ptr]),
+    "fitgnn_louvain_sweep_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "fitgnn_louvain_bucket_rows": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, ptr, c_size, ptr]),
+    "fitgnn_louvain_sweep": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, c_i64, ptr, ptr, ptr, c_i32, ptr, c_i32, ptr, ptr, c_size, ptr]),
+    "fitgnn_louvain_stats": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, c_i64, ptr, ptr, ptr, ptr, ptr, ptr]),
+    "fitgnn_louvain_components_workspace_bytes": (c_size, [c_i64]),
+    "fitgnn_louvain_components": (ctypes.c_int, [ptr, ptr, c_i64, ptr, ptr, ptr, ptr, c_size, ptr]),
 }
 
 _lib = None

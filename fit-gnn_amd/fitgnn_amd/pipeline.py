@@ -739,12 +739,19 @@ def node_regression_baseline(args, path, data, device="cuda", log=print):
 # ---------------------------------------------------------------------------------------------
 # --use_community_detection (main.py:247-267): keep the largest communities up to k nodes
 # ---------------------------------------------------------------------------------------------
-def detect_communities(edge_index, num_nodes, seed=0, iters=20):
+def detect_communities(edge_index, num_nodes, seed=0, iters=20, method="label_propagation"):
     """A node partition for --use_community_detection.  The reference calls leidenalg.find_partition(...,
     ModularityVertexPartition) on an igraph Graph (main.py:257-258); neither package exists here, and only the partition
-    is consumed downstream, so this is a substitute: seeded label propagation (every node repeatedly adopts the most
-    frequent label among its neighbours, ties to the smallest label, half of the nodes per sweep), vectorised with
-    sort-based modes.  Returns int64 labels in 0..n_comm-1."""
+    is consumed downstream.  method="label_propagation" (the default) is a substitute on the CPU: seeded label propagation
+    (every node repeatedly adopts the most frequent label among its neighbours, ties to the smallest label, half of the
+    nodes per sweep), vectorised with sort-based modes.  method="modularity" optimises what the reference optimises, on the
+    GPU: community.modularity_communities (deterministic; seed and iters do not apply).  Returns int64 labels in
+    0..n_comm-1."""
+    if method == "modularity":
+        from . import community
+        return community.modularity_communities(edge_index, num_nodes)
+    if method != "label_propagation":
+        raise ValueError(f"detect_communities: unknown method {method!r} (label_propagation or modularity)")
     ei = np.asarray(edge_index)
     src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
     N = int(num_nodes)

@@ -13,7 +13,7 @@ Datasets: the reference downloads through torch_geometric / ogb, which are not a
   synthetic-qm9              QM9-shaped graph regression stand-in (--n_graphs molecules of ~18 nodes, 19 targets)
   cora | citeseer | pubmed   Planetoid raw files `ind.<name>.*` under --data_root/<name>/raw (PyG's own layout)
   synthetic-{cora,citeseer,pubmed,physics}   seeded stand-ins of the same shape (dataset_info.csv)
-Extra flags (not in the reference): --data_root, --device, --community_nodes, --n_graphs, --dropout.
+Extra flags (not in the reference): --data_root, --device, --community_nodes, --community_method, --n_graphs, --dropout.
 
 Data parallel (BASELINE.json config 4, "subgraph-batch DP on 8 x MI355X"; new functionality): launch one
 process per GPU, e.g. `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 main.py
@@ -78,6 +78,8 @@ def build_parser():
     p.add_argument('--data_root', type=str, default='./dataset')
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--community_nodes', type=int, default=165000)  # main.py:264 hard-codes 165000
+    # modularity: community.modularity_communities on the GPU (what the reference's leidenalg call optimises); the default is the CPU substitute
+    p.add_argument('--community_method', type=str, default='label_propagation', choices=['label_propagation', 'modularity'])
     p.add_argument('--n_graphs', type=int, default=2000)  # size of the synthetic-qm9 stand-in (QM9 itself: 130 831)
     p.add_argument('--dropout', type=float, default=0.5)  # the reference calls F.dropout with its default p = 0.5 (network.py:33)
     return p
@@ -221,7 +223,8 @@ def main(argv=None):
     path = f"save/{args.task}/" + (f"baseline/{args.output_dir}/" if args.baseline else f"{args.output_dir}/")
     os.makedirs(path, exist_ok=True)
     if args.use_community_detection and args.task == 'node_cls':   # main.py:247-267
-        labels = pipeline.detect_communities(data.edge_index, data.num_nodes, seed=0 if args.seed is None else args.seed)
+        labels = pipeline.detect_communities(data.edge_index, data.num_nodes, seed=0 if args.seed is None else args.seed,
+                                             method=args.community_method)
         data = pipeline.merge_communities(data, labels, args.community_nodes)
         print(f"community detection: {int(labels.max()) + 1} communities, kept {data.num_nodes} nodes (<= {args.community_nodes})")
     if args.task == 'node_reg':

@@ -1105,6 +1105,39 @@ size_t fitgnn_cross_atb_workspace_bytes(int32_t n, int32_t k1, int32_t k2);
 int fitgnn_cross_atb_f64(const double *A, int64_t lda, int32_t k1, const double *B, int64_t ldb, int32_t k2, int32_t n, double *out,
                          int64_t ldo, void *work, size_t work_bytes, void *stream);
 
+/* ---- modularity community detection (main.py:257-258 leidenalg.find_partition(.., ModularityVertexPartition); the rule built
+ * instead is stated in DESIGN.md §4 "Community detection").  A level graph is a CSR with ascending columns and int32 weights >= 1
+ * (w == NULL: all ones); from level 1 on a diagonal entry holds the weight inside the community.  k int32[N]: the row sums,
+ * diagonal included; M2 = sum of k.  N >= 2^31 or M2 >= 2^31 is refused with FITGNN_E_BADARG before any GPU work: below that limit
+ * every score fits int64.  All arithmetic is integer and independent of the order of the atomics: two runs give identical bytes.
+ *
+ * fitgnn_louvain_bucket_rows, once per level: sorts the rows into the sweep's three launch branches by row length (<= 128: one
+ * wavefront per node, table in LDS; <= 4096: one workgroup per node, 64 KiB table in LDS; longer: one workgroup per node, table in
+ * the workspace) and leaves the node lists in `work`, which the sweeps of the level then read.  counts (HOST int32[4]): the three
+ * list lengths and the longest row.  Synchronises `stream` once.  max_row: an upper bound of the row length, which sizes the third
+ * branch's tables (fitgnn_louvain_sweep_workspace_bytes is 0 for N or max_row out of range, max_row > N or > 2^30 included);
+ * FITGNN_E_BADARG if a row is longer.
+ * fitgnn_louvain_sweep: sweep t from the snapshot comm / tot / size (int32[N]: community of a node, sum of k and number of nodes of a
+ * community id): comm_out[i] = the community node i moves to if (i + t) is even, else comm[i].  counts / max_row / work as left by
+ * fitgnn_louvain_bucket_rows for the same rowptr. */
+size_t fitgnn_louvain_sweep_workspace_bytes(int64_t N, int32_t max_row);
+int fitgnn_louvain_bucket_rows(const int32_t *rowptr, int64_t N, int32_t max_row, int32_t *counts, void *work, size_t work_bytes,
+                               void *stream);
+int fitgnn_louvain_sweep(const int32_t *rowptr, const int32_t *col, const int32_t *w, const int32_t *k, int64_t N, int64_t M2,
+                         const int32_t *comm, const int32_t *tot, const int32_t *size, int32_t t, const int32_t *counts, int32_t max_row,
+                         int32_t *comm_out, void *work, size_t work_bytes, void *stream);
+/* What the host needs to accept or discard a sweep: tot / size int32[N] of the labelling comm, and out int64[3] = {nodes whose
+ * community differs from snapshot, sum over entries with comm[i] == comm[j] of w_ij (diagonal included), sum of tot[c]^2}.
+ * Qnum = M2 * out[1] - out[2]. */
+int fitgnn_louvain_stats(const int32_t *rowptr, const int32_t *col, const int32_t *w, const int32_t *k, int64_t N, int64_t M2,
+                         const int32_t *comm, const int32_t *snapshot, int32_t *tot, int32_t *size, int64_t *out, void *stream);
+/* The connectivity finish: label[i] (int32[N]) = the smallest node of i's connected component in the subgraph induced by i's
+ * community (label = min over same-community neighbours, then pointer jumping, until a pass changes nothing).  Synchronises
+ * `stream` once per chunk of 1, 2, 4 .. 64 passes.  passes (HOST int32, may be NULL): passes that changed a label. */
+size_t fitgnn_louvain_components_workspace_bytes(int64_t N);
+int fitgnn_louvain_components(const int32_t *rowptr, const int32_t *col, int64_t N, const int32_t *comm, int32_t *label, int32_t *passes,
+                              void *work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
