@@ -216,15 +216,29 @@ SIGNATURES = {
 }
 
 _lib = None
+_plans = {}      # name -> per-parameter plan of call(), built once by lib()
+_Tensor = None   # torch.Tensor, set by lib()
+_NO_CPU = "fitgnn ops run on the MI355X only: got a CPU tensor (no CPU fallback exists)"
 
 
 class FitgnnError(RuntimeError):
     pass
 
 
+def _plan(argtypes):
+    """(number of parameters, positions of the pointers, (position, lo, hi) of every integer parameter: the range of its type) of one
+    signature; what ctypes converts alone (floats) is in neither list."""
+    ints = []
+    for i, t in enumerate(argtypes):
+        if t in (c_i32, c_u32, c_i64, c_u64, c_size):
+            bits, signed = 8 * ctypes.sizeof(t), t(-1).value < 0
+            ints.append((i, -(1 << (bits - 1)), (1 << (bits - 1)) - 1) if signed else (i, 0, (1 << bits) - 1))
+    return len(argtypes), tuple(i for i, t in enumerate(argtypes) if t is ptr), tuple(ints)
+
+
 def lib():
     """The loaded library; raises (never falls back) when it is not built."""
-    global _lib
+    global _lib, _Tensor
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise FitgnnError(f"{LIB_PATH} not found: build the HIP extension first "
@@ -239,8 +253,10 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
+            _plans[name] = _plan(args)
         if L.fitgnn_abi_version() != 1:
             raise FitgnnError("libfitgnn_hip.so ABI version mismatch")
+        _Tensor = torch.Tensor
         _lib = L
     return _lib
 
@@ -249,6 +265,35 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().fitgnn_error_string(int(rc)).decode()
         raise FitgnnError(f"{what}: {msg} (code {rc})")
+
+
+def call(name, *args):
+    """Call the status-returning entry point `name` (a key of SIGNATURES) and raise FitgnnError unless it returns 0.
+
+    Each argument is converted by its parameter's declared type before anything is launched.  A pointer takes a CUDA tensor (its
+    data_ptr(); a CPU tensor is an error: there is no CPU fallback), None (NULL), or anything ctypes itself takes for a void*
+    (an int address, a c_void_p, a ctypes array, a byref).  An integer must fit the parameter's type: ctypes would truncate it
+    silently.  The stream is an argument like any other."""
+    L = _lib or lib()   # the library object of this moment: a tool may have put a wrapper in its place
+    try:
+        n, ptrs, ints = _plans[name]
+    except KeyError:
+        raise FitgnnError(f"{name}: not an entry point that lib() has bound (SIGNATURES lists them)") from None
+    if len(args) != n:
+        raise FitgnnError(f"{name}: takes {n} arguments, got {len(args)}")
+    for i, lo, hi in ints:
+        if not lo <= args[i] <= hi:
+            raise FitgnnError(f"{name}: argument {i} = {args[i]} does not fit {SIGNATURES[name][1][i].__name__}")
+    conv = list(args)
+    for i in ptrs:
+        a = conv[i]
+        if a is not None and isinstance(a, _Tensor):   # (None first: an identity test costs less than isinstance)
+            if not a.is_cuda:
+                raise FitgnnError(_NO_CPU)
+            conv[i] = a.data_ptr()
+    rc = getattr(L, name)(*conv)
+    if rc:
+        check(rc, name)
 
 
 def dptr(t):
@@ -265,4 +310,4 @@ def stream_ptr(device=None):
 def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise FitgnnError("fitgnn ops run on the MI355X only: got a CPU tensor (no CPU fallback exists)")
+            raise FitgnnError(_NO_CPU)

@@ -152,28 +152,25 @@ def lanczos_smallest(L, K, device="cuda", tol=1e-5, m=None, max_restarts=300, se
     ha, hb, hc = (torch.empty(m + 2, dtype=torch.float64, device=dev) for _ in range(3))
 
     def project(ncol, h_in, h_out):
-        _lib.check(Lh.fitgnn_lanczos_project_f64(_lib.dptr(V), N, ncol, _lib.dptr(w), N, _lib.dptr(h_in), _lib.dptr(part), st), "lanczos_project")
-        _lib.check(Lh.fitgnn_lanczos_reduce_f64(_lib.dptr(part), parts, ncol + 1, _lib.dptr(h_out), st), "lanczos_reduce")
+        _lib.call("fitgnn_lanczos_project_f64", V, N, ncol, w, N, h_in, part, st)
+        _lib.call("fitgnn_lanczos_reduce_f64", part, parts, ncol + 1, h_out, st)
 
     def rotate(src, Smat, dst):
         """dst[c] = sum_j Smat[j, c] src[j] (Smat: host array [m, nk]); the kernel rotates at most 16 columns per launch: groups."""
         for c0 in range(0, int(Smat.shape[1]), 16):
             blk = Smat[:, c0:c0 + 16]
             Sd = torch.from_numpy(np.ascontiguousarray(blk, dtype=np.float64)).to(dev)
-            _lib.check(Lh.fitgnn_lanczos_rotate_f64(_lib.dptr(src), N, int(blk.shape[0]), _lib.dptr(Sd), int(blk.shape[1]), _lib.dptr(dst[c0:]), N, N,
-                                                    st), "lanczos_rotate")
+            _lib.call("fitgnn_lanczos_rotate_f64", src, N, int(blk.shape[0]), Sd, int(blk.shape[1]), dst[c0:], N, N, st)
 
     j0 = 0
     for _ in range(max_restarts):
         for j in range(j0, m):
-            _lib.check(Lh.fitgnn_lanczos_spmv_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(V[j]), _lib.dptr(w), N, -1.0, offset,
-                                                  st), "fitgnn_lanczos_spmv_f64")
+            _lib.call("fitgnn_lanczos_spmv_f64", rowptr, col, val, V[j], w, N, -1.0, offset, st)
             # h = V^T w;  w -= V h, h2 = V^T w;  w -= V h2, |w|^2;  v_{j+1} = w / |w|, H[:, j] = h + h2
             project(j + 1, None, ha)
             project(j + 1, ha, hb)
             project(j + 1, hb, hc)
-            _lib.check(Lh.fitgnn_lanczos_finish_f64(_lib.dptr(V), N, j, _lib.dptr(w), N, _lib.dptr(ha), _lib.dptr(hb), _lib.dptr(hc), _lib.dptr(H), m,
-                                                    st), "fitgnn_lanczos_finish_f64")
+            _lib.call("fitgnn_lanczos_finish_f64", V, N, j, w, N, ha, hb, hc, H, m, st)
         # the projected m x m eigenproblem on the host (60 x 60: LAPACK takes less than the launch of a device solver)
         Hh = H.cpu().numpy()
         Hm = (Hh[:m, :m] + Hh[:m, :m].T) / 2
@@ -243,13 +240,10 @@ def contract_level(G, A, r_cur, device="cuda", keep_debug=False):
     nnz = int(W.nnz)
     set_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
     set_mem = torch.empty(nnz + N, dtype=torch.int32, device=dev)
-    _lib.check(L.fitgnn_closed_neighbourhoods(_lib.dptr(rowptr), _lib.dptr(col), N, _lib.dptr(set_off), _lib.dptr(set_mem), st),
-               "closed_neighbourhoods")
+    _lib.call("fitgnn_closed_neighbourhoods", rowptr, col, N, set_off, set_mem, st)
     set_len = (set_off[1:] - set_off[:-1]).contiguous()
     cost0 = torch.empty(N, dtype=torch.float64, device=dev)
-    _lib.check(L.fitgnn_variation_costs_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad), K, K,
-                                            _lib.dptr(set_off), _lib.dptr(set_len), _lib.dptr(set_mem), N, _lib.dptr(cost0), st),
-               "variation_costs")
+    _lib.call("fitgnn_variation_costs_f64", rowptr, col, w, dw, Ad, K, K, set_off, set_len, set_mem, N, cost0, st)
     n_reduce = int(np.floor(r_cur * N))  # coarsening_utils.py:612
     total = nnz + N
     wb = int(L.fitgnn_greedy_select_workspace_bytes(N, total))
@@ -257,16 +251,13 @@ def contract_level(G, A, r_cur, device="cuda", keep_debug=False):
     sel_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
     sel_mem = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
-    _lib.check(L.fitgnn_greedy_select(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad), K, K, N,
-                                      _lib.dptr(set_off), _lib.dptr(set_mem), _lib.dptr(cost0), n_reduce, _lib.dptr(sel_off),
-                                      _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(work), wb, st), "greedy_select")
+    _lib.call("fitgnn_greedy_select", rowptr, col, w, dw, Ad, K, K, N, set_off, set_mem, cost0, n_reduce, sel_off, sel_mem, sel_count, work, wb, st)
     assign = torch.empty(N, dtype=torch.int32, device=dev)
     cval = torch.empty(N, dtype=torch.float64, device=dev)
     n_out = torch.zeros(1, dtype=torch.int32, device=dev)
     wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
     work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
-    _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
-                                         _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
+    _lib.call("fitgnn_build_assignment", N, sel_off, sel_mem, sel_count, assign, cval, n_out, work2, wb2, st)
     res = LevelResult()
     res.N, res.n, res.assign, res.cval, res.device = N, int(n_out.item()), assign, cval, dev
     res.rowptr, res.col, res.w = rowptr, col, w
@@ -292,9 +283,7 @@ def lift_adjacency(res):
     cc = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
     wc = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
     nz = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(L.fitgnn_lift_adjacency(res.N, _lib.dptr(res.rowptr), _lib.dptr(res.col), _lib.dptr(res.w), _lib.dptr(res.assign),
-                                       _lib.dptr(res.cval), res.n, _lib.dptr(rp), _lib.dptr(cc), _lib.dptr(wc), _lib.dptr(nz),
-                                       _lib.dptr(work), wb, st), "lift_adjacency")
+    _lib.call("fitgnn_lift_adjacency", res.N, res.rowptr, res.col, res.w, res.assign, res.cval, res.n, rp, cc, wc, nz, work, wb, st)
     m = int(nz.item())
     return sp.csr_matrix((wc[:m].cpu().numpy(), cc[:m].cpu().numpy(), rp.cpu().numpy()), shape=(res.n, res.n))
 
@@ -333,7 +322,6 @@ class EdgeList:
     __slots__ = ("N", "M", "rowptr", "col", "w", "dw", "edge_off", "src", "dst", "ew", "csr_eid", "device")
 
     def __init__(self, G, device="cuda"):
-        L = _lib.lib()
         dev = torch.device(device)
         if dev.type != "cuda":
             raise _lib.FitgnnError("the matching methods run on the MI355X (no CPU fallback)")
@@ -348,9 +336,8 @@ class EdgeList:
         self.src, self.dst = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
         self.ew = torch.empty(m, dtype=torch.float64, device=dev)
         self.csr_eid = torch.empty(max(int(W.nnz), 1), dtype=torch.int32, device=dev)
-        _lib.check(L.fitgnn_edge_list(_lib.dptr(self.rowptr), _lib.dptr(self.col), _lib.dptr(self.w), self.N, _lib.dptr(self.edge_off),
-                                      _lib.dptr(self.src), _lib.dptr(self.dst), _lib.dptr(self.ew), self.M, _lib.dptr(self.csr_eid),
-                                      _lib.stream_ptr(dev)), "edge_list")
+        _lib.call("fitgnn_edge_list", self.rowptr, self.col, self.w, self.N, self.edge_off, self.src, self.dst, self.ew, self.M, self.csr_eid,
+                  _lib.stream_ptr(dev))
 
 
 def test_vectors(el, method, X0):
@@ -368,12 +355,10 @@ def test_vectors(el, method, X0):
     if method == "algebraic_JC":
         wb = int(L.fitgnn_jacobi_vectors_workspace_bytes(N, K))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        _lib.check(L.fitgnn_jacobi_vectors_f64(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), _lib.dptr(el.dw), N, _lib.dptr(X0d),
-                                               K, 20, _lib.dptr(X), _lib.dptr(work), wb, st), "jacobi_vectors")
+        _lib.call("fitgnn_jacobi_vectors_f64", el.rowptr, el.col, el.w, el.dw, N, X0d, K, 20, X, work, wb, st)
     elif method == "affinity_GS":
         comp_off = torch.tensor([0, N], dtype=torch.int32, device=dev)
-        _lib.check(L.fitgnn_gauss_seidel_vectors_f64(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), _lib.dptr(el.dw), N, 1,
-                                                     _lib.dptr(comp_off), _lib.dptr(X0d), K, _lib.dptr(X), st), "gauss_seidel_vectors")
+        _lib.call("fitgnn_gauss_seidel_vectors_f64", el.rowptr, el.col, el.w, el.dw, N, 1, comp_off, X0d, K, X, st)
     else:
         raise ValueError(method)
     return X
@@ -388,18 +373,15 @@ def proximity(el, method, X=None):
     if method == "heavy_edge":
         wb = int(L.fitgnn_heavy_edge_proximity_workspace_bytes(el.N))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        _lib.check(L.fitgnn_heavy_edge_proximity(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.w), el.N, _lib.dptr(el.src),
-                                                 _lib.dptr(el.dst), _lib.dptr(el.ew), el.M, _lib.dptr(prox), _lib.dptr(work), wb, st),
-                   "heavy_edge_proximity")
+        _lib.call("fitgnn_heavy_edge_proximity", el.rowptr, el.col, el.w, el.N, el.src, el.dst, el.ew, el.M, prox, work, wb, st)
     elif method == "algebraic_JC":
         K = int(X.shape[1])
-        _lib.check(L.fitgnn_jc_proximity(_lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(X), K, K, _lib.dptr(prox), st), "jc_proximity")
+        _lib.call("fitgnn_jc_proximity", el.src, el.dst, el.M, X, K, K, prox, st)
     elif method == "affinity_GS":
         K = int(X.shape[1])
         wb = int(L.fitgnn_affinity_proximity_workspace_bytes(el.N, el.M))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        _lib.check(L.fitgnn_affinity_proximity(el.N, _lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(X), K, K, _lib.dptr(prox),
-                                               _lib.dptr(work), wb, st), "affinity_proximity")
+        _lib.call("fitgnn_affinity_proximity", el.N, el.src, el.dst, el.M, X, K, K, prox, work, wb, st)
     else:
         raise ValueError(method)
     return prox[: el.M]
@@ -407,7 +389,6 @@ def proximity(el, method, X=None):
 
 def edge_costs(el, A):
     """variation_edges' per-edge cost (:495-514) from the level's spectral matrix A (host [N x K], or a device f64 tensor)."""
-    L = _lib.lib()
     if not torch.is_tensor(A) and np.iscomplexobj(A):
         # np.linalg.eig at later levels can return a complex basis (:98-104); the reference's Frobenius norm then sums squared
         # moduli: the cost of the real part plus the cost of the imaginary part
@@ -417,8 +398,7 @@ def edge_costs(el, A):
     if not (1 <= K <= _lib.MAX_K):
         raise _lib.FitgnnError(f"K={K} outside [1,{_lib.MAX_K}]")
     cost = torch.empty(max(el.M, 1), dtype=torch.float64, device=el.device)
-    _lib.check(L.fitgnn_edge_variation_costs_f64(_lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(el.dw), _lib.dptr(Ad), K, K,
-                                                 _lib.dptr(cost), _lib.stream_ptr(el.device)), "edge_variation_costs")
+    _lib.call("fitgnn_edge_variation_costs_f64", el.src, el.dst, el.M, el.dw, Ad, K, K, cost, _lib.stream_ptr(el.device))
     return cost[: el.M]
 
 
@@ -445,17 +425,14 @@ def greedy_matching(el, weight, k_keep, comp_off=None, min_gain=0):
     sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
     taken = torch.zeros(max(n_comp, 1), dtype=torch.int32, device=dev)
     rounds = _lib.c_i32(0)
-    _lib.check(L.fitgnn_greedy_matching(_lib.dptr(el.rowptr), _lib.dptr(el.col), _lib.dptr(el.csr_eid), N, _lib.dptr(el.edge_off),
-                                        _lib.dptr(el.src), _lib.dptr(el.dst), el.M, _lib.dptr(wd), n_comp, _lib.dptr(co_d), _lib.dptr(k_d),
-                                        int(min_gain), _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(taken),
-                                        _lib.ctypes.byref(rounds), _lib.dptr(work), wb, st), "greedy_matching")
+    _lib.call("fitgnn_greedy_matching", el.rowptr, el.col, el.csr_eid, N, el.edge_off, el.src, el.dst, el.M, wd, n_comp, co_d, k_d, int(min_gain),
+              sel_off, sel_mem, sel_count, taken, _lib.ctypes.byref(rounds), work, wb, st)
     assign = torch.empty(N, dtype=torch.int32, device=dev)
     cval = torch.empty(N, dtype=torch.float64, device=dev)
     n_out = torch.zeros(1, dtype=torch.int32, device=dev)
     wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
     work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
-    _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
-                                         _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
+    _lib.call("fitgnn_build_assignment", N, sel_off, sel_mem, sel_count, assign, cval, n_out, work2, wb2, st)
     res = MatchLevelResult()
     res.N, res.n, res.assign, res.cval, res.device = N, int(n_out.item()), assign, cval, dev
     res.rowptr, res.col, res.w = el.rowptr, el.col, el.w
@@ -492,8 +469,7 @@ def pool_rows(assign, cval, n, X, want_f64=False):
     Xc64 = torch.empty((n, F), dtype=torch.float64, device=dev) if want_f64 else None
     wb = int(L.fitgnn_pool_rows_workspace_bytes(N, n))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
-    _lib.check(L.fitgnn_pool_rows_f32(_lib.dptr(assign), _lib.dptr(cval), N, n, _lib.dptr(X), F, F, _lib.dptr(Xc), F,
-                                      _lib.dptr(Xc64), _lib.dptr(work), wb, _lib.stream_ptr(dev)), "pool_rows")
+    _lib.call("fitgnn_pool_rows_f32", assign, cval, N, n, X, F, F, Xc, F, Xc64, work, wb, _lib.stream_ptr(dev))
     return (Xc, Xc64) if want_f64 else Xc
 
 
@@ -562,7 +538,6 @@ def _coarsen(G, K, r, max_levels, method, algorithm, Uk, lk, max_level_r, device
     N = G.N
     n, n_target = N, np.ceil((1 - r) * N)
     dev = torch.device(device)
-    L = _lib.lib()
     assign_tot = torch.arange(N, dtype=torch.int32, device=dev)
     cval_tot = torch.ones(N, dtype=torch.float64, device=dev)
     Gc = G
@@ -590,8 +565,7 @@ def _coarsen(G, K, r, max_levels, method, algorithm, Uk, lk, max_level_r, device
         if iC.shape[1] - iC.shape[0] <= 2:  # :131-135 avoid too many levels for so few nodes
             mapping_dict_list.append({i: i for i in range(G.N)})
             break
-        _lib.check(L.fitgnn_compose_levels(N, _lib.dptr(res.assign), _lib.dptr(res.cval), _lib.dptr(assign_tot),
-                                           _lib.dptr(cval_tot), _lib.stream_ptr(dev)), "compose_levels")
+        _lib.call("fitgnn_compose_levels", N, res.assign, res.cval, assign_tot, cval_tot, _lib.stream_ptr(dev))
         Wc = lift_adjacency(res)
         coords = None
         if hasattr(G, "coords"):
@@ -700,7 +674,6 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         raise NotImplementedError(f"coarsen_batch: '{method}' draws random test vectors per component and level; use coarsen() "
                                   "per component (the reference's draw order)")
     matching = method in MATCHING_METHODS
-    L = _lib.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.FitgnnError("coarsen_batch needs the MI355X (no CPU fallback)")
@@ -781,8 +754,7 @@ def coarsen_batch(W, comp_off, r=0.5, K=10, max_levels=10, A0=None, max_level_r=
         active = applied.copy()
         if not applied.any():
             break
-        _lib.check(L.fitgnn_compose_levels(N0, _lib.dptr(assign), _lib.dptr(cval), _lib.dptr(assign_tot), _lib.dptr(cval_tot), st),
-                   "compose_levels")
+        _lib.call("fitgnn_compose_levels", N0, assign, cval, assign_tot, cval_tot, st)
         res = LevelResult()
         res.N, res.n, res.assign, res.cval, res.device = N, n_out_h, assign, cval, dev
         res.rowptr, res.col, res.w = rowptr, col, w
@@ -877,7 +849,6 @@ def coarsen_in_order(W, comp_off, r=0.5, K=10, max_levels=10, method="algebraic_
     order, with the global state at exactly that position.  Returns a BatchCoarsening (levels: applied levels)."""
     if method not in IN_ORDER_METHODS:
         raise NotImplementedError(f"coarsen_in_order: method '{method}' is not supported; supported: {', '.join(IN_ORDER_METHODS)}")
-    L = _lib.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.FitgnnError("coarsen_in_order needs the MI355X (no CPU fallback)")
@@ -925,11 +896,8 @@ def coarsen_in_order(W, comp_off, r=0.5, K=10, max_levels=10, method="algebraic_
 
     def launch(c0, c1, draws=None, sqrt_n=None, progress=None):
         nd = 0 if draws is None else int(draws.numel())
-        _lib.check(L.fitgnn_match_small(mcode, _lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(co_d), int(c0), int(c1), r,
-                                        int(K), int(max_levels), float(max_level_r), _lib.dptr(draws), nd, _lib.dptr(sqrt_n), cap_n,
-                                        cap_z, _lib.dptr(assign), _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(levels),
-                                        _lib.dptr(status), _lib.dptr(wc_rowptr), _lib.dptr(wc_col), _lib.dptr(wc_w),
-                                        _lib.dptr(progress), st), "match_small")
+        _lib.call("fitgnn_match_small", mcode, rowptr, col, w, co_d, int(c0), int(c1), r, int(K), int(max_levels), float(max_level_r), draws, nd,
+                  sqrt_n, cap_n, cap_z, assign, cval, n_out, levels, status, wc_rowptr, wc_col, wc_w, progress, st)
 
     if method == "heavy_edge":
         if fits.any():
@@ -1028,13 +996,10 @@ def _select_level_batch(G, A, node_K_comp, off, n_comp, n_reduce, dev, st):
     nnz = int(Wl.nnz)
     set_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
     set_mem = torch.empty(nnz + N, dtype=torch.int32, device=dev)
-    _lib.check(L.fitgnn_closed_neighbourhoods(_lib.dptr(rowptr), _lib.dptr(col), N, _lib.dptr(set_off), _lib.dptr(set_mem), st),
-               "closed_neighbourhoods")
+    _lib.call("fitgnn_closed_neighbourhoods", rowptr, col, N, set_off, set_mem, st)
     set_len = (set_off[1:] - set_off[:-1]).contiguous()
     cost0 = torch.empty(N, dtype=torch.float64, device=dev)
-    _lib.check(L.fitgnn_variation_costs_batch_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad),
-                                                  lda, lda, _lib.dptr(nK), _lib.dptr(set_off), _lib.dptr(set_len),
-                                                  _lib.dptr(set_mem), N, _lib.dptr(cost0), st), "variation_costs_batch")
+    _lib.call("fitgnn_variation_costs_batch_f64", rowptr, col, w, dw, Ad, lda, lda, nK, set_off, set_len, set_mem, N, cost0, st)
     wb = int(L.fitgnn_greedy_select_batch_workspace_bytes(N, nnz + N, n_comp))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     sel_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
@@ -1042,18 +1007,14 @@ def _select_level_batch(G, A, node_K_comp, off, n_comp, n_reduce, dev, st):
     sel_count = torch.zeros(2, dtype=torch.int32, device=dev)
     gain_d = torch.zeros(n_comp, dtype=torch.int64, device=dev)
     off_d, n_reduce_d = _dev(off, torch.int32, dev), _dev(n_reduce, torch.int64, dev)  # named: they must outlive the call
-    _lib.check(L.fitgnn_greedy_select_batch(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(Ad), lda,
-                                            lda, N, _lib.dptr(set_off), _lib.dptr(set_mem), _lib.dptr(cost0), n_comp,
-                                            _lib.dptr(off_d), _lib.dptr(n_reduce_d),
-                                            2, _lib.dptr(nK), _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count),
-                                            _lib.dptr(gain_d), _lib.dptr(work), wb, st), "greedy_select_batch")
+    _lib.call("fitgnn_greedy_select_batch", rowptr, col, w, dw, Ad, lda, lda, N, set_off, set_mem, cost0, n_comp, off_d, n_reduce_d, 2, nK, sel_off,
+              sel_mem, sel_count, gain_d, work, wb, st)
     assign = torch.empty(N, dtype=torch.int32, device=dev)
     cval = torch.empty(N, dtype=torch.float64, device=dev)
     n_out = torch.zeros(1, dtype=torch.int32, device=dev)
     wb2 = int(L.fitgnn_build_assignment_workspace_bytes(N))
     work2 = torch.empty(wb2, dtype=torch.uint8, device=dev)
-    _lib.check(L.fitgnn_build_assignment(N, _lib.dptr(sel_off), _lib.dptr(sel_mem), _lib.dptr(sel_count), _lib.dptr(assign),
-                                         _lib.dptr(cval), _lib.dptr(n_out), _lib.dptr(work2), wb2, st), "build_assignment")
+    _lib.call("fitgnn_build_assignment", N, sel_off, sel_mem, sel_count, assign, cval, n_out, work2, wb2, st)
     return assign, cval, gain_d.cpu().numpy(), int(n_out.item()), rowptr, col, w
 
 
@@ -1086,9 +1047,7 @@ def coarse_laplacian(W, dw, assign, cval, n):
     cc = torch.empty(max(nnz + n, 1), dtype=torch.int32, device=dev)
     vv = torch.empty(max(nnz + n, 1), dtype=torch.float64, device=dev)
     nz = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(L.fitgnn_coarse_laplacian(N, _lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), nnz, _lib.dptr(dwd), _lib.dptr(assign),
-                                         _lib.dptr(cval), n, _lib.dptr(rp), _lib.dptr(cc), _lib.dptr(vv), _lib.dptr(nz), _lib.dptr(work), wb,
-                                         _lib.stream_ptr(dev)), "coarse_laplacian")
+    _lib.call("fitgnn_coarse_laplacian", N, rowptr, col, w, nnz, dwd, assign, cval, n, rp, cc, vv, nz, work, wb, _lib.stream_ptr(dev))
     m = int(nz.item())
     return sp.csr_matrix((vv[:m].cpu().numpy(), cc[:m].cpu().numpy(), rp.cpu().numpy()), shape=(n, n))
 
@@ -1104,8 +1063,8 @@ def project_lift(assign, cval, n, U, want_Y=True):
     wb = int(L.fitgnn_project_lift_workspace_bytes(N, n))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     for c0, c1 in _col_tiles(k):
-        _lib.check(L.fitgnn_project_lift_f64(_lib.dptr(assign), _lib.dptr(cval), N, n, _off(U, 0, c0), k, c1 - c0, _off(CU, 0, c0), k,
-                                             _off(Y, 0, c0) if want_Y else None, k, _lib.dptr(work), wb, _lib.stream_ptr(dev)), "project_lift")
+        _lib.call("fitgnn_project_lift_f64", assign, cval, N, n, _off(U, 0, c0), k, c1 - c0, _off(CU, 0, c0), k, _off(Y, 0, c0) if want_Y else None,
+                  k, work, wb, _lib.stream_ptr(dev))
     return CU, Y
 
 
@@ -1124,9 +1083,8 @@ def laplacian_gram(W, dw, Y):
         for q0, q1 in _col_tiles(k):
             wb = int(L.fitgnn_laplacian_gram_workspace_bytes(N, p1 - p0, q1 - q0))
             work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-            _lib.check(L.fitgnn_laplacian_gram_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dwd), N, _off(Y, 0, p0), k,
-                                                   p1 - p0, _off(Y, 0, q0), k, q1 - q0, _off(G, p0, q0), k, _lib.dptr(work), wb,
-                                                   _lib.stream_ptr(dev)), "laplacian_gram")
+            _lib.call("fitgnn_laplacian_gram_f64", rowptr, col, w, dwd, N, _off(Y, 0, p0), k, p1 - p0, _off(Y, 0, q0), k, q1 - q0, _off(G, p0, q0), k,
+                      work, wb, _lib.stream_ptr(dev))
     return G
 
 
@@ -1142,8 +1100,8 @@ def cross_atb(A, B):
         for q0, q1 in _col_tiles(k2):
             wb = int(L.fitgnn_cross_atb_workspace_bytes(n, p1 - p0, q1 - q0))
             work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-            _lib.check(L.fitgnn_cross_atb_f64(_off(A, 0, p0), k1, p1 - p0, _off(B, 0, q0), k2, q1 - q0, n, _off(out, p0, q0), k2,
-                                              _lib.dptr(work), wb, _lib.stream_ptr(dev)), "cross_atb")
+            _lib.call("fitgnn_cross_atb_f64", _off(A, 0, p0), k1, p1 - p0, _off(B, 0, q0), k2, q1 - q0, n, _off(out, p0, q0), k2, work, wb,
+                      _lib.stream_ptr(dev))
     return out
 
 

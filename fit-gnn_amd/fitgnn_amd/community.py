@@ -84,20 +84,16 @@ class _Level:
             raise _lib.FitgnnError(f"fitgnn_louvain_sweep: N = {self.n}, longest row = {self.max_row} out of range")
         self.work = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         self.counts = (ctypes.c_int32 * 4)()
-        _lib.check(self.L.fitgnn_louvain_bucket_rows(_lib.dptr(rowptr), self.n, self.max_row, self.counts, _lib.dptr(self.work), nbytes,
-                                                     self.stream), "fitgnn_louvain_bucket_rows")
+        _lib.call("fitgnn_louvain_bucket_rows", rowptr, self.n, self.max_row, self.counts, self.work, nbytes, self.stream)
         self.out = torch.zeros(3, dtype=torch.int64, device=self.dev)
 
     def sweep(self, comm, tot, size, t, comm_out):
-        _lib.check(self.L.fitgnn_louvain_sweep(_lib.dptr(self.rowptr), _lib.dptr(self.col), _lib.dptr(self.w), _lib.dptr(self.k), self.n, self.m2,
-                                               _lib.dptr(comm), _lib.dptr(tot), _lib.dptr(size), int(t), self.counts, self.max_row,
-                                               _lib.dptr(comm_out), _lib.dptr(self.work), self.work.numel(), self.stream), "fitgnn_louvain_sweep")
+        _lib.call("fitgnn_louvain_sweep", self.rowptr, self.col, self.w, self.k, self.n, self.m2, comm, tot, size, int(t), self.counts, self.max_row,
+                  comm_out, self.work, self.work.numel(), self.stream)
 
     def stats(self, comm, snapshot, tot, size):
         """tot / size of comm are written; returns (moved, Qnum) as Python ints: the one host read of a sweep."""
-        _lib.check(self.L.fitgnn_louvain_stats(_lib.dptr(self.rowptr), _lib.dptr(self.col), _lib.dptr(self.w), _lib.dptr(self.k), self.n, self.m2,
-                                               _lib.dptr(comm), _lib.dptr(snapshot), _lib.dptr(tot), _lib.dptr(size), _lib.dptr(self.out),
-                                               self.stream), "fitgnn_louvain_stats")
+        _lib.call("fitgnn_louvain_stats", self.rowptr, self.col, self.w, self.k, self.n, self.m2, comm, snapshot, tot, size, self.out, self.stream)
         moved, sum_in, sum_tot2 = (int(v) for v in self.out.tolist())
         return moved, self.m2 * sum_in - sum_tot2
 
@@ -137,8 +133,7 @@ def connected_pieces(rowptr, col, comm):
     label = torch.empty(n, dtype=torch.int32, device=dev)
     nbytes = L.fitgnn_louvain_components_workspace_bytes(n)
     work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    _lib.check(L.fitgnn_louvain_components(_lib.dptr(rowptr), _lib.dptr(col), n, _lib.dptr(comm), _lib.dptr(label), None, _lib.dptr(work),
-                                           nbytes, _lib.stream_ptr(dev)), "fitgnn_louvain_components")
+    _lib.call("fitgnn_louvain_components", rowptr, col, n, comm, label, None, work, nbytes, _lib.stream_ptr(dev))
     return label
 
 

@@ -98,8 +98,7 @@ def make_tiles(ptr, max_rows, whole=True):
     cap = nb + n // max(int(max_rows), 1) + 2
     buf = np.zeros((cap, 4), dtype=np.int32)
     nt = ctypes.c_int64(0)
-    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    _lib.check(_lib.lib().fitgnn_make_tiles_host(vp(ptr), nb, int(max_rows), vp(buf), cap, ctypes.byref(nt)), "fitgnn_make_tiles_host")
+    _lib.call("fitgnn_make_tiles_host", ptr.ctypes.data, nb, int(max_rows), buf.ctypes.data, cap, ctypes.byref(nt))
     out = np.zeros(nt.value, dtype=TILE_DTYPE)
     if nt.value:
         arr = buf[: nt.value]
@@ -177,10 +176,8 @@ def split_blocks(ptr, rowptr, cap, limit=None):
     blocks = np.zeros((max(nb, 1), BLOCK_INTS), dtype=np.int32)
     longs = np.zeros(max(n, 1), dtype=np.int32)
     nt, nl, nlong = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    _lib.check(_lib.lib().fitgnn_split_blocks_host(vp(ptr), nb, vp(rp), int(cap), int(limit), LONG_ROW, vp(tiles4), t_cap, ctypes.byref(nt),
-                                                   vp(blocks), ctypes.byref(nl), vp(longs), len(longs), ctypes.byref(nlong)),
-               "fitgnn_split_blocks_host")
+    _lib.call("fitgnn_split_blocks_host", ptr.ctypes.data, nb, rp.ctypes.data, int(cap), int(limit), LONG_ROW, tiles4.ctypes.data, t_cap,
+              ctypes.byref(nt), blocks.ctypes.data, ctypes.byref(nl), longs.ctypes.data, len(longs), ctypes.byref(nlong))
     small = np.zeros(nt.value, dtype=TILE_DTYPE)
     if nt.value:
         arr = tiles4[: nt.value]
@@ -268,7 +265,6 @@ class _Side:
 
 def plan_tiles(rowptr, col, n_rows, max_rows, max_window, block_ptr=None):
     """fitgnn_plan_tiles_host on host copies of the pattern -> (tiles int32 [T,8], win_cols, lcol) numpy."""
-    L = _lib.lib()
     rp = np.ascontiguousarray(rowptr.detach().cpu().numpy(), dtype=np.int32)
     cc = np.ascontiguousarray(col.detach().cpu().numpy(), dtype=np.int32)
     nnz = int(rp[-1]) if n_rows else 0
@@ -276,14 +272,12 @@ def plan_tiles(rowptr, col, n_rows, max_rows, max_window, block_ptr=None):
     win = np.zeros(max(nnz, 1), dtype=np.int32)
     lcol = np.zeros(max(nnz, 1), dtype=np.int32)
     nt, nw = ctypes.c_int32(0), ctypes.c_int32(0)
-    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     bp, nb = None, 0
     if block_ptr is not None:
         bp = np.ascontiguousarray(block_ptr.detach().cpu().numpy() if torch.is_tensor(block_ptr) else block_ptr, dtype=np.int64)
         nb = len(bp) - 1
-    _lib.check(L.fitgnn_plan_tiles_host(vp(rp), vp(cc), n_rows, n_rows, None if bp is None else vp(bp), nb, int(max_rows),
-                                        int(max_window), vp(tiles), ctypes.byref(nt), vp(win), ctypes.byref(nw), vp(lcol)),
-               "plan_tiles")
+    _lib.call("fitgnn_plan_tiles_host", rp.ctypes.data, cc.ctypes.data, n_rows, n_rows, None if bp is None else bp.ctypes.data, nb, int(max_rows),
+              int(max_window), tiles.ctypes.data, ctypes.byref(nt), win.ctypes.data, ctypes.byref(nw), lcol.ctypes.data)
     return tiles[: nt.value].copy(), win[: max(nw.value, 1)].copy(), lcol[: max(nnz, 1)].copy()
 
 
@@ -353,8 +347,7 @@ class CSRGraph:
         if self.mode == "gcn":
             f.val = torch.empty(self.nnz, dtype=torch.float32, device=dev)
             self.dinv = torch.empty(self.n, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_gcn_norm_csr_f32(_lib.dptr(f.rowptr), _lib.dptr(f.col), None, _lib.dptr(f.val),
-                                                 _lib.dptr(self.dinv), self.n, st), "gcn_norm")
+            _lib.call("fitgnn_gcn_norm_csr_f32", f.rowptr, f.col, None, f.val, self.dinv, self.n, st)
         elif self.mode in ("sum", "gat"):  # gat: values are replaced by attention weights per forward
             f.val = torch.ones(self.nnz, dtype=torch.float32, device=dev)
         elif self.mode == "mean":

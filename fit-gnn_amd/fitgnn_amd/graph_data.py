@@ -314,7 +314,7 @@ class PaddedBatchPlan:
         self.perm = None                                     # int64 [>= steps x B]: set_epoch()
         self._zero_rows = int(ops.ZERO_ROWS)
         self.batch = self._static_batch(g_all)
-        self._L, self._lib = _lib.lib(), _lib
+        self._lib = _lib
 
     def _static_batch(self, g_all):
         """The batch dict the model is stepped on: stand-in x / edge_index / index tensors whose cached objects are the plan's buffers."""
@@ -372,18 +372,14 @@ class PaddedBatchPlan:
 
     def assemble(self):
         """The two launches that fill the static batch with perm[step B .. + B) (capturable)."""
-        L, lb = self._L, self._lib
+        lb = self._lib
         st = lb.stream_ptr(self.dev)
-        d = lb.dptr
-        lb.check(L.fitgnn_batch_offsets(d(self.perm), d(self.step_idx), self.B, d(self.g_row), d(self.g_nnz), d(self.g_tile), d(self.g_mem),
-                                        d(self.off), d(self.gid), d(self.loss_slot), d(self.loss_sum), st), "fitgnn_batch_offsets")
-        lb.check(L.fitgnn_batch_gather(self.B, d(self.off), d(self.gid), d(self.g_row), d(self.g_nnz), d(self.g_tile), d(self.g_mem),
-                                       d(self.rowptr), d(self.col), d(self.val), d(self.tiles), d(self.mem), d(self.pooled), d(self.ax),
-                                       self.ax.stride(0), d(self.tgt), self.n_tgt, self.K, self.R_cap, self.E_cap, self.T_cap, self.M_cap,
-                                       d(self.b_rowptr), d(self.b_col), d(self.b_val), d(self.b_tiles), d(self.b_members), d(self.b_seg_off),
-                                       d(self.b_seg_of_row), d(self.b_inv_cnt), d(self.b_ax), self.b_ax.stride(0), d(self.b_tgt), d(self.mem_rank),
-                                       d(self.b_members64), d(self.b_cseg), d(self.b_pos), self._zero_rows, st),
-                 "fitgnn_batch_gather")
+        lb.call("fitgnn_batch_offsets", self.perm, self.step_idx, self.B, self.g_row, self.g_nnz, self.g_tile, self.g_mem, self.off, self.gid,
+                self.loss_slot, self.loss_sum, st)
+        lb.call("fitgnn_batch_gather", self.B, self.off, self.gid, self.g_row, self.g_nnz, self.g_tile, self.g_mem, self.rowptr, self.col, self.val,
+                self.tiles, self.mem, self.pooled, self.ax, self.ax.stride(0), self.tgt, self.n_tgt, self.K, self.R_cap, self.E_cap, self.T_cap,
+                self.M_cap, self.b_rowptr, self.b_col, self.b_val, self.b_tiles, self.b_members, self.b_seg_off, self.b_seg_of_row, self.b_inv_cnt,
+                self.b_ax, self.b_ax.stride(0), self.b_tgt, self.mem_rank, self.b_members64, self.b_cseg, self.b_pos, self._zero_rows, st)
 
 
 def cut_tiles_at_graphs(base, g_row, rowptr):

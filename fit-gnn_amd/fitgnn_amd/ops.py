@@ -195,7 +195,7 @@ def gemm_exact(a, b, form, cfg=DEFAULT, out=None, a_rows=None, b_rows=None):
         a_rows = _row_list(a_rows)
     if b_rows is not None:
         b_rows = _row_list(b_rows)
-    _lib.require_cuda(a, b, a_rows, b_rows)
+    _lib.require_cuda(a)   # a.device places the output and names the stream; the call checks the others
     a0 = a.shape[0] if a_rows is None else int(a_rows.numel())   # rows of the product's operands
     b0 = b.shape[0] if b_rows is None else int(b_rows.numel())
     if form == "nt":
@@ -213,11 +213,9 @@ def gemm_exact(a, b, form, cfg=DEFAULT, out=None, a_rows=None, b_rows=None):
         assert out.shape == (I, J) and out.dtype == torch.float32 and out.stride(1) == 1 and out.is_cuda
     wb = int(L.fitgnn_gemm_exact_workspace_bytes(I, J, K, akm, bkm))
     ws = torch.empty(wb // 4, dtype=torch.float32, device=a.device) if wb else None
-    ev = _gemm_events(cfg, "gemm_f32_kernel[%s]" % form, 2.0 * I * J * K)
-    rc = L.fitgnn_gemm_exact_rows_f32(_lib.dptr(a), a.stride(0), akm, _lib.dptr(a_rows), _lib.dptr(b), b.stride(0), bkm, _lib.dptr(b_rows),
-                                      I, J, K, _lib.dptr(out), out.stride(0), _lib.dptr(ws), _lib.stream_ptr(a.device))
-    _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_exact_rows_f32")
+    with _gemm_events(cfg, "gemm_f32_kernel[%s]" % form, 2.0 * I * J * K):
+        _lib.call("fitgnn_gemm_exact_rows_f32", a, a.stride(0), akm, a_rows, b, b.stride(0), bkm, b_rows, I, J, K, out, out.stride(0), ws,
+                  _lib.stream_ptr(a.device))
     return out
 
 
@@ -231,8 +229,7 @@ def gemm_exact_epi(a, b, rows, bias, epilogue, p=0.0, seed=0, mask=None, cfg=DEF
     I = a.shape[0] if a_rows is None else int(a_rows.numel())
     assert b.shape[1] == K
     shape, nchunks, main_rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
-    _lib.check(L.fitgnn_gemm_exact_plan(I, J, K, 0, 0, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows)),
-               "fitgnn_gemm_exact_plan")
+    _lib.call("fitgnn_gemm_exact_plan", I, J, K, 0, 0, ctypes.byref(shape), ctypes.byref(nchunks), ctypes.byref(main_rows))
     if nchunks.value > 1:
         return None
     seed, epilogue = _seed_arg(seed, epilogue)
@@ -245,12 +242,9 @@ def gemm_exact_epi(a, b, rows, bias, epilogue, p=0.0, seed=0, mask=None, cfg=DEF
     out = torch.empty((I, J), dtype=torch.float32, device=a.device)
     wb = int(L.fitgnn_gemm_exact_workspace_bytes(I, J, K, 0, 0))
     ws = torch.empty(wb // 4, dtype=torch.float32, device=a.device) if wb else None
-    ev = _gemm_events(cfg, "gemm_f32_kernel[nt+epi]", 2.0 * I * J * K)
-    rc = L.fitgnn_gemm_exact_epi_rows_f32(_lib.dptr(a), a.stride(0), _lib.dptr(a_rows), _lib.dptr(b), b.stride(0), I, J, K, _lib.dptr(out),
-                                          out.stride(0), _lib.dptr(rows), _lib.dptr(None if bias is None else _f32c(bias)), epilogue,
-                                          float(p), seed, _lib.dptr(mask), _lib.dptr(ws), _lib.stream_ptr(a.device))
-    _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_exact_epi_rows_f32")
+    with _gemm_events(cfg, "gemm_f32_kernel[nt+epi]", 2.0 * I * J * K):
+        _lib.call("fitgnn_gemm_exact_epi_rows_f32", a, a.stride(0), a_rows, b, b.stride(0), I, J, K, out, out.stride(0), rows,
+                  None if bias is None else _f32c(bias), epilogue, float(p), seed, mask, ws, _lib.stream_ptr(a.device))
     return out
 
 
@@ -318,14 +312,18 @@ def _atb_ok(t):
 
 class _timed:
     """`with _timed(cfg, kind):` -- when cfg.profile is a list, a HIP-event pair around the launches inside (recorded on torch's
-    current stream = the one handed to the C ABI) is appended to it as (start, end, kind)."""
-    __slots__ = ("cfg", "kind", "ev")
+    current stream = the one handed to the C ABI) is appended to it as (start, end, kind).
+    `with _timed(sink=events):` -- the same around another list (cfg.profile_fused, a trainer's comm_events; None: nothing is
+    recorded), whose records are (start, end) + tail.  The pair is closed and appended also when a launch inside raises."""
+    __slots__ = ("sink", "tail", "ev")
 
-    def __init__(self, cfg, kind):
-        self.cfg, self.kind, self.ev = cfg, kind, None
+    def __init__(self, cfg=None, kind=None, sink=None, tail=()):
+        if cfg is not None:
+            sink, tail = cfg.profile, (kind,)
+        self.sink, self.tail, self.ev = sink, tail, None
 
     def __enter__(self):
-        if self.cfg is not None and self.cfg.profile is not None:
+        if self.sink is not None:
             self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             self.ev[0].record()
         return self
@@ -333,23 +331,14 @@ class _timed:
     def __exit__(self, *exc):
         if self.ev is not None:
             self.ev[1].record()
-            self.cfg.profile.append((self.ev[0], self.ev[1], self.kind))
+            self.sink.append(self.ev + self.tail)
         return False
 
 
 def _gemm_events(cfg, name, flops):
-    """cfg.profile_gemm: list of (start event, end event, kernel name, bf16 flops) per hand-written GEMM launch."""
-    if cfg.profile_gemm is None:
-        return None
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), name, flops)
-    ev[0].record()
-    return ev
-
-
-def _gemm_done(cfg, ev):
-    if ev is not None:
-        ev[1].record()
-        cfg.profile_gemm.append(ev)
+    """`with _gemm_events(cfg, name, flops):` -- cfg.profile_gemm: list of (start event, end event, kernel name, bf16 flops) per
+    hand-written GEMM launch."""
+    return _timed(sink=cfg.profile_gemm, tail=(name, flops))
 
 
 def gemm_atb(a, b, cfg=DEFAULT):
@@ -359,11 +348,8 @@ def gemm_atb(a, b, cfg=DEFAULT):
     R, M, N = a.shape[0], a.shape[1], b.shape[1]
     ws = torch.empty(int(L.fitgnn_gemm_atb_workspace_bytes(R, M, N)) // 4, dtype=torch.float32, device=a.device)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    ev = _gemm_events(cfg, "gemm_atb_kernel+atb_reduce_kernel", 6.0 * R * M * N)
-    rc = L.fitgnn_gemm_atb_f32(_lib.dptr(a), a.stride(0), _lib.dptr(b), b.stride(0), R, M, N, _lib.dptr(out), _lib.dptr(ws),
-                               _lib.stream_ptr(a.device))
-    _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_atb_f32")
+    with _gemm_events(cfg, "gemm_atb_kernel+atb_reduce_kernel", 6.0 * R * M * N):
+        _lib.call("fitgnn_gemm_atb_f32", a, a.stride(0), b, b.stride(0), R, M, N, out, ws, _lib.stream_ptr(a.device))
     return out
 
 
@@ -374,8 +360,7 @@ def _presplit(b, K_pad=None):
     N, K = b.shape
     Kp = K if K_pad is None else int(K_pad)
     img = torch.empty(int(L.fitgnn_gemm_nt_presplit_bytes(N, Kp)), dtype=torch.uint8, device=b.device)
-    _lib.check(L.fitgnn_gemm_nt_presplit_f32(_lib.dptr(b), b.stride(0), b.stride(1), N, Kp, K, _lib.dptr(img),
-                                             _lib.stream_ptr(b.device)), "fitgnn_gemm_nt_presplit_f32")
+    _lib.call("fitgnn_gemm_nt_presplit_f32", b, b.stride(0), b.stride(1), N, Kp, K, img, _lib.stream_ptr(b.device))
     return img
 
 
@@ -393,15 +378,11 @@ def padded_table(x):
 
 def gemm_nt_padded_k(a_pad, b, cfg=DEFAULT):
     """a_pad [R, K'] (zero columns from K = b.shape[1] on) @ b [N, K]^T through the pre-split path."""
-    L = _lib.lib()
     R, Kp, N = a_pad.shape[0], a_pad.shape[1], b.shape[0]
     out = torch.empty((R, N), dtype=torch.float32, device=a_pad.device)
     img = _presplit(b, K_pad=Kp)
-    ev = _gemm_events(cfg, "gemm_nt_kernel<4,false,true>", 6.0 * R * N * Kp)
-    rc = L.fitgnn_gemm_nt_pre_f32(_lib.dptr(a_pad), a_pad.stride(0), _lib.dptr(img), R, N, Kp, _lib.dptr(out), N,
-                                  _lib.stream_ptr(a_pad.device))
-    _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_nt_pre_f32")
+    with _gemm_events(cfg, "gemm_nt_kernel<4,false,true>", 6.0 * R * N * Kp):
+        _lib.call("fitgnn_gemm_nt_pre_f32", a_pad, a_pad.stride(0), img, R, N, Kp, out, N, _lib.stream_ptr(a_pad.device))
     return out
 
 
@@ -414,19 +395,15 @@ def _padded_table_path(Xt, W, cfg):
 
 def gemm_nt(a, b, cfg=DEFAULT):
     """a [R, K] @ b [N, K]^T through the hand-written MFMA kernel (csrc/gemm_nt.hip).  b may be any strided view."""
-    L = _lib.lib()
     R, K, N = a.shape[0], a.shape[1], b.shape[0]
     out = torch.empty((R, N), dtype=torch.float32, device=a.device)
     if cfg.nt_presplit and _full_grid(R, N):
         img = _presplit(b)
-        ev = _gemm_events(cfg, "gemm_nt_kernel<4,false,true>", 6.0 * R * N * K)
-        rc = L.fitgnn_gemm_nt_pre_f32(_lib.dptr(a), a.stride(0), _lib.dptr(img), R, N, K, _lib.dptr(out), N, _lib.stream_ptr(a.device))
-        _gemm_done(cfg, ev)
-        _lib.check(rc, "fitgnn_gemm_nt_pre_f32")
+        with _gemm_events(cfg, "gemm_nt_kernel<4,false,true>", 6.0 * R * N * K):
+            _lib.call("fitgnn_gemm_nt_pre_f32", a, a.stride(0), img, R, N, K, out, N, _lib.stream_ptr(a.device))
         return out
     b = b.contiguous()
-    _lib.check(L.fitgnn_gemm_nt_f32(_lib.dptr(a), a.stride(0), _lib.dptr(b), b.stride(0), R, N, K, _lib.dptr(out), N,
-                                    _lib.stream_ptr(a.device)), "fitgnn_gemm_nt_f32")
+    _lib.call("fitgnn_gemm_nt_f32", a, a.stride(0), b, b.stride(0), R, N, K, out, N, _lib.stream_ptr(a.device))
     return out
 
 
@@ -446,12 +423,9 @@ def gemm_nt_epilogue_bwd(a, b, out, epilogue, p=0.0, seed=0, mask=None, want_db=
     else:
         b_arg = b.contiguous()
         ldb = b_arg.stride(0)
-    ev = _gemm_events(cfg, "gemm_nt_kernel<4,true,%s>" % ("true" if ldb == 0 else "false"), 6.0 * R * N * K)
-    rc = L.fitgnn_gemm_nt_epilogue_bwd_f32(_lib.dptr(a), a.stride(0), _lib.dptr(b_arg), ldb, R, N, K, _lib.dptr(out),
-                                           _lib.dptr(dZ), epilogue, float(p), seed, _lib.dptr(mask), _lib.dptr(db),
-                                           _lib.dptr(work), wb, _lib.stream_ptr(a.device))
-    _gemm_done(cfg, ev)
-    _lib.check(rc, "fitgnn_gemm_nt_epilogue_bwd_f32")
+    with _gemm_events(cfg, "gemm_nt_kernel<4,true,%s>" % ("true" if ldb == 0 else "false"), 6.0 * R * N * K):
+        _lib.call("fitgnn_gemm_nt_epilogue_bwd_f32", a, a.stride(0), b_arg, ldb, R, N, K, out, dZ, epilogue, float(p), seed, mask, db, work,
+                  wb, _lib.stream_ptr(a.device))
     return dZ, db
 
 
@@ -503,7 +477,6 @@ def mm_at_b(a, b, cfg=DEFAULT, out=None, b_rows=None):
     part = torch.bmm(a[:main].view(B, Kc, a.shape[1]).transpose(1, 2), b[:main].view(B, Kc, b.shape[1]))
     W = part.shape[1] * part.shape[2]
     if part.is_cuda and W % 4 == 0:
-        L = _lib.lib()
         st = _lib.stream_ptr(part.device)
         # many partials of a narrow product (GAT's h^T [da_src da_dst] at S-products: 5 856 partials of 1 024 floats) would be ONE
         # workgroup walking them all (765 us): fold them in two fixed-order stages -- viewed as [B / G, G x W] the same kernel sums
@@ -513,14 +486,14 @@ def mm_at_b(a, b, cfg=DEFAULT, out=None, b_rows=None):
             Bg = B // G
             flat = part.view(B, W)
             stage = torch.empty((G + B - Bg * G, W), dtype=torch.float32, device=part.device)
-            _lib.check(L.fitgnn_sum_leading_f32(_lib.dptr(flat), Bg, G * W, _lib.dptr(stage), st), "fitgnn_sum_leading_f32")
+            _lib.call("fitgnn_sum_leading_f32", flat, Bg, G * W, stage, st)
             if B > Bg * G:
                 stage[G:].copy_(flat[Bg * G:])
             part, B = stage, int(stage.shape[0])
             out = torch.empty((a.shape[1], b.shape[1]), dtype=torch.float32, device=part.device)
         else:
             out = torch.empty(part.shape[1:], dtype=torch.float32, device=part.device)
-        _lib.check(L.fitgnn_sum_leading_f32(_lib.dptr(part), B, W, _lib.dptr(out), st), "fitgnn_sum_leading_f32")
+        _lib.call("fitgnn_sum_leading_f32", part, B, W, out, st)
     else:
         out = part.sum(0)
     if main < R:
@@ -557,8 +530,7 @@ def colsum_narrow(x, out=None):
         out = torch.empty(C, dtype=torch.float32, device=x.device)
     wb = int(L.fitgnn_colsum_narrow_workspace_bytes(n, C))
     work = torch.empty(max(wb, 4), dtype=torch.uint8, device=x.device)
-    _lib.check(L.fitgnn_colsum_narrow_f32(_lib.dptr(x), x.stride(0), n, C, _lib.dptr(out), _lib.dptr(work), wb,
-                                          _lib.stream_ptr(x.device)), "fitgnn_colsum_narrow_f32")
+    _lib.call("fitgnn_colsum_narrow_f32", x, x.stride(0), n, C, out, work, wb, _lib.stream_ptr(x.device))
     return out
 
 
@@ -616,9 +588,7 @@ def softmax_nll_raw(z, idx, labels, scale):
     dz = torch.empty((n_rows, ldz), dtype=torch.float32, device=z.device)
     wb = int(L.fitgnn_softmax_nll_workspace_bytes(n))
     work = torch.empty(wb, dtype=torch.uint8, device=z.device)
-    _lib.check(L.fitgnn_softmax_nll_f32(_lib.dptr(z), ldz, n_rows, C, _lib.dptr(idx), _lib.dptr(labels), n, float(scale),
-                                        _lib.dptr(loss), _lib.dptr(dz), _lib.dptr(work), wb, _lib.stream_ptr(z.device)),
-               "fitgnn_softmax_nll_f32")
+    _lib.call("fitgnn_softmax_nll_f32", z, ldz, n_rows, C, idx, labels, n, float(scale), loss, dz, work, wb, _lib.stream_ptr(z.device))
     return loss, (dz if ldz == C else dz[:, :C])
 
 
@@ -648,8 +618,7 @@ def l1_loss_raw(out, tgt, scale, loss_out=None):
     assert o.numel() == t.numel()
     loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=o.device)
     grad = torch.empty_like(o)
-    _lib.check(_lib.lib().fitgnn_l1_loss_f32(_lib.dptr(o), _lib.dptr(t), int(o.numel()), float(scale), _lib.dptr(loss), _lib.dptr(grad),
-                                             _lib.stream_ptr(o.device)), "fitgnn_l1_loss_f32")
+    _lib.call("fitgnn_l1_loss_f32", o, t, int(o.numel()), float(scale), loss, grad, _lib.stream_ptr(o.device))
     return loss, grad.view(out.shape)
 
 
@@ -664,8 +633,7 @@ class L1Loss(torch.autograd.Function):
         assert o.numel() == t.numel()
         loss = torch.empty(1, dtype=torch.float32, device=o.device)
         grad = torch.empty_like(o)
-        _lib.check(_lib.lib().fitgnn_l1_loss_f32(_lib.dptr(o), _lib.dptr(t), int(o.numel()), float(scale), _lib.dptr(loss), _lib.dptr(grad),
-                                                 _lib.stream_ptr(o.device)), "fitgnn_l1_loss_f32")
+        _lib.call("fitgnn_l1_loss_f32", o, t, int(o.numel()), float(scale), loss, grad, _lib.stream_ptr(o.device))
         ctx.save_for_backward(grad)
         ctx.shape = out.shape
         return loss[0]
@@ -695,25 +663,15 @@ def _f32c(t):
 def spmm_raw(rowptr, col, val, tiles, X, n_rows, bias=None, epilogue=0, p=0.0, seed=0, mask=None, out=None, window_rows=0,
              lcol=None, win_cols=None, xrow=None, cfg=DEFAULT, profile_kind=None, zero_from=-1):
     """Y = epilogue(A @ X) through fitgnn_spmm_csr_f32.  X: [n_cols_of_A, H] f32 contiguous."""
-    _lib.require_cuda(rowptr, col, val, tiles, X, bias, mask)
-    L = _lib.lib()
+    _lib.require_cuda(X)   # _f32c touches it, X.device names the stream; the call checks the others
     X = _f32c(X)
     H = X.shape[1]
     seed, epilogue = _seed_arg(seed, epilogue)
     Y = out if out is not None else torch.empty((n_rows, H), dtype=torch.float32, device=X.device)
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    rc = L.fitgnn_spmm_csr_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(X), X.stride(0) if X.numel() else H,
-                               _lib.dptr(Y), Y.stride(0) if Y.numel() else H, n_rows, H, _lib.dptr(tiles), int(tiles.shape[0]),
-                               _lib.dptr(lcol), _lib.dptr(win_cols), _lib.dptr(xrow), int(zero_from), int(window_rows), _lib.dptr(bias), epilogue, float(p),
-                               seed, _lib.dptr(mask),
-                               _lib.stream_ptr(X.device))
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], profile_kind or ("gather" if (epilogue & _lib.SPMM_GATHER) else "tile")))
-    _lib.check(rc, "fitgnn_spmm_csr_f32")
+    with _timed(cfg, profile_kind or ("gather" if (epilogue & _lib.SPMM_GATHER) else "tile")):
+        _lib.call("fitgnn_spmm_csr_f32", rowptr, col, val, X, X.stride(0) if X.numel() else H, Y, Y.stride(0) if Y.numel() else H, n_rows, H,
+                  tiles, int(tiles.shape[0]), lcol, win_cols, xrow, int(zero_from), int(window_rows), bias, epilogue, float(p), seed, mask,
+                  _lib.stream_ptr(X.device))
     return Y
 
 
@@ -728,10 +686,7 @@ def epilogue_bwd_raw(dOut, out, epilogue, p=0.0, seed=0, mask=None, want_db=True
     db = (db_out if db_out is not None else torch.empty(H, dtype=torch.float32, device=dOut.device)) if want_db else None
     wb = int(L.fitgnn_epilogue_bwd_workspace_bytes(n, H)) if want_db else 0
     work = torch.empty(max(wb, 4), dtype=torch.uint8, device=dOut.device)
-    rc = L.fitgnn_epilogue_bwd_f32(_lib.dptr(dOut), _lib.dptr(out), _lib.dptr(dZ), n, H, epilogue, float(p),
-                                   seed, _lib.dptr(mask), _lib.dptr(db), _lib.dptr(work), wb,
-                                   _lib.stream_ptr(dOut.device))
-    _lib.check(rc, "fitgnn_epilogue_bwd_f32")
+    _lib.call("fitgnn_epilogue_bwd_f32", dOut, out, dZ, n, H, epilogue, float(p), seed, mask, db, work, wb, _lib.stream_ptr(dOut.device))
     return dZ, db
 
 
@@ -748,9 +703,8 @@ def epilogue_bwd_rows_raw(dOutc, outc, rows, epilogue, p=0.0, seed=0, mask=None,
     db = (db_out if db_out is not None else torch.empty(H, dtype=torch.float32, device=outc.device)) if want_db else None
     wb = int(L.fitgnn_epilogue_bwd_workspace_bytes(n, H)) if want_db else 0
     work = torch.empty(max(wb, 4), dtype=torch.uint8, device=outc.device)
-    rc = L.fitgnn_epilogue_bwd_rows_f32(_lib.dptr(dOutc), _lib.dptr(outc), _lib.dptr(rows), n, 1, _lib.dptr(dZ), H, epilogue, float(p), seed,
-                                        _lib.dptr(mask), _lib.dptr(db), _lib.dptr(work), wb, _lib.stream_ptr(outc.device))
-    _lib.check(rc, "fitgnn_epilogue_bwd_rows_f32")
+    _lib.call("fitgnn_epilogue_bwd_rows_f32", dOutc, outc, rows, n, 1, dZ, H, epilogue, float(p), seed, mask, db, work, wb,
+              _lib.stream_ptr(outc.device))
     return dZ, db
 
 
@@ -758,22 +712,12 @@ def spmm_blocks_raw(rowptr, col, val, blocks, long_rows, X, Y, bias=None, epilog
                     xcol=None, zero_from=-1):
     """The rows of the listed large diagonal blocks of Y = epilogue(A @ X) through fitgnn_spmm_csr_blocks_f32 (one workgroup
     walks a whole subgraph: every operand row read once)."""
-    _lib.require_cuda(rowptr, col, val, blocks, long_rows, X, Y, bias, mask, xrow, xcol)
-    L = _lib.lib()
+    _lib.require_cuda(X)   # X.device names the stream; the call checks the others
     seed, epilogue = _seed_arg(seed, epilogue)
     H = X.shape[1]
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    rc = L.fitgnn_spmm_csr_blocks_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(X), X.stride(0), _lib.dptr(Y), Y.stride(0),
-                                      int(Y.shape[0]), H, _lib.dptr(blocks), int(blocks.shape[0]), _lib.dptr(long_rows), _lib.dptr(xrow),
-                                      _lib.dptr(xcol), int(zero_from), _lib.dptr(bias),
-                                      epilogue, float(p), seed, _lib.dptr(mask), _lib.stream_ptr(X.device))
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], "blocks"))
-    _lib.check(rc, "fitgnn_spmm_csr_blocks_f32")
+    with _timed(cfg, "blocks"):
+        _lib.call("fitgnn_spmm_csr_blocks_f32", rowptr, col, val, X, X.stride(0), Y, Y.stride(0), int(Y.shape[0]), H, blocks,
+                  int(blocks.shape[0]), long_rows, xrow, xcol, int(zero_from), bias, epilogue, float(p), seed, mask, _lib.stream_ptr(X.device))
     return Y
 
 
@@ -837,95 +781,68 @@ def _spmm_split(g, side, val, Xc, epi, kw):
     kind = kw.pop("profile_kind", None)
     zero_from = kw.pop("zero_from", -1)
     Y = out if out is not None else torch.empty((g.n, Xc.shape[1]), dtype=torch.float32, device=Xc.device)
-    ev = None
-    if cfg.profile is not None:   # ONE event pair around both launches: together they are the SpMM
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
     quiet = cfg if cfg.profile is None else cfg.replace(profile=None)
-    if side.small_tiles.shape[0]:
-        spmm_raw(side.rowptr, side.col, val, side.small_tiles, Xc, g.n, epilogue=epi, window_rows=g.window_rows, out=Y, cfg=quiet,
-                 xrow=xrow, zero_from=zero_from, **kw)
-    xcol = None
-    if xrow is not None:   # the table row of every CSR entry, listed once per (pattern side, index): see fitgnn_spmm_csr_blocks_f32
-        xcol = _entry_rows(side, xrow)
-    spmm_blocks_raw(side.rowptr, side.col, val, side.blocks, side.long_rows, Xc, Y, epilogue=epi, cfg=quiet, xrow=xrow, xcol=xcol,
-                    zero_from=zero_from, **kw)
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], kind or ("tile" if xrow is None else "table")))   # "table": layer 0 on the de-duplicated table
+    # ONE event pair around both launches: together they are the SpMM ("table": layer 0 on the de-duplicated table)
+    with _timed(cfg, kind or ("tile" if xrow is None else "table")):
+        if side.small_tiles.shape[0]:
+            spmm_raw(side.rowptr, side.col, val, side.small_tiles, Xc, g.n, epilogue=epi, window_rows=g.window_rows, out=Y, cfg=quiet,
+                     xrow=xrow, zero_from=zero_from, **kw)
+        xcol = None
+        if xrow is not None:   # the table row of every CSR entry, listed once per (pattern side, index): see fitgnn_spmm_csr_blocks_f32
+            xcol = _entry_rows(side, xrow)
+        spmm_blocks_raw(side.rowptr, side.col, val, side.blocks, side.long_rows, Xc, Y, epilogue=epi, cfg=quiet, xrow=xrow, xcol=xcol,
+                        zero_from=zero_from, **kw)
     return Y
 
 
 def _spmm_stream(g, side, Xc, xrow, cfg, kind, bias=None, epilogue=0, p=0.0, seed=0, mask=None, dz=None):
     """epilogue(A @ X) over EVERY row of a segmented batch through the segment-streaming kernel.  dz = (prev, want_db): the
     epilogue flags / p / seed / mask are the previous layer's forward ones and the store applies its derivative -> (dZ, db)."""
-    L = _lib.lib()
-    _lib.require_cuda(Xc, xrow, bias, mask)
+    _lib.require_cuda(Xc, xrow)   # Xc.device names the stream, _entry_rows indexes with xrow; the call checks the others
     H, dev = Xc.shape[1], Xc.device
     xcol = _entry_rows(side, xrow) if xrow is not None else None
     Y = torch.empty((g.n, H), dtype=torch.float32, device=dev)
     st = _lib.stream_ptr(dev)
     n_seg, n_ranges = int(g.seg.numel()) - 1, int(g.range_seg.numel()) - 1
     seed_v, epi_v = _seed_arg(seed, epilogue)
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
     db = None
-    if dz is None:
-        _lib.check(L.fitgnn_spmm_csr_stream_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), int(side.col.numel()),
-                                                _lib.dptr(Xc), Xc.stride(0), _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(g.seg), n_seg,
-                                                _lib.dptr(g.range_seg), n_ranges, _lib.dptr(xrow), _lib.dptr(xcol), _lib.dptr(bias), epi_v,
-                                                float(p), seed_v, _lib.dptr(mask), st), "fitgnn_spmm_csr_stream_f32")
-    else:
-        prev, want_db = dz
-        part = torch.empty((n_ranges, H), dtype=torch.float32, device=dev) if want_db else None
-        _lib.check(L.fitgnn_spmm_csr_stream_dz_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), int(side.col.numel()),
-                                                   _lib.dptr(Xc), Xc.stride(0), _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(g.seg), n_seg,
-                                                   _lib.dptr(g.range_seg), n_ranges, _lib.dptr(xrow), _lib.dptr(xcol), _lib.dptr(prev), epi_v,
-                                                   float(p), seed_v, _lib.dptr(mask), _lib.dptr(part), st), "fitgnn_spmm_csr_stream_dz_f32")
-        if want_db:
-            db = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part), n_ranges, H, _lib.dptr(db), st), "fitgnn_colsum_partials_f32")
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], kind or ("dz" if dz is not None else ("tile" if xrow is None else "table"))))
+    with _timed(cfg, kind or ("dz" if dz is not None else ("tile" if xrow is None else "table"))):
+        if dz is None:
+            _lib.call("fitgnn_spmm_csr_stream_f32", side.rowptr, side.col, side.val, int(side.col.numel()), Xc, Xc.stride(0), Y, Y.stride(0), g.n,
+                      H, g.seg, n_seg, g.range_seg, n_ranges, xrow, xcol, bias, epi_v, float(p), seed_v, mask, st)
+        else:
+            prev, want_db = dz
+            part = torch.empty((n_ranges, H), dtype=torch.float32, device=dev) if want_db else None
+            _lib.call("fitgnn_spmm_csr_stream_dz_f32", side.rowptr, side.col, side.val, int(side.col.numel()), Xc, Xc.stride(0), Y, Y.stride(0),
+                      g.n, H, g.seg, n_seg, g.range_seg, n_ranges, xrow, xcol, prev, epi_v, float(p), seed_v, mask, part, st)
+            if want_db:   # at most 8192 ranges (csr.stream_ranges): _fold_partials folds them in the kernel alone
+                db = _fold_partials(part, dev, st)
     return Y if dz is None else (Y, db)
 
 
 def _spmm_rows_compact(g, side, Xc, xrow, zero_from, cfg, kind, dz=None, val=None):
     """A @ X for a compact operand through the row-streaming kernel.  dz = (prev, epilogue, p, seed, mask, want_db): with the
     previous layer's derivative in the store -> (dZ, db).  val: per-call CSR values (side's entry order) instead of side.val."""
-    L = _lib.lib()
-    _lib.require_cuda(Xc, xrow, val)
+    _lib.require_cuda(Xc, xrow)   # Xc.device names the stream, _entry_rows indexes with xrow; the call checks the others
     val = side.val if val is None else val
     H, dev = Xc.shape[1], Xc.device
     xcol = _entry_rows(side, xrow)
     Y = torch.empty((g.n, H), dtype=torch.float32, device=dev)
     st = _lib.stream_ptr(dev)
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
     db = None
-    if dz is None:
-        _lib.check(L.fitgnn_spmm_rows_compact_f32(_lib.dptr(side.rowptr), _lib.dptr(xcol), _lib.dptr(val), int(side.col.numel()), _lib.dptr(Xc),
-                                                  Xc.stride(0), int(zero_from), _lib.dptr(Y), Y.stride(0), g.n, H, st), "fitgnn_spmm_rows_compact_f32")
-    else:
-        prev, epilogue, p, seed, mask, want_db = dz
-        seed_v, epi_v = _seed_arg(seed, epilogue & ~_lib.SPMM_GATHER)
-        n_part = int(L.fitgnn_spmm_rows_compact_parts(g.n))
-        part = torch.empty((n_part, H), dtype=torch.float32, device=dev) if want_db else None
-        _lib.check(L.fitgnn_spmm_rows_compact_dz_f32(_lib.dptr(side.rowptr), _lib.dptr(xcol), _lib.dptr(val), int(side.col.numel()),
-                                                     _lib.dptr(Xc), Xc.stride(0), int(zero_from), _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(prev),
-                                                     epi_v, float(p), seed_v, _lib.dptr(mask), _lib.dptr(part), st),
-                   "fitgnn_spmm_rows_compact_dz_f32")
-        if want_db:
-            db = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part), n_part, H, _lib.dptr(db), st), "fitgnn_colsum_partials_f32")
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], kind or ("compact" if dz is None else "compact_dz")))
+    with _timed(cfg, kind or ("compact" if dz is None else "compact_dz")):
+        if dz is None:
+            _lib.call("fitgnn_spmm_rows_compact_f32", side.rowptr, xcol, val, int(side.col.numel()), Xc, Xc.stride(0), int(zero_from), Y,
+                      Y.stride(0), g.n, H, st)
+        else:
+            prev, epilogue, p, seed, mask, want_db = dz
+            seed_v, epi_v = _seed_arg(seed, epilogue & ~_lib.SPMM_GATHER)
+            n_part = int(_lib.lib().fitgnn_spmm_rows_compact_parts(g.n))
+            part = torch.empty((n_part, H), dtype=torch.float32, device=dev) if want_db else None
+            _lib.call("fitgnn_spmm_rows_compact_dz_f32", side.rowptr, xcol, val, int(side.col.numel()), Xc, Xc.stride(0), int(zero_from), Y,
+                      Y.stride(0), g.n, H, prev, epi_v, float(p), seed_v, mask, part, st)
+            if want_db:   # at most 8192 parts (csrc/spmm.hip rows_plan): _fold_partials folds them in the kernel alone
+                db = _fold_partials(part, dev, st)
     return Y if dz is None else (Y, db)
 
 
@@ -1004,7 +921,6 @@ def spmm_two_hop_blocks(g, Xc, prev, rows, pos, link, cfg=DEFAULT, profile_kind=
     """(A_hat^T dZ, db) with dZ = (A_hat^T Xc) . ELU'/dropout'(prev) made in the whole-subgraph kernel's LDS windows instead of being
     written and re-read (fitgnn_two_hop_rows_f32 for the side table, fitgnn_spmm_two_hop_blocks_f32; the rows outside the blocks
     through the tile kernel over the table).  Xc: the compact operand [len(rows) + ZERO_ROWS, H]; pos = _compact_positions(g, rows)."""
-    L = _lib.lib()
     side = g.t
     Xc, prev = _f32c(Xc), _f32c(prev)
     _lib.require_cuda(Xc, prev, rows, pos, link.mask)
@@ -1014,52 +930,44 @@ def spmm_two_hop_blocks(g, Xc, prev, rows, pos, link, cfg=DEFAULT, profile_kind=
     n_zt = int(ix["zt_rows"].numel())
     seed_v, epi_v = _seed_arg(link.seed, link.epi)
     st = _lib.stream_ptr(dev)
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    ZT = torch.empty((max(n_zt, 1), H), dtype=torch.float32, device=dev)
-    _lib.check(L.fitgnn_two_hop_rows_f32(_lib.dptr(side.rowptr), _lib.dptr(ix["zcol"]), _lib.dptr(side.val), _lib.dptr(Xc), Xc.stride(0), n_sel,
-                                         _lib.dptr(ix["zt_rows"]), n_zt, _lib.dptr(prev), H, epi_v, float(link.p), seed_v, _lib.dptr(link.mask),
-                                         _lib.dptr(ZT), ZT.stride(0), st), "fitgnn_two_hop_rows_f32")
-    Y = torch.empty((g.n, H), dtype=torch.float32, device=dev)
-    quiet = cfg if cfg.profile is None else cfg.replace(profile=None)
-    if side.small_tiles.shape[0]:
-        spmm_raw(side.rowptr, side.col, side.val, side.small_tiles, ZT, g.n, window_rows=g.window_rows, out=Y, cfg=quiet, xrow=ix["zrow"])
-    n_blocks = int(side.blocks.shape[0])
-    # one partial row of column sums per block + one for the rows outside the blocks (their dZ sits in the table).  No fill: the
-    # kernel writes the row of every record, a padding record's as zeros (FITGNN_POISON=1 hands out NaN, which is how the tests check it)
-    part = _scratch((n_blocks + 1, H), dev) if link.want_db else None
-    _lib.check(L.fitgnn_spmm_two_hop_blocks_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(ZT), ZT.stride(0),
-                                                _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(side.blocks), n_blocks, _lib.dptr(side.long_rows),
-                                                _lib.dptr(ix["zrow"]), _lib.dptr(ix["zcol"]), _lib.dptr(prev), _lib.dptr(Xc), Xc.stride(0), n_sel,
-                                                _lib.dptr(ix["row_p"]), _lib.dptr(ix["row_w"]), epi_v, float(link.p), seed_v, _lib.dptr(link.mask),
-                                                _lib.dptr(part), st), "fitgnn_spmm_two_hop_blocks_f32")
-    db = None
-    if link.want_db:
-        if ix["tile_zt"].numel():
-            torch.sum(ZT.index_select(0, ix["tile_zt"]), 0, out=part[n_blocks])
-        else:
-            part[n_blocks].zero_()
-        db = _fold_partials(part, dev, st)
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], profile_kind or "two_hop"))
+    with _timed(cfg, profile_kind or "two_hop"):
+        ZT = torch.empty((max(n_zt, 1), H), dtype=torch.float32, device=dev)
+        _lib.call("fitgnn_two_hop_rows_f32", side.rowptr, ix["zcol"], side.val, Xc, Xc.stride(0), n_sel, ix["zt_rows"], n_zt, prev, H, epi_v,
+                  float(link.p), seed_v, link.mask, ZT, ZT.stride(0), st)
+        Y = torch.empty((g.n, H), dtype=torch.float32, device=dev)
+        quiet = cfg if cfg.profile is None else cfg.replace(profile=None)
+        if side.small_tiles.shape[0]:
+            spmm_raw(side.rowptr, side.col, side.val, side.small_tiles, ZT, g.n, window_rows=g.window_rows, out=Y, cfg=quiet, xrow=ix["zrow"])
+        n_blocks = int(side.blocks.shape[0])
+        # one partial row of column sums per block + one for the rows outside the blocks (their dZ sits in the table).  No fill: the
+        # kernel writes the row of every record, a padding record's as zeros (FITGNN_POISON=1 hands out NaN, which is how the tests check it)
+        part = _scratch((n_blocks + 1, H), dev) if link.want_db else None
+        _lib.call("fitgnn_spmm_two_hop_blocks_f32", side.rowptr, side.col, side.val, ZT, ZT.stride(0), Y, Y.stride(0), g.n, H, side.blocks, n_blocks,
+                  side.long_rows, ix["zrow"], ix["zcol"], prev, Xc, Xc.stride(0), n_sel, ix["row_p"], ix["row_w"], epi_v, float(link.p), seed_v,
+                  link.mask, part, st)
+        db = None
+        if link.want_db:
+            if ix["tile_zt"].numel():
+                torch.sum(ZT.index_select(0, ix["tile_zt"]), 0, out=part[n_blocks])
+            else:
+                part[n_blocks].zero_()
+            db = _fold_partials(part, dev, st)
     return Y, db
 
 
 def _fold_partials(part, dev, st):
     """Column sums of a [n x H] matrix of partial rows in a fixed order (fitgnn_colsum_partials_f32; many rows are folded in runs first)."""
-    L = _lib.lib()
     n_part, H = int(part.shape[0]), int(part.shape[1])
     if n_part > 8192:
+        # colsum_partials' grid is H / 16 workgroups (0.4 ms for 166 000 rows): fold contiguous runs of rows first (torch's reduction:
+        # deterministic for a fixed shape), then the fixed-order kernel
         G = 1024
         per = n_part // G
         head = part[: G * per].view(G, per, H).sum(1)
         part = torch.cat([head, part[G * per:]]) if n_part > G * per else head
         n_part = int(part.shape[0])
     db = torch.empty(H, dtype=torch.float32, device=dev)
-    _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part.contiguous()), n_part, H, _lib.dptr(db), st), "fitgnn_colsum_partials_f32")
+    _lib.call("fitgnn_colsum_partials_f32", part.contiguous(), n_part, H, db, st)
     return db
 
 
@@ -1071,7 +979,6 @@ def spmm_graph_dz(g, X, prev, epilogue, p=0.0, seed=0, mask=None, want_db=True, 
     side = g.t if transposed else g.f
     Xc, prev = _f32c(X), _f32c(prev)
     _lib.require_cuda(Xc, prev, mask, xrow)
-    L = _lib.lib()
     H = Xc.shape[1]
     if xrow is not None and zero_from >= 0 and cfg.compact_rows_kernel and H % 4 == 0 and g.n >= cfg.rows_kernel_min_rows:
         return _spmm_rows_compact(g, side, Xc, xrow, zero_from, cfg, profile_kind, dz=(prev, epilogue, p, seed, mask, want_db))
@@ -1091,42 +998,19 @@ def spmm_graph_dz(g, X, prev, epilogue, p=0.0, seed=0, mask=None, want_db=True, 
     # row is written.
     part = _scratch((n_tiles + n_blocks, H), dev) if want_db else None
     st = _lib.stream_ptr(dev)
-    ev = None
-    if cfg.profile is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    if n_tiles:
-        _lib.check(L.fitgnn_spmm_csr_dz_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(Xc), Xc.stride(0),
-                                            _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(tiles), n_tiles,
-                                            _lib.dptr(None if split else side.lcol), _lib.dptr(None if split else side.win_cols),
-                                            _lib.dptr(xrow), int(zero_from), int(g.window_rows), _lib.dptr(prev), epi_v, float(p), seed_v,
-                                            _lib.dptr(mask), _lib.dptr(part), st), "fitgnn_spmm_csr_dz_f32")
-    if n_blocks:
-        xcol = None
-        if xrow is not None:
-            xcol = _entry_rows(side, xrow)
-        _lib.check(L.fitgnn_spmm_csr_blocks_dz_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(Xc), Xc.stride(0),
-                                                   _lib.dptr(Y), Y.stride(0), g.n, H, _lib.dptr(side.blocks), n_blocks, _lib.dptr(side.long_rows),
-                                                   _lib.dptr(xrow), _lib.dptr(xcol), int(zero_from), _lib.dptr(prev), epi_v, float(p), seed_v, _lib.dptr(mask),
-                                                   _lib.dptr(None if part is None else part[n_tiles:]), st), "fitgnn_spmm_csr_blocks_dz_f32")
-    if ev is not None:
-        ev[1].record()
-        cfg.profile.append((ev[0], ev[1], profile_kind or "dz"))
-    db = None
-    if want_db:
-        n_part = n_tiles + n_blocks
-        if n_part > 8192:
-            # one partial row per star: 166 000 at S-products.  colsum_partials' grid is H / 16 workgroups (0.4 ms for them); fold
-            # contiguous runs of rows first (torch's reduction: deterministic for a fixed shape), then the fixed-order kernel
-            G = 1024
-            per = n_part // G
-            head = part[: G * per].view(G, per, H).sum(1)
-            part2 = torch.cat([head, part[G * per:]]) if n_part > G * per else head
-            db = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part2), int(part2.shape[0]), H, _lib.dptr(db), st), "fitgnn_colsum_partials_f32")
-        else:
-            db = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part), n_part, H, _lib.dptr(db), st), "fitgnn_colsum_partials_f32")
+    with _timed(cfg, profile_kind or "dz"):
+        if n_tiles:
+            _lib.call("fitgnn_spmm_csr_dz_f32", side.rowptr, side.col, side.val, Xc, Xc.stride(0), Y, Y.stride(0), g.n, H, tiles, n_tiles,
+                      None if split else side.lcol, None if split else side.win_cols, xrow, int(zero_from), int(g.window_rows), prev, epi_v, float(p),
+                      seed_v, mask, part, st)
+        if n_blocks:
+            xcol = None
+            if xrow is not None:
+                xcol = _entry_rows(side, xrow)
+            _lib.call("fitgnn_spmm_csr_blocks_dz_f32", side.rowptr, side.col, side.val, Xc, Xc.stride(0), Y, Y.stride(0), g.n, H, side.blocks, n_blocks,
+                      side.long_rows, xrow, xcol, int(zero_from), prev, epi_v, float(p), seed_v, mask, None if part is None else part[n_tiles:], st)
+    # one partial row per star: 166 000 at S-products, which _fold_partials folds in runs first
+    db = _fold_partials(part, dev, st) if want_db else None
     return Y, db
 
 
@@ -1144,10 +1028,8 @@ def epilogue_bwd_head_raw(dy, Wl, out, epilogue, p=0.0, seed=0, mask=None, want_
     dWl = torch.empty((C, H), dtype=torch.float32, device=out.device) if want_dWl else None
     wb = int(L.fitgnn_epilogue_bwd_head_workspace_bytes(n, H, C))
     work = torch.empty(max(wb, 4), dtype=torch.uint8, device=out.device)
-    rc = L.fitgnn_epilogue_bwd_head_f32(_lib.dptr(dy), _lib.dptr(Wl), C, _lib.dptr(out), _lib.dptr(dZ), n, H, epilogue, float(p),
-                                        seed, _lib.dptr(mask), _lib.dptr(db), _lib.dptr(dWl),
-                                        _lib.dptr(work), wb, _lib.stream_ptr(out.device))
-    _lib.check(rc, "fitgnn_epilogue_bwd_head_f32")
+    _lib.call("fitgnn_epilogue_bwd_head_f32", dy, Wl, C, out, dZ, n, H, epilogue, float(p), seed, mask, db, dWl, work, wb,
+              _lib.stream_ptr(out.device))
     return dZ, db, dWl
 
 
@@ -1176,10 +1058,8 @@ def epilogue_bwd_head_rows_raw(dy, Wl, out, rows, epilogue, p=0.0, seed=0, mask=
     dWl = (dWl_out if dWl_out is not None else torch.empty((C, H), dtype=torch.float32, device=out.device)) if want_dWl else None
     wb = int(L.fitgnn_epilogue_bwd_head_workspace_bytes(n_sel, H, C))
     work = torch.empty(max(wb, 4), dtype=torch.uint8, device=out.device)
-    rc = L.fitgnn_epilogue_bwd_head_rows_f32(_lib.dptr(dy), _lib.dptr(Wl), C, _lib.dptr(out), _lib.dptr(rows), n_sel, 1 if inputs_compact else 0,
-                                             _lib.dptr(dZc), H, epilogue, float(p), seed, _lib.dptr(mask), _lib.dptr(db), _lib.dptr(dWl),
-                                             _lib.dptr(work), wb, _lib.stream_ptr(out.device))
-    _lib.check(rc, "fitgnn_epilogue_bwd_head_rows_f32")
+    _lib.call("fitgnn_epilogue_bwd_head_rows_f32", dy, Wl, C, out, rows, n_sel, 1 if inputs_compact else 0, dZc, H, epilogue, float(p), seed, mask,
+              db, dWl, work, wb, _lib.stream_ptr(out.device))
     return dZc, db, dWl
 
 
@@ -1188,9 +1068,8 @@ def epilogue_fwd_rows_(z, rows, bias, epilogue, p=0.0, seed=0, mask=None):
     _lib.require_cuda(z, rows, bias, mask)
     seed, epilogue = _seed_arg(seed, epilogue)
     rows = (rows if rows.dtype == torch.int64 else rows.long()).contiguous()
-    _lib.check(_lib.lib().fitgnn_epilogue_fwd_rows_f32(_lib.dptr(z), z.stride(0), _lib.dptr(rows), z.shape[0], z.shape[1],
-                                                       _lib.dptr(None if bias is None else _f32c(bias)), epilogue, float(p), seed,
-                                                       _lib.dptr(mask), _lib.stream_ptr(z.device)), "fitgnn_epilogue_fwd_rows_f32")
+    _lib.call("fitgnn_epilogue_fwd_rows_f32", z, z.stride(0), rows, z.shape[0], z.shape[1], None if bias is None else _f32c(bias), epilogue, float(p),
+              seed, mask, _lib.stream_ptr(z.device))
     return z
 
 
@@ -1222,9 +1101,8 @@ def head_rows(out, rows, Wl, bl, n_total=None):
     Wl = _f32c(Wl)
     y = torch.zeros((R, C), dtype=torch.float32, device=out.device)
     rows = rows if rows.dtype == torch.int64 else rows.long()
-    _lib.check(_lib.lib().fitgnn_head_rows_f32(_lib.dptr(out), out.stride(0), _lib.dptr(rows.contiguous()), rows.numel(), _lib.dptr(Wl),
-                                               _lib.dptr(None if bl is None else _f32c(bl)), C, H, _lib.dptr(y), C, 1 if compact else 0,
-                                               _lib.stream_ptr(out.device)), "fitgnn_head_rows_f32")
+    _lib.call("fitgnn_head_rows_f32", out, out.stride(0), rows.contiguous(), rows.numel(), Wl, None if bl is None else _f32c(bl), C, H, y, C,
+              1 if compact else 0, _lib.stream_ptr(out.device))
     return y
 
 
@@ -1250,24 +1128,21 @@ def _f32_on_gpu(params):
 def gcn_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
     """G [Q, H]: row i = the layer-1 aggregation of union row rows[i] over layer-0 rows made from T = X W0^T on the fly
     (fitgnn_gcn_query_gather_f32).  rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
-    _lib.require_cuda(rowptr, col, val, T, rows, xrow, b0)
+    _lib.require_cuda(T)   # T.device places the output and names the stream; the call checks the others
     Q, H = int(rows.numel()), int(T.shape[1])
     G = out if out is not None else torch.empty((Q, H), dtype=torch.float32, device=T.device)
-    _lib.check(_lib.lib().fitgnn_gcn_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                      _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
-                                                      _lib.stream_ptr(T.device)), "fitgnn_gcn_query_gather_f32")
+    _lib.call("fitgnn_gcn_query_gather_f32", rowptr, col, val, T, T.stride(0), xrow, b0, rows, Q, H, G, G.stride(0), _lib.stream_ptr(T.device))
     return G
 
 
 def gcn_query_tail(G, W1, b1, Wl, bl, log_softmax=False, out=None):
     """[Q, C] = Wl ELU(W1 G^T + b1) + bl per row, log-softmax on request (fitgnn_gcn_query_tail_f32).  W1 [H2, H], Wl [C, H2] contiguous."""
-    _lib.require_cuda(G, W1, b1, Wl, bl)
+    _lib.require_cuda(G)   # G.device places the output and names the stream; the call checks the others
     Q, H = int(G.shape[0]), int(G.shape[1])
     H2, C = int(W1.shape[0]), int(Wl.shape[0])
     y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
-    _lib.check(_lib.lib().fitgnn_gcn_query_tail_f32(_lib.dptr(G), G.stride(0), Q, _lib.dptr(W1), _lib.dptr(b1), _lib.dptr(Wl), _lib.dptr(bl),
-                                                    H, H2, C, _lib.dptr(y), y.stride(0), 1 if log_softmax else 0,
-                                                    _lib.stream_ptr(G.device)), "fitgnn_gcn_query_tail_f32")
+    _lib.call("fitgnn_gcn_query_tail_f32", G, G.stride(0), Q, W1, b1, Wl, bl, H, H2, C, y, y.stride(0), 1 if log_softmax else 0,
+              _lib.stream_ptr(G.device))
     return y
 
 
@@ -1299,29 +1174,25 @@ def gcn_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=No
     T = X W0^T (fitgnn_gcn_graph_query_hops_f32).  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled
     rows, graph i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int).  The caller checks that
     prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
-    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)
+    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)   # all of them: P == 0 returns before the call
     Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1])
     G = out if out is not None else torch.empty((P, H), dtype=torch.float32, device=T.device)
     if P == 0:
         return G
-    _lib.check(_lib.lib().fitgnn_gcn_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                          _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q, H,
-                                                          int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
-               "fitgnn_gcn_graph_query_hops_f32")
+    _lib.call("fitgnn_gcn_graph_query_hops_f32", rowptr, col, val, T, T.stride(0), xrow, b0, seg, prow, pptr, Q, H, int(max_rows), G, G.stride(0),
+              _lib.stream_ptr(T.device))
     return G
 
 
 def gcn_graph_query_tail(G, pptr, W1, b1, Wl, bl, pool="max", softmax=False, out=None):
     """[Q, C] = Wl pool_i(ELU(W1 G[r] + b1): r in pptr[i] .. pptr[i + 1]) + bl per graph, pool "max" or "mean", a softmax on request
     (fitgnn_gcn_graph_query_tail_f32).  W1 [H2, H], Wl [C, H2] contiguous; pptr int64 [Q + 1]."""
-    _lib.require_cuda(G, pptr, W1, b1, Wl, bl)
+    _lib.require_cuda(G)   # G.device places the output and names the stream; the call checks the others
     Q, H = int(pptr.numel()) - 1, int(G.shape[1])
     H2, C = int(W1.shape[0]), int(Wl.shape[0])
     y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
-    _lib.check(_lib.lib().fitgnn_gcn_graph_query_tail_f32(_lib.dptr(G), G.stride(0), _lib.dptr(pptr), Q, _lib.dptr(W1), _lib.dptr(b1),
-                                                          _lib.dptr(Wl), _lib.dptr(bl), H, H2, C, {"max": 0, "mean": 1}[pool],
-                                                          1 if softmax else 0, _lib.dptr(y), y.stride(0), _lib.stream_ptr(G.device)),
-               "fitgnn_gcn_graph_query_tail_f32")
+    _lib.call("fitgnn_gcn_graph_query_tail_f32", G, G.stride(0), pptr, Q, W1, b1, Wl, bl, H, H2, C, {"max": 0, "mean": 1}[pool], 1 if softmax else 0,
+              y, y.stride(0), _lib.stream_ptr(G.device))
     return y
 
 
@@ -1341,13 +1212,11 @@ def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=No
     """G [Q, H]: row i = the layer-1 attention aggregation (before its Linear) of union row rows[i] over layer-0 GAT rows made from
     T = X W0^T on the fly (fitgnn_gat_query_gather_f32).  a_src0 / a_dst0: the layer-0 score dots per TABLE row; u_src / u_dst [H]:
     W1^T att_src1, W1^T att_dst1.  rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
-    _lib.require_cuda(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow, b0)
+    _lib.require_cuda(T)   # T.device places the output and names the stream; the call checks the others
     Q, H = int(rows.numel()), int(T.shape[1])
     G = out if out is not None else torch.empty((Q, H), dtype=torch.float32, device=T.device)
-    _lib.check(_lib.lib().fitgnn_gat_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(T), T.stride(0), _lib.dptr(xrow),
-                                                      _lib.dptr(a_src0), _lib.dptr(a_dst0), _lib.dptr(b0), float(slope0), _lib.dptr(u_src),
-                                                      _lib.dptr(u_dst), float(slope1), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
-                                                      _lib.stream_ptr(T.device)), "fitgnn_gat_query_gather_f32")
+    _lib.call("fitgnn_gat_query_gather_f32", rowptr, col, T, T.stride(0), xrow, a_src0, a_dst0, b0, float(slope0), u_src, u_dst, float(slope1), rows,
+              Q, H, G, G.stride(0), _lib.stream_ptr(T.device))
     return G
 
 
@@ -1384,16 +1253,13 @@ def gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow
     as gat_query_gather's.  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled rows, graph i's at
     pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int, at most gat_graph_query_max_rows(H)).  The
     caller checks that prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
-    _lib.require_cuda(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, xrow, b0)
+    _lib.require_cuda(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, xrow, b0)   # all: P == 0 returns before the call
     Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1])
     G = out if out is not None else torch.empty((P, H), dtype=torch.float32, device=T.device)
     if P == 0:
         return G
-    _lib.check(_lib.lib().fitgnn_gat_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(T), T.stride(0), _lib.dptr(xrow),
-                                                          _lib.dptr(a_src0), _lib.dptr(a_dst0), _lib.dptr(b0), float(slope0),
-                                                          _lib.dptr(u_src), _lib.dptr(u_dst), float(slope1), _lib.dptr(seg), _lib.dptr(prow),
-                                                          _lib.dptr(pptr), Q, H, int(max_rows), _lib.dptr(G), G.stride(0),
-                                                          _lib.stream_ptr(T.device)), "fitgnn_gat_graph_query_hops_f32")
+    _lib.call("fitgnn_gat_graph_query_hops_f32", rowptr, col, T, T.stride(0), xrow, a_src0, a_dst0, b0, float(slope0), u_src, u_dst, float(slope1),
+              seg, prow, pptr, Q, H, int(max_rows), G, G.stride(0), _lib.stream_ptr(T.device))
     return G
 
 
@@ -1413,12 +1279,10 @@ def sage_query_gather(rowptr, col, val, T, rows, xrow=None, b0=None, out=None):
     """G [Q, 2H]: row i = [g_q | h_q] for union row q = rows[i] -- the layer-1 mean aggregation over layer-0 SAGE rows and q's own
     layer-0 row, both made on the fly from T = X [W_l0 ; W_r0]^T [n_table, 2H] (fitgnn_sage_query_gather_f32) over the mean CSR.
     rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
-    _lib.require_cuda(rowptr, col, val, T, rows, xrow, b0)
+    _lib.require_cuda(T)   # T.device places the output and names the stream; the call checks the others
     Q, H = int(rows.numel()), int(T.shape[1]) // 2
     G = out if out is not None else torch.empty((Q, 2 * H), dtype=torch.float32, device=T.device)
-    _lib.check(_lib.lib().fitgnn_sage_query_gather_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                       _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(rows), Q, H, _lib.dptr(G), G.stride(0),
-                                                       _lib.stream_ptr(T.device)), "fitgnn_sage_query_gather_f32")
+    _lib.call("fitgnn_sage_query_gather_f32", rowptr, col, val, T, T.stride(0), xrow, b0, rows, Q, H, G, G.stride(0), _lib.stream_ptr(T.device))
     return G
 
 
@@ -1452,15 +1316,13 @@ def sage_graph_query_hops(rowptr, col, val, T, seg, prow, pptr, max_rows, xrow=N
     (fitgnn_sage_graph_query_hops_f32).  seg int64 [Q, 2]: the row range of every queried graph; prow int64 [P]: the pooled rows, graph
     i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the largest range (host int, at most sage_graph_query_max_rows(H)).
     The caller checks that prow and the CSR's columns stay inside their graph's range: the kernel cannot."""
-    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)
+    _lib.require_cuda(rowptr, col, val, T, seg, prow, pptr, xrow, b0)   # all of them: P == 0 returns before the call
     Q, P, H = int(seg.shape[0]), int(prow.numel()), int(T.shape[1]) // 2
     G = out if out is not None else torch.empty((P, 2 * H), dtype=torch.float32, device=T.device)
     if P == 0:
         return G
-    _lib.check(_lib.lib().fitgnn_sage_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                           _lib.dptr(xrow), _lib.dptr(b0), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q,
-                                                           H, int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
-               "fitgnn_sage_graph_query_hops_f32")
+    _lib.call("fitgnn_sage_graph_query_hops_f32", rowptr, col, val, T, T.stride(0), xrow, b0, seg, prow, pptr, Q, H, int(max_rows), G, G.stride(0),
+              _lib.stream_ptr(T.device))
     return G
 
 
@@ -1481,26 +1343,23 @@ def gin_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow=None, b
     h_r = ReLU(W0b ReLU(sum_k val[k] T[t(col[k])] + (1 + eps0) T[t(r)] + b0a) + b0b) made on the fly from T = X W0a^T [n_table, Ha]
     over the sum CSR (fitgnn_gin_query_hops_f32).  eps0 / eps1: float32 tensors of one element ON THE DEVICE, read by the kernel.
     rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
-    _lib.require_cuda(rowptr, col, val, T, eps0, W0b, b0b, eps1, rows, xrow, b0a)
+    _lib.require_cuda(T)   # T.device places the output and names the stream; the call checks the others
     Q, Ha, Hb = int(rows.numel()), int(T.shape[1]), int(W0b.shape[0])
     G = out if out is not None else torch.empty((Q, Hb), dtype=torch.float32, device=T.device)
-    _lib.check(_lib.lib().fitgnn_gin_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                    _lib.dptr(xrow), _lib.dptr(b0a), _lib.dptr(eps0), _lib.dptr(W0b), _lib.dptr(b0b),
-                                                    _lib.dptr(eps1), _lib.dptr(rows), Q, Ha, Hb, _lib.dptr(G), G.stride(0),
-                                                    _lib.stream_ptr(T.device)), "fitgnn_gin_query_hops_f32")
+    _lib.call("fitgnn_gin_query_hops_f32", rowptr, col, val, T, T.stride(0), xrow, b0a, eps0, W0b, b0b, eps1, rows, Q, Ha, Hb, G, G.stride(0),
+              _lib.stream_ptr(T.device))
     return G
 
 
 def gin_query_tail(G, W1a, b1a, W1b, b1b, Wl, bl, log_softmax=False, out=None):
     """[Q, C] = Wl ReLU(W1b ReLU(W1a G^T + b1a) + b1b) + bl per row, log-softmax on request (fitgnn_gin_query_tail_f32).
     W1a [H2a, K], W1b [H2b, H2a], Wl [C, H2b] contiguous."""
-    _lib.require_cuda(G, W1a, b1a, W1b, b1b, Wl, bl)
+    _lib.require_cuda(G)   # G.device places the output and names the stream; the call checks the others
     Q, K = int(G.shape[0]), int(G.shape[1])
     H2a, H2b, C = int(W1a.shape[0]), int(W1b.shape[0]), int(Wl.shape[0])
     y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
-    _lib.check(_lib.lib().fitgnn_gin_query_tail_f32(_lib.dptr(G), G.stride(0), Q, _lib.dptr(W1a), _lib.dptr(b1a), _lib.dptr(W1b),
-                                                    _lib.dptr(b1b), _lib.dptr(Wl), _lib.dptr(bl), K, H2a, H2b, C, _lib.dptr(y), y.stride(0),
-                                                    1 if log_softmax else 0, _lib.stream_ptr(G.device)), "fitgnn_gin_query_tail_f32")
+    _lib.call("fitgnn_gin_query_tail_f32", G, G.stride(0), Q, W1a, b1a, W1b, b1b, Wl, bl, K, H2a, H2b, C, y, y.stride(0), 1 if log_softmax else 0,
+              _lib.stream_ptr(G.device))
     return y
 
 
@@ -1539,30 +1398,25 @@ def gin_graph_query_hops(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, p
     of every queried graph; prow int64 [P]: the pooled rows, graph i's at pptr[i] .. pptr[i + 1] (pptr int64 [Q + 1]); max_rows: the
     largest range (host int, at most gin_graph_query_max_rows(Ha, Hb)).  The caller checks that prow and the CSR's columns stay inside
     their graph's range: the kernel cannot."""
-    _lib.require_cuda(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, xrow, b0a)
+    _lib.require_cuda(rowptr, col, val, T, eps0, W0b, b0b, eps1, seg, prow, pptr, xrow, b0a)   # all: P == 0 returns before the call
     Q, P, Ha, Hb = int(seg.shape[0]), int(prow.numel()), int(T.shape[1]), int(W0b.shape[0])
     G = out if out is not None else torch.empty((P, Hb), dtype=torch.float32, device=T.device)
     if P == 0:
         return G
-    _lib.check(_lib.lib().fitgnn_gin_graph_query_hops_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), _lib.dptr(T), T.stride(0),
-                                                          _lib.dptr(xrow), _lib.dptr(b0a), _lib.dptr(eps0), _lib.dptr(W0b), _lib.dptr(b0b),
-                                                          _lib.dptr(eps1), _lib.dptr(seg), _lib.dptr(prow), _lib.dptr(pptr), Q, Ha, Hb,
-                                                          int(max_rows), _lib.dptr(G), G.stride(0), _lib.stream_ptr(T.device)),
-               "fitgnn_gin_graph_query_hops_f32")
+    _lib.call("fitgnn_gin_graph_query_hops_f32", rowptr, col, val, T, T.stride(0), xrow, b0a, eps0, W0b, b0b, eps1, seg, prow, pptr, Q, Ha, Hb,
+              int(max_rows), G, G.stride(0), _lib.stream_ptr(T.device))
     return G
 
 
 def gin_graph_query_tail(G, pptr, W1a, b1a, W1b, b1b, Wl, bl, pool="max", softmax=False, out=None):
     """[Q, C] = Wl pool_i(ReLU(W1b ReLU(W1a G[r] + b1a) + b1b): r in pptr[i] .. pptr[i + 1]) + bl per graph, pool "max" or "mean", a
     softmax on request (fitgnn_gin_graph_query_tail_f32).  W1a [H2a, K], W1b [H2b, H2a], Wl [C, H2b] contiguous; pptr int64 [Q + 1]."""
-    _lib.require_cuda(G, pptr, W1a, b1a, W1b, b1b, Wl, bl)
+    _lib.require_cuda(G)   # G.device places the output and names the stream; the call checks the others
     Q, K = int(pptr.numel()) - 1, int(G.shape[1])
     H2a, H2b, C = int(W1a.shape[0]), int(W1b.shape[0]), int(Wl.shape[0])
     y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
-    _lib.check(_lib.lib().fitgnn_gin_graph_query_tail_f32(_lib.dptr(G), G.stride(0), _lib.dptr(pptr), Q, _lib.dptr(W1a), _lib.dptr(b1a),
-                                                          _lib.dptr(W1b), _lib.dptr(b1b), _lib.dptr(Wl), _lib.dptr(bl), K, H2a, H2b, C,
-                                                          {"max": 0, "mean": 1}[pool], 1 if softmax else 0, _lib.dptr(y), y.stride(0),
-                                                          _lib.stream_ptr(G.device)), "fitgnn_gin_graph_query_tail_f32")
+    _lib.call("fitgnn_gin_graph_query_tail_f32", G, G.stride(0), pptr, Q, W1a, b1a, W1b, b1b, Wl, bl, K, H2a, H2b, C, {"max": 0, "mean": 1}[pool],
+              1 if softmax else 0, y, y.stride(0), _lib.stream_ptr(G.device))
     return y
 
 
@@ -1590,8 +1444,7 @@ def segment_sum(seg_off, members, X, n_seg):
     X = _f32c(X)
     F_ = X.shape[1]
     out = torch.empty((n_seg, F_), dtype=torch.float32, device=X.device)
-    _lib.check(_lib.lib().fitgnn_segment_sum_f32(_lib.dptr(seg_off), _lib.dptr(members), n_seg, _lib.dptr(X), F_, F_, _lib.dptr(out),
-                                                 F_, _lib.stream_ptr(X.device)), "fitgnn_segment_sum_f32")
+    _lib.call("fitgnn_segment_sum_f32", seg_off, members, n_seg, X, F_, F_, out, F_, _lib.stream_ptr(X.device))
     return out
 
 
@@ -1654,8 +1507,7 @@ class SegmentMeanPool(torch.autograd.Function):
         n, F_ = ctx.shape
         g = _f32c(g)
         dx = torch.empty((n, F_), dtype=torch.float32, device=g.device)
-        _lib.check(_lib.lib().fitgnn_segment_expand_f32(_lib.dptr(g), _lib.dptr(pi.seg_of_row), _lib.dptr(pi.inv_cnt), n, F_, _lib.dptr(dx),
-                                                        _lib.stream_ptr(g.device)), "fitgnn_segment_expand_f32")
+        _lib.call("fitgnn_segment_expand_f32", g, pi.seg_of_row, pi.inv_cnt, n, F_, dx, _lib.stream_ptr(g.device))
         return dx, None
 
 
@@ -1671,8 +1523,7 @@ class SegmentMaxPool(torch.autograd.Function):
         n, F_ = x.shape
         out = torch.empty((pi.n_seg, F_), dtype=torch.float32, device=x.device)
         arg = torch.empty((pi.n_seg, F_), dtype=torch.int32, device=x.device)
-        _lib.check(_lib.lib().fitgnn_segment_max_f32(_lib.dptr(pi.seg_off), _lib.dptr(pi.members), pi.n_seg, _lib.dptr(x), x.stride(0), F_,
-                                                     _lib.dptr(out), _lib.dptr(arg), _lib.stream_ptr(x.device)), "fitgnn_segment_max_f32")
+        _lib.call("fitgnn_segment_max_f32", pi.seg_off, pi.members, pi.n_seg, x, x.stride(0), F_, out, arg, _lib.stream_ptr(x.device))
         ctx.save_for_backward(arg)
         ctx.shape = x.shape
         return out
@@ -1683,8 +1534,7 @@ class SegmentMaxPool(torch.autograd.Function):
         n, F_ = ctx.shape
         g = _f32c(g)
         dx = torch.zeros((n, F_), dtype=torch.float32, device=g.device)
-        _lib.check(_lib.lib().fitgnn_segment_max_bwd_f32(_lib.dptr(g), _lib.dptr(arg), int(arg.shape[0]), F_, _lib.dptr(dx), F_,
-                                                         _lib.stream_ptr(g.device)), "fitgnn_segment_max_bwd_f32")
+        _lib.call("fitgnn_segment_max_bwd_f32", g, arg, int(arg.shape[0]), F_, dx, F_, _lib.stream_ptr(g.device))
         return dx, None
 
 
@@ -1701,15 +1551,13 @@ class MeanPoolHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, pi, Wl, bl, cfg):
-        L = _lib.lib()
         x, W = _f32c(x), _f32c(Wl)
         n, F_ = x.shape
         C = int(W.shape[0])
         pooled = torch.empty((pi.n_seg, F_), dtype=torch.float32, device=x.device)
         y = torch.empty((pi.n_seg, C), dtype=torch.float32, device=x.device)
-        _lib.check(L.fitgnn_pool_head_f32(_lib.dptr(pi.seg_off), _lib.dptr(pi.members), pi.n_seg, _lib.dptr(x), x.stride(0), F_,
-                                          _lib.dptr(pi.inv_cnt), _lib.dptr(W), _lib.dptr(bl), C, _lib.dptr(pooled), _lib.dptr(y),
-                                          _lib.stream_ptr(x.device)), "fitgnn_pool_head_f32")
+        _lib.call("fitgnn_pool_head_f32", pi.seg_off, pi.members, pi.n_seg, x, x.stride(0), F_, pi.inv_cnt, W, bl, C, pooled, y,
+                  _lib.stream_ptr(x.device))
         ctx.save_for_backward(pooled, W)
         ctx.pi, ctx.shape, ctx.cfg, ctx.has_bl = pi, (n, F_), cfg, bl is not None
         ctx.ptrs = _addresses(Wl, bl)
@@ -1718,7 +1566,6 @@ class MeanPoolHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         pooled, W = ctx.saved_tensors
-        L = _lib.lib()
         pi, (n, F_), cfg = ctx.pi, ctx.shape, ctx.cfg
         C = int(W.shape[0])
         dy = _f32c(dy)
@@ -1727,9 +1574,8 @@ class MeanPoolHead(torch.autograd.Function):
         sink, (pW, pb) = _GradSink(cfg.grad_sink), ctx.ptrs
         dW = sink.buffer(pW, (C, F_), dev) if ctx.needs_input_grad[2] else None
         db = sink.buffer(pb, C, dev) if (ctx.has_bl and ctx.needs_input_grad[3]) else None
-        _lib.check(L.fitgnn_pool_head_bwd_f32(_lib.dptr(dy), _lib.dptr(W), C, _lib.dptr(pooled), _lib.dptr(pi.seg_of_row), _lib.dptr(pi.inv_cnt),
-                                              n if dx is not None else 0, pi.n_seg, F_, _lib.dptr(dx), _lib.dptr(dW), _lib.dptr(db),
-                                              _lib.stream_ptr(dev)), "fitgnn_pool_head_bwd_f32")
+        _lib.call("fitgnn_pool_head_bwd_f32", dy, W, C, pooled, pi.seg_of_row, pi.inv_cnt, n if dx is not None else 0, pi.n_seg, F_, dx, dW, db,
+                  _lib.stream_ptr(dev))
         return dx, None, sink.result(dW), sink.result(db), None
 
 
@@ -1776,19 +1622,10 @@ def layer_backward(g, out, epi, p, seed, mask, want_db, dOut=None, dy=None, Wl=N
             dy, Wl = _f32c(dy), _f32c(Wl)
         else:
             dOut = _f32c(dOut)
-        ev = None
-        if cfg.profile_fused is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
         seed_v, epi_v = _seed_arg(seed, epi)
-        rc = L.fitgnn_spmm_epilogue_bwd_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(side.tiles), nt,
-                                            g.window_rows, _lib.dptr(dOut), _lib.dptr(dy), _lib.dptr(Wl), C, _lib.dptr(out),
-                                            _lib.dptr(dH), n, H, epi_v, float(p), seed_v, _lib.dptr(mask),
-                                            _lib.dptr(db), _lib.dptr(dWl), _lib.dptr(work), wb, _lib.stream_ptr(dev))
-        if ev is not None:
-            ev[1].record()
-            cfg.profile_fused.append(ev)
-        _lib.check(rc, "fitgnn_spmm_epilogue_bwd_f32")
+        with _timed(sink=cfg.profile_fused):
+            _lib.call("fitgnn_spmm_epilogue_bwd_f32", side.rowptr, side.col, side.val, side.tiles, nt, g.window_rows, dOut, dy, Wl, C, out, dH, n,
+                      H, epi_v, float(p), seed_v, mask, db, dWl, work, wb, _lib.stream_ptr(dev))
         return dH, db, dWl
     if head and loss_rows is not None and cfg.compact_head_backward and H % 4 == 0 and loss_rows.numel() > 0:
         inside = want_dWl and bool(L.fitgnn_epilogue_bwd_head_supported(H, C, 1))
@@ -1983,17 +1820,14 @@ class FusedGCNLayerAggregatedInput(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, AX, W, b, p, training, seed, mask, link_out, cfg):
-        L = _lib.lib()
         n, K = AX.shape
         H = int(W.shape[0])
         Wc = _f32c(W)
         ep = _Epilogue(b is not None, p, training, seed, mask)
         out = torch.empty((n, H), dtype=torch.float32, device=AX.device)
         seed_v, epi_v = _seed_arg(ep.seed, ep.fwd)
-        rc = L.fitgnn_dense_narrow_k_f32(_lib.dptr(AX), AX.stride(0), _lib.dptr(Wc), Wc.stride(0), n, K, H, _lib.dptr(b), epi_v,
-                                         float(ep.p), seed_v, _lib.dptr(ep.mask), _lib.dptr(out), out.stride(0),
-                                         _lib.stream_ptr(AX.device))
-        _lib.check(rc, "fitgnn_dense_narrow_k_f32")
+        _lib.call("fitgnn_dense_narrow_k_f32", AX, AX.stride(0), Wc, Wc.stride(0), n, K, H, b, epi_v, float(ep.p), seed_v, ep.mask, out,
+                  out.stride(0), _lib.stream_ptr(AX.device))
         ctx.save_for_backward(AX, out, ep.mask)
         ctx.ep, ctx.has_bias, ctx.cfg, ctx.link_out, ctx.H = ep, b is not None, cfg, link_out, H
         ctx.ptrs = _addresses(W, b)
@@ -2019,10 +1853,8 @@ class FusedGCNLayerAggregatedInput(torch.autograd.Function):
         db = sink.buffer(pb if want_db else None, H, dOut.device)
         wb = int(L.fitgnn_narrow_atb_workspace_bytes(n, K, H))
         work = torch.empty(wb // 4, dtype=torch.float32, device=dOut.device)
-        rc = L.fitgnn_narrow_atb_f32(_lib.dptr(dOut), dOut.stride(0), _lib.dptr(prev), epi_v, float(ep.p), seed_v,
-                                     _lib.dptr(mask), _lib.dptr(AX), AX.stride(0), n, K, H, _lib.dptr(dW), _lib.dptr(db), _lib.dptr(work), wb,
-                                     _lib.stream_ptr(dOut.device))
-        _lib.check(rc, "fitgnn_narrow_atb_f32")
+        _lib.call("fitgnn_narrow_atb_f32", dOut, dOut.stride(0), prev, epi_v, float(ep.p), seed_v, mask, AX, AX.stride(0), n, K, H, dW, db, work, wb,
+                  _lib.stream_ptr(dOut.device))
         return None, (sink.result(dW) if want_dW else None), (sink.result(db) if want_db else None), None, None, None, None, None, None
 
 
@@ -2320,7 +2152,6 @@ class GATAggregate(torch.autograd.Function):
         ridx (RowIndex, optional): h is a de-duplicated TABLE [N0, C] and row r of the graph is a copy of table row ridx.index[r] (the
         first layer of a union batch: h = x W^T and the score dots run on the N0 original nodes; the aggregation, the SDDMM and the
         softmax read the table through the row indirection; the backward sums each node's copies before the weight-side products)."""
-        L = _lib.lib()
         h = _f32c(h)
         nh, C = h.shape
         n = g.n
@@ -2330,14 +2161,12 @@ class GATAggregate(torch.autograd.Function):
         a_dst = torch.empty(nh, dtype=torch.float32, device=dev)
         att_src, att_dst = _f32c(att_src.reshape(-1)), _f32c(att_dst.reshape(-1))
         with _timed(cfg, "gat_scores"):
-            _lib.check(L.fitgnn_gat_scores_f32(_lib.dptr(h), C, nh, C, _lib.dptr(att_src), _lib.dptr(att_dst), _lib.dptr(a_src),
-                                               _lib.dptr(a_dst), st), "gat_scores")
+            _lib.call("fitgnn_gat_scores_f32", h, C, nh, C, att_src, att_dst, a_src, a_dst, st)
             if ridx is not None:   # per union row
                 a_src, a_dst = a_src.index_select(0, ridx.index.long()), a_dst.index_select(0, ridx.index.long())
         alpha = torch.empty(g.nnz, dtype=torch.float32, device=dev)
         with _timed(cfg, "gat_edge_softmax"):
-            _lib.check(L.fitgnn_gat_edge_softmax_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(a_src), _lib.dptr(a_dst),
-                                                     float(slope), n, _lib.dptr(alpha), st), "gat_edge_softmax")
+            _lib.call("fitgnn_gat_edge_softmax_f32", g.f.rowptr, g.f.col, a_src, a_dst, float(slope), n, alpha, st)
         ep = _Epilogue(bias is not None, p, training, seed, mask, act=act)
         # (a union whose runs go to the whole-subgraph kernel takes it here too: the attention weights are the launch's CSR values)
         out = spmm_graph(g, h, val=alpha, bias=bias, epilogue=ep.fwd, p=ep.p, seed=ep.seed, mask=ep.mask, cfg=cfg,
@@ -2353,7 +2182,7 @@ class GATAggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dOut):
         h, att_src, att_dst, a_src, a_dst, alpha, out, mask = ctx.saved_tensors
-        g, L = ctx.g, _lib.lib()
+        g = ctx.g
         dOut = _f32c(dOut)
         db_fused = None
         cfg, ep = ctx.cfg, ctx.ep
@@ -2372,18 +2201,15 @@ class GATAggregate(torch.autograd.Function):
         # (with a table operand the entries' columns are its rows: index[col], listed once per graph and index)
         ecol = g.f.col if ridx is None else _entry_rows(g.f, ridx.index)
         with _timed(cfg, "gat_sddmm"):
-            _lib.check(L.fitgnn_sddmm_csr_f32(_lib.dptr(g.f.rowptr), _lib.dptr(ecol), _lib.dptr(dOut), C, _lib.dptr(h), C, n, C,
-                                              _lib.dptr(dalpha), st), "sddmm")
+            _lib.call("fitgnn_sddmm_csr_f32", g.f.rowptr, ecol, dOut, C, h, C, n, C, dalpha, st)
         ds = torch.empty_like(alpha)
         da_dst = torch.empty(n, dtype=torch.float32, device=dev)
         with _timed(cfg, "gat_softmax_bwd"):
-            _lib.check(L.fitgnn_gat_softmax_bwd_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(a_src), _lib.dptr(a_dst),
-                                                    _lib.dptr(alpha), _lib.dptr(dalpha), float(ctx.slope), n, _lib.dptr(ds),
-                                                    _lib.dptr(da_dst), st), "gat_softmax_bwd")
+            _lib.call("fitgnn_gat_softmax_bwd_f32", g.f.rowptr, g.f.col, a_src, a_dst, alpha, dalpha, float(ctx.slope), n, ds, da_dst, st)
         with _timed(cfg, "gat_transpose_edges"):
             ds_t = ds[g._perm_t].contiguous()
             da_src = torch.empty(n, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_csr_row_sum_f32(_lib.dptr(g.t.rowptr), _lib.dptr(ds_t), n, _lib.dptr(da_src), st), "csr_row_sum")
+            _lib.call("fitgnn_csr_row_sum_f32", g.t.rowptr, ds_t, n, da_src, st)
             # dh = A_alpha^T dOut + da_src (x) att_src + da_dst (x) att_dst
             alpha_t = alpha[g._perm_t].contiguous()
         dh = spmm_graph(g, dOut, transposed=True, val=alpha_t, cfg=ctx.cfg, profile_kind="gat_aggregate_t")
@@ -2447,7 +2273,6 @@ class FusedGATLastLayerRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, W, att_src, att_dst, b, Wl, bl, g, slope, p, training, seed, mask, rows, cfg, compact_out=False, link_in=None):
-        L = _lib.lib()
         X = _f32c(X)
         R, K = X.shape
         dev, st = X.device, _lib.stream_ptr(X.device)
@@ -2457,12 +2282,10 @@ class FusedGATLastLayerRows(torch.autograd.Function):
         a_src = torch.empty(R, dtype=torch.float32, device=dev)
         a_dst = torch.empty(R, dtype=torch.float32, device=dev)
         with _timed(cfg, "gat_scores"):
-            _lib.check(L.fitgnn_gat_scores_f32(_lib.dptr(X), X.stride(0), R, K, _lib.dptr(u[0]), _lib.dptr(u[1]), _lib.dptr(a_src), _lib.dptr(a_dst),
-                                               st), "gat_scores")
+            _lib.call("fitgnn_gat_scores_f32", X, X.stride(0), R, K, u[0], u[1], a_src, a_dst, st)
         alpha = torch.empty(g.nnz, dtype=torch.float32, device=dev)
         with _timed(cfg, "gat_edge_softmax"):
-            _lib.check(L.fitgnn_gat_edge_softmax_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(a_src), _lib.dptr(a_dst), float(slope), R,
-                                                     _lib.dptr(alpha), st), "gat_edge_softmax")
+            _lib.call("fitgnn_gat_edge_softmax_f32", g.f.rowptr, g.f.col, a_src, a_dst, float(slope), R, alpha, st)
         AX = spmm_graph(g, X, val=alpha, cfg=cfg, profile_kind="gat_aggregate")                   # [R, K]: every row, every edge
         AXc = AX.index_select(0, rows)
         del AX
@@ -2498,18 +2321,15 @@ class FusedGATLastLayerRows(torch.autograd.Function):
         # the aggregation's backward, on the loss rows' entries: d(alpha), then the softmax / LeakyReLU backward
         dalpha = torch.zeros_like(alpha)
         with _timed(cfg, "gat_sddmm"):
-            _lib.check(L.fitgnn_sddmm_csr_rows_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(dAX), K, _lib.dptr(X), X.stride(0),
-                                                   _lib.dptr(rows), n, K, _lib.dptr(dalpha), st), "sddmm_rows")
+            _lib.call("fitgnn_sddmm_csr_rows_f32", g.f.rowptr, g.f.col, dAX, K, X, X.stride(0), rows, n, K, dalpha, st)
         ds = torch.zeros_like(alpha)
         da_dst = torch.zeros(R, dtype=torch.float32, device=dev)
         with _timed(cfg, "gat_softmax_bwd"):
-            _lib.check(L.fitgnn_gat_softmax_bwd_rows_f32(_lib.dptr(g.f.rowptr), _lib.dptr(g.f.col), _lib.dptr(a_src), _lib.dptr(a_dst), _lib.dptr(alpha),
-                                                         _lib.dptr(dalpha), float(ctx.slope), _lib.dptr(rows), n, _lib.dptr(ds), _lib.dptr(da_dst),
-                                                         st), "gat_softmax_bwd_rows")
+            _lib.call("fitgnn_gat_softmax_bwd_rows_f32", g.f.rowptr, g.f.col, a_src, a_dst, alpha, dalpha, float(ctx.slope), rows, n, ds, da_dst, st)
         with _timed(cfg, "gat_transpose_edges"):
             ds_t = ds[g._perm_t].contiguous()
             da_src = torch.empty(R, dtype=torch.float32, device=dev)
-            _lib.check(L.fitgnn_csr_row_sum_f32(_lib.dptr(g.t.rowptr), _lib.dptr(ds_t), R, _lib.dptr(da_src), st), "csr_row_sum")
+            _lib.call("fitgnn_csr_row_sum_f32", g.t.rowptr, ds_t, R, da_src, st)
             alpha_t = alpha[g._perm_t].contiguous()
         da = torch.stack([da_src, da_dst], dim=1)                                                 # [R, 2]
         du = mm_at_b(da, X, cfg)                                                                  # [2, K] = da^T x
@@ -2533,19 +2353,12 @@ class FusedGATLastLayerRows(torch.autograd.Function):
                     n_part = int(L.fitgnn_spmm_rows_compact_parts(R))
                     part = torch.empty((n_part, K), dtype=torch.float32, device=dev) if link.want_db else None
                     seed_v, epi_v = _seed_arg(link.seed, link.epi)
-                    _lib.check(L.fitgnn_spmm_rows_compact_dz_f32(_lib.dptr(rp_aug), _lib.dptr(xcol_aug), _lib.dptr(val_aug), int(xcol_aug.numel()),
-                                                                 _lib.dptr(op), op.stride(0), n + 2, _lib.dptr(dX), dX.stride(0), R, K, _lib.dptr(X),
-                                                                 epi_v, float(link.p), seed_v, _lib.dptr(link.mask), _lib.dptr(part), st),
-                               "fitgnn_spmm_rows_compact_dz_f32")
-                    db_prev = None
-                    if link.want_db:
-                        db_prev = torch.empty(K, dtype=torch.float32, device=dev)
-                        _lib.check(L.fitgnn_colsum_partials_f32(_lib.dptr(part), n_part, K, _lib.dptr(db_prev), st), "fitgnn_colsum_partials_f32")
-                    link.hand_back(db_prev)
+                    _lib.call("fitgnn_spmm_rows_compact_dz_f32", rp_aug, xcol_aug, val_aug, int(xcol_aug.numel()), op, op.stride(0), n + 2, dX,
+                              dX.stride(0), R, K, X, epi_v, float(link.p), seed_v, link.mask, part, st)
+                    link.hand_back(_fold_partials(part, dev, st) if link.want_db else None)   # at most 8192 parts: no pre-fold
                 else:
-                    _lib.check(L.fitgnn_spmm_rows_compact_f32(_lib.dptr(rp_aug), _lib.dptr(xcol_aug), _lib.dptr(val_aug), int(xcol_aug.numel()),
-                                                              _lib.dptr(op), op.stride(0), n + 2, _lib.dptr(dX), dX.stride(0), R, K, st),
-                               "fitgnn_spmm_rows_compact_f32")
+                    _lib.call("fitgnn_spmm_rows_compact_f32", rp_aug, xcol_aug, val_aug, int(xcol_aug.numel()), op, op.stride(0), n + 2, dX,
+                              dX.stride(0), R, K, st)
         elif ctx.needs_input_grad[0]:
             dX = spmm_graph(g, dAX, transposed=True, val=alpha_t, cfg=cfg, xrow=_compact_positions(g, rows), zero_from=n,
                             profile_kind="gat_aggregate_t")
@@ -2720,8 +2533,7 @@ class APPNPPropagate(torch.autograd.Function):
         idx = None if row_index is None else row_index.index
         n = int(z.shape[0] if idx is None else idx.numel())
         zp = torch.empty((n, 4 * h4), dtype=torch.float32, device=z.device)
-        _lib.check(_lib.lib().fitgnn_gather_rows_padded_f32(_lib.dptr(z), z.stride(0), H, _lib.dptr(idx), n, _lib.dptr(zp), h4,
-                                                            _lib.stream_ptr(z.device)), "fitgnn_gather_rows_padded_f32")
+        _lib.call("fitgnn_gather_rows_padded_f32", z, z.stride(0), H, idx, n, zp, h4, _lib.stream_ptr(z.device))
         return zp
 
     @staticmethod
@@ -2742,29 +2554,24 @@ class APPNPPropagate(torch.autograd.Function):
     def _in_lds(plan, side, x, out, h4, K, alpha, backward, cfg, st, tag):
         """The launches whose K steps run in LDS: the units (the column-sliced kernel, or the whole-signal one under
         OpConfig(appnp_sliced=False)) and the larger subgraphs that fit LDS a slice at a time."""
-        L = _lib.lib()
         if plan.n_units and plan.sliced:
             with _timed(cfg, "appnp_units" + tag):
-                _lib.check(L.fitgnn_appnp_lds_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(plan.units),
-                                                  plan.n_units, plan.max_rows, plan.max_entries, _lib.dptr(x), _lib.dptr(out), h4, K, float(alpha),
-                                                  backward, plan.unit_threads, plan.unit_slice, st), "fitgnn_appnp_lds_f32")
+                _lib.call("fitgnn_appnp_lds_f32", side.rowptr, side.col, side.val, plan.units, plan.n_units, plan.max_rows, plan.max_entries, x, out,
+                          h4, K, float(alpha), backward, plan.unit_threads, plan.unit_slice, st)
         elif plan.n_units:
             with _timed(cfg, "appnp_units" + tag):
-                _lib.check(L.fitgnn_appnp_units_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(plan.units),
-                                                    plan.n_units, plan.max_rows, plan.max_entries, _lib.dptr(x), _lib.dptr(out), h4, K, float(alpha),
-                                                    backward, st), "fitgnn_appnp_units_f32")
+                _lib.call("fitgnn_appnp_units_f32", side.rowptr, side.col, side.val, plan.units, plan.n_units, plan.max_rows, plan.max_entries, x,
+                          out, h4, K, float(alpha), backward, st)
         for sl, ranges, m, max_rows, max_entries, threads in plan.lds_launches:
             with _timed(cfg, "appnp_lds_blocks" + tag):
-                _lib.check(L.fitgnn_appnp_lds_f32(_lib.dptr(side.rowptr), _lib.dptr(side.col), _lib.dptr(side.val), _lib.dptr(ranges), m, max_rows,
-                                                  max_entries, _lib.dptr(x), _lib.dptr(out), h4, K, float(alpha), backward, threads, sl, st),
-                           "fitgnn_appnp_lds_f32")
+                _lib.call("fitgnn_appnp_lds_f32", side.rowptr, side.col, side.val, ranges, m, max_rows, max_entries, x, out, h4, K, float(alpha),
+                          backward, threads, sl, st)
 
     @staticmethod
     def forward(ctx, z0, g, K, alpha, cfg=None, row_index=None):
         """row_index (ops.RowIndex, optional): z0 is the class-wide output on a de-duplicated table and the signal's row r is
         z0[row_index.index[r]] -- gathered into the padded layout in one pass, its adjoint (fitgnn_segment_sum_f32) in backward.
         The result is the [rows x H] VIEW of the padded signal (no copy out of it)."""
-        L = _lib.lib()
         if z0.dtype != torch.float32:
             z0 = z0.float()
         H = int(z0.shape[1])
@@ -2788,9 +2595,8 @@ class APPNPPropagate(torch.autograd.Function):
             if plan.n_blocks:
                 t1, t2 = torch.empty_like(z0p), torch.empty_like(z0p)
                 with _timed(cfg, "appnp_blocks"):
-                    _lib.check(L.fitgnn_appnp_blocks_f32(_lib.dptr(f.rowptr), _lib.dptr(f.col), _lib.dptr(f.val), _lib.dptr(plan.blocks),
-                                                         plan.n_blocks, plan.block_max_rows, plan.block_max_entries, _lib.dptr(z0p), _lib.dptr(out),
-                                                         _lib.dptr(t1), _lib.dptr(t2), h4, K, float(alpha), 0, st), "fitgnn_appnp_blocks_f32")
+                    _lib.call("fitgnn_appnp_blocks_f32", f.rowptr, f.col, f.val, plan.blocks, plan.n_blocks, plan.block_max_rows,
+                              plan.block_max_entries, z0p, out, t1, t2, h4, K, float(alpha), 0, st)
             if plan.n_open:
                 rp, cc, vv = plan.sub["f"]
                 zb0 = z0p.index_select(0, plan.open_rows)
@@ -2798,9 +2604,7 @@ class APPNPPropagate(torch.autograd.Function):
                 for _ in range(K):
                     nxt = torch.empty_like(zb0)
                     with _timed(cfg, "appnp_step"):
-                        _lib.check(L.fitgnn_spmm_narrow_padded_f32(_lib.dptr(rp), _lib.dptr(cc), _lib.dptr(vv), _lib.dptr(z), _lib.dptr(nxt),
-                                                                   plan.n_open, h4, 1.0 - alpha, _lib.dptr(zb0), float(alpha), None, 0.0, st),
-                                   "spmm_narrow_padded")
+                        _lib.call("fitgnn_spmm_narrow_padded_f32", rp, cc, vv, z, nxt, plan.n_open, h4, 1.0 - alpha, zb0, float(alpha), None, 0.0, st)
                     z = nxt
                 out.index_copy_(0, plan.open_rows, z)
             return out if H == 4 * h4 else out[:, :H]
@@ -2808,8 +2612,7 @@ class APPNPPropagate(torch.autograd.Function):
         for _ in range(K):
             nxt = torch.empty_like(z0p)
             with _timed(cfg, "appnp_step"):
-                _lib.check(L.fitgnn_spmm_narrow_padded_f32(_lib.dptr(f.rowptr), _lib.dptr(f.col), _lib.dptr(f.val), _lib.dptr(z), _lib.dptr(nxt),
-                                                           n, h4, 1.0 - alpha, _lib.dptr(z0p), float(alpha), None, 0.0, st), "spmm_narrow_padded")
+                _lib.call("fitgnn_spmm_narrow_padded_f32", f.rowptr, f.col, f.val, z, nxt, n, h4, 1.0 - alpha, z0p, float(alpha), None, 0.0, st)
             z = nxt
         if z is z0p and z0p is z0:
             z = z.clone()   # (K = 0: the input itself)
@@ -2822,13 +2625,11 @@ class APPNPPropagate(torch.autograd.Function):
         if ri is None:
             return res if H == 4 * h4 else res[:, :H]
         out = torch.empty((ri.n_table, H), dtype=torch.float32, device=res.device)
-        _lib.check(_lib.lib().fitgnn_segment_sum_f32(_lib.dptr(ri.seg_off), _lib.dptr(ri.members), ri.n_table, _lib.dptr(res), 4 * h4, H,
-                                                     _lib.dptr(out), H, _lib.stream_ptr(res.device)), "fitgnn_segment_sum_f32")
+        _lib.call("fitgnn_segment_sum_f32", ri.seg_off, ri.members, ri.n_table, res, 4 * h4, H, out, H, _lib.stream_ptr(res.device))
         return out
 
     @staticmethod
     def backward(ctx, dz):
-        L = _lib.lib()
         n, H = dz.shape
         h4 = (H + 3) // 4
         st = _lib.stream_ptr(dz.device)
@@ -2841,10 +2642,8 @@ class APPNPPropagate(torch.autograd.Function):
             if plan.n_blocks:
                 t1, t2 = torch.empty_like(dz), torch.empty_like(dz)
                 with _timed(ctx.cfg, "appnp_blocks_t"):
-                    _lib.check(L.fitgnn_appnp_blocks_f32(_lib.dptr(t.rowptr), _lib.dptr(t.col), _lib.dptr(t.val), _lib.dptr(plan.blocks),
-                                                         plan.n_blocks, plan.block_max_rows, plan.block_max_entries, _lib.dptr(dz), _lib.dptr(out),
-                                                         _lib.dptr(t1), _lib.dptr(t2), h4, ctx.K, float(ctx.alpha), 1, st),
-                               "fitgnn_appnp_blocks_f32")
+                    _lib.call("fitgnn_appnp_blocks_f32", t.rowptr, t.col, t.val, plan.blocks, plan.n_blocks, plan.block_max_rows,
+                              plan.block_max_entries, dz, out, t1, t2, h4, ctx.K, float(ctx.alpha), 1, st)
             if plan.n_open:
                 rp, cc, vv = plan.sub["t"]
                 gb = dz.index_select(0, plan.open_rows)
@@ -2852,9 +2651,8 @@ class APPNPPropagate(torch.autograd.Function):
                 for _ in range(ctx.K):
                     nxt = torch.empty_like(gb)
                     with _timed(ctx.cfg, "appnp_step_t"):
-                        _lib.check(L.fitgnn_spmm_narrow_padded_f32(_lib.dptr(rp), _lib.dptr(cc), _lib.dptr(vv), _lib.dptr(gb), _lib.dptr(nxt),
-                                                                   plan.n_open, h4, 1.0 - ctx.alpha, None, 0.0, _lib.dptr(accb), float(ctx.alpha), st),
-                                   "spmm_narrow_padded")
+                        _lib.call("fitgnn_spmm_narrow_padded_f32", rp, cc, vv, gb, nxt, plan.n_open, h4, 1.0 - ctx.alpha, None, 0.0, accb,
+                                  float(ctx.alpha), st)
                     gb = nxt
                 out.index_copy_(0, plan.open_rows, accb + gb)
             return APPNPPropagate._grad_out(ctx, out, H, h4), None, None, None, None, None
@@ -2862,9 +2660,8 @@ class APPNPPropagate(torch.autograd.Function):
         for _ in range(ctx.K):   # dz_k = (1 - alpha) A^T dz_{k+1};  acc += alpha * dz_{k+1}
             nxt = torch.empty_like(dz)
             with _timed(ctx.cfg, "appnp_step_t"):
-                _lib.check(L.fitgnn_spmm_narrow_padded_f32(_lib.dptr(t.rowptr), _lib.dptr(t.col), _lib.dptr(t.val), _lib.dptr(dz), _lib.dptr(nxt),
-                                                           n, h4, 1.0 - ctx.alpha, None, 0.0, _lib.dptr(acc), float(ctx.alpha), st),
-                           "spmm_narrow_padded")
+                _lib.call("fitgnn_spmm_narrow_padded_f32", t.rowptr, t.col, t.val, dz, nxt, n, h4, 1.0 - ctx.alpha, None, 0.0, acc, float(ctx.alpha),
+                          st)
             dz = nxt
         out = acc + dz
         return APPNPPropagate._grad_out(ctx, out, H, h4), None, None, None, None, None

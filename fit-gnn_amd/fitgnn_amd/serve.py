@@ -163,8 +163,7 @@ class GATPath(GCNPath):
         a0s = torch.empty(n, dtype=torch.float32, device=T.device)
         a0d = torch.empty(n, dtype=torch.float32, device=T.device)
         as0, ad0 = as0.detach().reshape(-1).contiguous(), ad0.detach().reshape(-1).contiguous()
-        _lib.check(_lib.lib().fitgnn_gat_scores_f32(_lib.dptr(T), T.stride(0), n, H, _lib.dptr(as0), _lib.dptr(ad0), _lib.dptr(a0s),
-                                                    _lib.dptr(a0d), _lib.stream_ptr(T.device)), "fitgnn_gat_scores_f32")
+        _lib.call("fitgnn_gat_scores_f32", T, T.stride(0), n, H, as0, ad0, a0s, a0d, _lib.stream_ptr(T.device))
         W1d = W1.detach().double()
         u_s = (as1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()
         u_d = (ad1.detach().reshape(1, -1).double() @ W1d).reshape(-1).float().contiguous()

@@ -76,12 +76,11 @@ def _spmm_csr_pair(rowptr, col, val, tiles, rowptr_t, col_t, val_t, tiles_t, X, 
 
 
 def _gcn_norm_csr(rowptr, col, w):
-    _lib.require_cuda(rowptr, col, w)
+    _lib.require_cuda(col)   # col.device places the outputs and names the stream; the call checks the others
     n = int(rowptr.numel()) - 1
     val = torch.empty(col.numel(), dtype=torch.float32, device=col.device)
     dinv = torch.empty(n, dtype=torch.float32, device=col.device)
-    _lib.check(_lib.lib().fitgnn_gcn_norm_csr_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(val), _lib.dptr(dinv), n,
-                                                  _lib.stream_ptr(col.device)), "fitgnn_gcn_norm_csr_f32")
+    _lib.call("fitgnn_gcn_norm_csr_f32", rowptr, col, w, val, dinv, n, _lib.stream_ptr(col.device))
     return val, dinv
 
 
@@ -99,9 +98,8 @@ def _variation_costs(rowptr, col, w, dw, A, set_off, set_mem):
     K = int(A.shape[1])
     set_len = (set_off[1:] - set_off[:-1]).contiguous()
     cost = torch.empty(n_sets, dtype=torch.float64, device=A.device)
-    _lib.check(_lib.lib().fitgnn_variation_costs_f64(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(w), _lib.dptr(dw), _lib.dptr(A), K,
-                                                     int(A.stride(0)), _lib.dptr(set_off), _lib.dptr(set_len), _lib.dptr(set_mem), n_sets,
-                                                     _lib.dptr(cost), _lib.stream_ptr(A.device)), "fitgnn_variation_costs_f64")
+    _lib.call("fitgnn_variation_costs_f64", rowptr, col, w, dw, A, K, int(A.stride(0)), set_off, set_len, set_mem, n_sets, cost,
+              _lib.stream_ptr(A.device))
     return cost
 
 

@@ -117,19 +117,14 @@ class FlatAdam:
             # step count, the next step's dropout seeds
             sb = self.seed_bank
             fresh = self.flat.fresh
-            _lib.check(_lib.lib().fitgnn_adam_step_acc_f32(_lib.dptr(self.P), _lib.dptr(b), _lib.dptr(fresh), _lib.dptr(self.m),
-                                                           _lib.dptr(self.v), int(b.numel()), self.lr, self.betas[0], self.betas[1],
-                                                           self.eps, self.wd, _lib.dptr(self.step_count),
-                                                           _lib.dptr(sb.seeds) if sb is not None else None,
-                                                           int(sb.seeds.numel()) if sb is not None else 0,
-                                                           (sb.GOLD & 0xFFFFFFFFFFFFFFFF) if sb is not None else 0,
-                                                           _lib.stream_ptr(b.device)), "fitgnn_adam_step_acc_f32")
+            _lib.call("fitgnn_adam_step_acc_f32", self.P, b, fresh, self.m, self.v, int(b.numel()), self.lr, self.betas[0], self.betas[1], self.eps,
+                      self.wd, self.step_count, sb.seeds if sb is not None else None, int(sb.seeds.numel()) if sb is not None else 0,
+                      (sb.GOLD & 0xFFFFFFFFFFFFFFFF) if sb is not None else 0, _lib.stream_ptr(b.device))
             if sb is not None:
                 sb.cursor = 0
             return
-        _lib.check(_lib.lib().fitgnn_adam_step_f32(_lib.dptr(self.P), _lib.dptr(b), _lib.dptr(self.m), _lib.dptr(self.v), int(b.numel()),
-                                                   self.lr, self.betas[0], self.betas[1], self.eps, self.wd, _lib.dptr(self.step_count),
-                                                   _lib.stream_ptr(b.device)), "fitgnn_adam_step_f32")
+        _lib.call("fitgnn_adam_step_f32", self.P, b, self.m, self.v, int(b.numel()), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                  self.step_count, _lib.stream_ptr(b.device))
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero()
@@ -302,14 +297,9 @@ class GDTrainer:
         """Finish the gradient all-reduce: the early bucket was launched from the hook, the first layer's follows here.
         comm_events (a list, or None): HIP-event pairs around this call on the compute stream -- the part of the all-reduce the
         step actually waits for (the early bucket runs on the collective's own stream under the first layer's backward)."""
-        ev = None
-        if self.comm_events is not None and self.flat.buf.is_cuda:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        self._reduce_grads_now()
-        if ev is not None:
-            ev[1].record()
-            self.comm_events.append(ev)
+        from . import ops
+        with ops._timed(sink=self.comm_events if self.flat.buf.is_cuda else None):
+            self._reduce_grads_now()
 
     def _reduce_grads_now(self):
         if self._split and self._work is not None:
