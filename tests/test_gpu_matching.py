@@ -10,6 +10,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+import matching_reference as mr
 from fitgnn_amd import coarsening
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +69,12 @@ def test_edge_list_and_proximities_from_reference_inputs(name):
         XG = torch.from_numpy(z["affinity_GS_X"]).cuda()
         pg = coarsening.proximity(el, "affinity_GS", XG).cpu().numpy()
         assert ulp_diff(pg, z["affinity_GS_w1"]).max() <= 2
+        # what the kernel's operation count allows (matching_reference.affinity_interval): between the float32 roundings of the two
+        # ends of the float64 interval, which lie at most one float32 apart -- and the long-double value rounds to the recorded one
+        p, c, cmax, cond = mr.affinity(t.row, t.col, z["affinity_GS_X"], G.N)
+        lo, hi = (v.astype(np.float32) for v in mr.affinity_interval(t.row, t.col, G.N, p, c, cmax, cond))
+        assert ulp_diff(lo, hi).max() <= 1 and ulp_diff(p.astype(np.float32), z["affinity_GS_w1"]).max() == 0
+        assert np.all((lo <= pg) & (pg <= hi)), f"{int((~((lo <= pg) & (pg <= hi))).sum())} proximities outside the rounded interval"
     A = coarsening._spectral_level1(G, K, z["Uk"].copy(), z["lk"].copy())
     cost = coarsening.edge_costs(el, A).cpu().numpy()
     # the closed form and the reference's 2 x K matrix products round differently only where a_i - a_j cancels (twin nodes,
@@ -80,9 +87,17 @@ def test_edge_list_and_proximities_from_reference_inputs(name):
 def test_test_vectors_from_the_reference_draw(name):
     z = fixture(name)
     el = coarsening.EdgeList(graph(z))
+    G = graph(z)
+    rowptr, col, w, dw = G.W.indptr, G.W.indices, G.W.data, np.asarray(el.dw.cpu().numpy())
     for m in coarsening.RANDOM_METHODS:
         X = coarsening.test_vectors(el, m, x0(z)).cpu().numpy()
         np.testing.assert_allclose(X, z[f"{m}_X"], rtol=1e-10, atol=1e-14 * np.abs(z[f"{m}_X"]).max())
+        # every operation of both kernels and its order is fixed: the float64 reference bit for bit, which itself meets the recorded
+        # vectors to 1e-13 of the largest entry (tests/test_matching_reference_cpu.py)
+        ref = (mr.jacobi(rowptr, col, w, dw, x0(z), 20) if m == "algebraic_JC"
+               else mr.gauss_seidel_ordered(rowptr, col, w, dw, [0, G.N], x0(z)))
+        assert np.array_equal(X.view(np.int64), ref.view(np.int64)), f"{m}: {int((X != ref).sum())} entries differ from the float64 reference"
+        assert np.abs(X - z[f"{m}_X"]).max() <= 1e-13 * np.abs(z[f"{m}_X"]).max()
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c['name']}-{c['method']}-{c['r']}")
