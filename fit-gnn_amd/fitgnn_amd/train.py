@@ -193,6 +193,49 @@ def _make_adam(model, flat, lr, weight_decay):
     return torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
 
 
+def _capture(model, opt, flat, warm_up, record, adam_advances=True, reset=lambda: None):
+    """The ONE way a trainer captures steps in hipGraphs: (the seed bank, what record returned), or (None, None) when the steps must
+    run eagerly.  warm_up(bank) runs two eager steps (library workspaces, autograd buffers), here on a side stream; then the weights
+    and Adam's state are put back in place, and record(bank) captures the caller's graph(s) and returns them.  The captured kernels
+    read their dropout seeds through the bank's device pointers (ops.SeedBank; replays re-run no Python): while the two callables
+    run, the model runs under a copy of its config that carries the bank, afterwards under the very config it had at entry.
+    adam_advances: the optimiser kernel moves the seeds on after every step (one launch less per step); where it does not, the
+    callables issue bank.advance() before each step.  reset(): what the caller's steps leave behind besides the gradient buffer.
+    A warm-up in which autograd meets a stale AccumulateGrad node (_accumulate_stream_guard) is not followed by a capture: ending
+    that capture would take the process down."""
+    assert isinstance(opt, FlatAdam), ("steps are captured on the GPU only, where every trainer's optimiser is a FlatAdam (_make_adam): "
+                                       "its moments and its device-resident step counter exist from construction")
+    from . import ops
+
+    dev = flat.buf.device
+    bank = ops.SeedBank(max(len(getattr(model, "conv", [])), 1), dev)
+    saved_m = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    saved_o = (opt.m.clone(), opt.v.clone(), opt.step_count.clone())
+    prev = model.op_config
+    model.set_op_config(prev.replace(seed_bank=bank))
+    if adam_advances:
+        opt.seed_bank = bank
+    try:
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with _accumulate_stream_guard() as guard, torch.cuda.stream(side):
+            warm_up(bank)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        model.load_state_dict(saved_m)
+        opt.m.copy_(saved_o[0]); opt.v.copy_(saved_o[1]); opt.step_count.copy_(saved_o[2])
+        flat.zero(); reset()   # (GDTrainer's step clears the gradient buffer itself, before and inside its capture: harmless there)
+        if guard.mismatch:
+            if adam_advances:
+                opt.seed_bank = None
+            return None, None
+        graphs = record(bank)
+        flat.zero(); reset()   # capturing does not execute: the weights are untouched, but what the steps clear was only cleared eagerly
+        return bank, graphs
+    finally:
+        model.set_op_config(prev)
+
+
 class GDTrainer:
     def __init__(self, model, batch, lr=0.01, weight_decay=5e-4, reduction="mean", process_group=None, dedup=True,
                  task="node_cls", prune_unused_rows=False, op_config=None, global_train_count=None, lean_step=True, capture="auto"):
@@ -222,10 +265,7 @@ class GDTrainer:
         # first layer on the de-duplicated feature table when the batch carries one (same arithmetic, fewer FLOPs)
         self.dedup = dedup and getattr(batch, "row_index", None) is not None
         self.flat = FlatGrads(model.parameters())
-        if next(model.parameters()).is_cuda:   # one kernel over the flat buffers (same arithmetic as torch.optim.Adam)
-            self.opt = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        else:                                  # host-side logic tests (gloo): the reference's optimiser itself
-            self.opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+        self.opt = _make_adam(model, self.flat, lr, weight_decay)
         self.reduction = reduction
         self.pg = process_group
         self.dist = process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -321,39 +361,35 @@ class GDTrainer:
         self.opt.step()
         return self.flat.tail[0].clone() if self.dist else loss.detach()
 
+    def _loss_step(self, z, rows, scale):
+        """The fused softmax + NLL loss of the logits z on `rows`, backward, optimiser step.  Returns the global loss."""
+        if self.lean:   # the loss's own gradient handed to backward (no ones-fill, no multiplication by it); lean excludes data parallelism
+            from .ops import softmax_nll_raw
+            loss, dz = softmax_nll_raw(z, rows, self._y_train, scale)
+            self.local_loss = loss[0]
+            z.backward(dz)
+            self.opt.step()
+            return loss[0]
+        from .ops import SoftmaxNLL
+        return self._backward_and_step(SoftmaxNLL.apply(z, rows, self._y_train, scale))
+
     def _capture_step(self):
         """Capture one step in a hipGraph (weights / optimiser state are put back after the warm-up steps)."""
-        from . import ops
+        def warm_up(bank):
+            for _ in range(2):
+                bank.cursor = 0
+                self._step_eager()
 
-        dev = self.flat.buf.device
-        bank = ops.SeedBank(max(len(getattr(self.model, "conv", [])), 1), dev)
-        saved_m = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        saved_o = (self.opt.m.clone(), self.opt.v.clone(), self.opt.step_count.clone())
-        self.model.set_op_config(self.cfg.replace(seed_bank=bank))
-        self.opt.seed_bank = bank
-        try:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with _accumulate_stream_guard() as guard, torch.cuda.stream(side):
-                for _ in range(2):
-                    bank.cursor = 0
-                    self._step_eager()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.model.load_state_dict(saved_m)
-            self.opt.m.copy_(saved_o[0]); self.opt.v.copy_(saved_o[1]); self.opt.step_count.copy_(saved_o[2])
-            if guard.mismatch:   # an older autograd graph keeps the parameters' AccumulateGrad nodes on another stream: no capture
-                self.capture = False
-                self.opt.seed_bank = None
-                return
+        def record(bank):
             g = torch.cuda.CUDAGraph()
-            self._graph_loss = torch.zeros((), device=dev)
+            self._graph_loss = torch.zeros((), device=self.flat.buf.device)
             with torch.cuda.graph(g):
                 bank.cursor = 0
                 self._graph_loss.copy_(self._step_eager())
-            self._graph, self._bank = g, bank
-        finally:
-            self.model.set_op_config(self.cfg)
+            return g
+
+        self._bank, self._graph = _capture(self.model, self.opt, self.flat, warm_up, record)   # (the model runs under self.cfg before and after)
+        self.capture = self._graph is not None
 
     def step(self):
         """One GD epoch (run.py:177-215).  Returns the global loss (over every rank's subgraphs) as a 0-dim device tensor."""
@@ -375,41 +411,24 @@ class GDTrainer:
             self._pending, self._work = len(self._late), None
         scale = 1.0 / self.global_count if self.reduction == "mean" else 1.0
         if self.fused_loss:   # logits -> loss and d(loss)/d(logits) in one kernel (same arithmetic as log_softmax + NLLLoss)
-            from .ops import SoftmaxNLL
             if self.sub is not None and not self.prune_forward:
+                from .ops import SoftmaxNLL
                 z = (m.embed_and_head(b.x_table, b.edge_index, b.row_index, out_rows=self.sub) if self.dedup
                      else m.embed_and_head(b.x, b.edge_index, out_rows=self.sub))
-                loss = SoftmaxNLL.apply(z, self._train_pos, self._y_train, scale)
+                return self._backward_and_step(SoftmaxNLL.apply(z, self._train_pos, self._y_train, scale))
+            z = (m.embed_and_head(b.x_table, b.edge_index, b.row_index, loss_rows=b.train_idx, compact_logits=True,
+                                  forward_rows_only=self.prune_forward) if self.dedup
+                 else m.embed_and_head(b.x, b.edge_index, loss_rows=b.train_idx, compact_logits=True, forward_rows_only=self.prune_forward))
+            if z.shape[0] == b.train_idx.numel() and z.shape[0] != b.n_rows:   # the logits of the train rows only, in their order
+                if self._train_arange is None:
+                    self._train_arange = torch.arange(z.shape[0], dtype=torch.int64, device=z.device)
+                rows = self._train_arange
             else:
-                z = (m.embed_and_head(b.x_table, b.edge_index, b.row_index, loss_rows=b.train_idx, compact_logits=True,
-                                      forward_rows_only=self.prune_forward) if self.dedup
-                     else m.embed_and_head(b.x, b.edge_index, loss_rows=b.train_idx, compact_logits=True, forward_rows_only=self.prune_forward))
-                if z.shape[0] == b.train_idx.numel() and z.shape[0] != b.n_rows:   # the logits of the train rows only, in their order
-                    if self._train_arange is None:
-                        self._train_arange = torch.arange(z.shape[0], dtype=torch.int64, device=z.device)
-                    rows = self._train_arange
-                else:
-                    rows = b.train_idx
-                if self.lean and not self.dist:   # the loss's own gradient handed to backward (no ones-fill, no multiplication by it)
-                    from .ops import softmax_nll_raw
-                    loss1, dz = softmax_nll_raw(z, rows, self._y_train, scale)
-                    self.local_loss = loss1[0]
-                    z.backward(dz)
-                    self.opt.step()
-                    return loss1[0]
-                loss = SoftmaxNLL.apply(z, rows, self._y_train, scale)
-            return self._backward_and_step(loss)
+                rows = b.train_idx
+            return self._loss_step(z, rows, scale)
         if self.fused_logits:
-            from .ops import SoftmaxNLL
             z = m.logits(b.x_table, b.edge_index, x_index=b.row_index) if self.dedup else m.logits(b.x, b.edge_index)
-            if self.lean and not self.dist:   # the loss's own gradient handed to backward (no ones-fill, no multiplication by it)
-                from .ops import softmax_nll_raw
-                loss, dz = softmax_nll_raw(z, b.train_idx, self._y_train, scale)
-                self.local_loss = loss[0]
-                z.backward(dz)
-                self.opt.step()
-                return loss[0]
-            return self._backward_and_step(SoftmaxNLL.apply(z, b.train_idx, self._y_train, scale))
+            return self._loss_step(z, b.train_idx, scale)
         out = m(b.x_table, b.edge_index, x_index=b.row_index) if self.dedup else m(b.x, b.edge_index)
         sel = out.index_select(0, b.train_idx)
         if self.task == "node_reg":
@@ -437,80 +456,45 @@ class _CapturedSteps:
     def _build_graphs(self):
         """Capture the steps in hipGraphs of `steps_per_graph` (8) consecutive batches each (shared memory pool: the graphs replay one
         after another, in order)."""
-        from . import ops
-
-        dev = self.flat.buf.device
-        self._bank = ops.SeedBank(max(len(self.model.conv), 1), dev)
-        self._losses = torch.zeros(len(self._steps()), device=dev)
-        # warm-up on a side stream (library workspaces, autograd buffers), then put the weights / Adam state back
-        saved_m = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        # Adam's moment / step tensors must EXIST before capture (a lazily initialised state would be allocated and
-        # zeroed inside the first captured step, i.e. reset on every replay): warm up, then restore them in place
-        flat_opt = isinstance(self.opt, FlatAdam)   # its state (m, v, the device-resident step counter) exists from construction
-        if flat_opt:
-            saved_o = (self.opt.m.clone(), self.opt.v.clone(), self.opt.step_count.clone())
-        else:
-            saved_o = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()} for p, st in self.opt.state.items()}
-        # the captured kernels read their dropout seeds through the bank's device pointers: the model runs under a copy of
-        # its config that carries the bank while the steps are built (replays re-run no Python)
-        prev = self.model.op_config
-        self.model.set_op_config(prev.replace(seed_bank=self._bank))
-        # the optimiser kernel moves the seeds on after every step (one launch less per step) when it is the flat one
-        adam_advances = flat_opt and getattr(self, "lean", True)
-        if adam_advances:
-            self.opt.seed_bank = self._bank
+        steps = self._steps()
+        self._losses = torch.zeros(len(steps), device=self.flat.buf.device)
         # what a step keeps per batch (A_hat x of a narrow first layer, ops.aggregated_input) is formed NOW: made lazily inside a
         # step it would be captured with it and replayed every epoch
         prepare = getattr(self.model, "prepare_static", None)
         if prepare is not None:
-            for b in self._steps():
+            for b in steps:
                 if b is not None:
                     prepare(*self._static_inputs(b))
-        try:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with _accumulate_stream_guard() as guard, torch.cuda.stream(side):
-                for b in self._steps()[:2]:
-                    if not adam_advances:
-                        self._bank.advance()
-                    self._one(b)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.model.load_state_dict(saved_m)
-            if flat_opt:
-                self.opt.m.copy_(saved_o[0]); self.opt.v.copy_(saved_o[1]); self.opt.step_count.copy_(saved_o[2])
-            else:
-                for p, st in self.opt.state.items():
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            v.copy_(saved_o[p][k]) if p in saved_o and k in saved_o[p] else v.zero_()
-            self.flat.zero()
-            if guard.mismatch:   # (see _accumulate_stream_guard) the steps run eagerly
-                self.capture = False
-                if adam_advances:
-                    self.opt.seed_bank = None
-                return
+        # the optimiser kernel moves the seeds on after every step unless the step is the plain one (GraphTrainer(lean_step=False)),
+        # which advances them by a launch of its own
+        adam_advances = getattr(self, "lean", True)
+
+        def warm_up(bank):
+            for b in steps[:2]:
+                if not adam_advances:
+                    bank.advance()
+                self._one(b)
+
+        def record(bank):
             pool = torch.cuda.graph_pool_handle()
-            self._graphs = []
-            steps = self._steps()
+            graphs = []
             per = max(int(getattr(self, "steps_per_graph", 8)), 1)   # consecutive steps share a hipGraph: a replay costs ~9 us of its own
             for k0 in range(0, len(steps), per):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
                     for k in range(k0, min(k0 + per, len(steps))):
                         if not adam_advances:
-                            self._bank.advance()
-                        self._bank.cursor = 0
+                            bank.advance()
+                        bank.cursor = 0
                         slot = self._losses[k:k + 1]
                         r = self._one(steps[k], loss_out=slot)   # (a loss kernel that can write the slot itself saves the copy)
                         if r.data_ptr() != slot.data_ptr():
                             slot.copy_(r.view(1))
-                self._graphs.append(g)
-            # capturing does not execute: the weights are untouched, but the gradient buffer was only zeroed eagerly
-            self.flat.zero()
-        finally:
-            self.model.set_op_config(prev)
+                graphs.append(g)
+            return graphs
 
+        self._bank, self._graphs = _capture(self.model, self.opt, self.flat, warm_up, record, adam_advances=adam_advances)
+        self.capture = self._graphs is not None   # (else the steps run eagerly)
 
     def _replay(self):
         """The epoch's losses from the captured steps, or None when the steps cannot be captured (the caller then runs them eagerly)."""
@@ -642,19 +626,9 @@ class GraphTrainer(_CapturedSteps):
         if batches is not None:   # pre-built (entries may be None: this rank holds no graph of that batch)
             self.batches = list(batches)
             self.global_sizes = list(global_sizes) if global_sizes is not None else [int(b["y"].shape[0]) for b in self.batches]
+            self._form_targets()
         else:
-            graphs = [int(g) for g in graphs]
-            self.batches, self.global_sizes = [], []
-            # contiguous runs of graph ids inside `graphs` are merged into ranges; a batch = list of ranges
-            for b0 in range(0, len(graphs), batch_size):
-                ids_all = graphs[b0:b0 + batch_size]
-                ids = ids_all[self.rank::self.world]
-                self.global_sizes.append(len(ids_all))
-                if not ids:
-                    self.batches.append(None)   # this rank holds no graph of a short last batch: it still joins the step
-                    continue
-                pieces = [gset.batch_ids(ids, kind)] if not _is_range(ids) else [gset.batch(ids[0], ids[-1] + 1, kind)]
-                self.batches.append(_cat_pieces(pieces, kind, types))
+            self._make_batches(gset, [int(g) for g in graphs], kind, batch_size, types)
         if self.world > 1:
             self.capture = False   # the per-step collective is issued eagerly
         if share is None:
@@ -665,6 +639,23 @@ class GraphTrainer(_CapturedSteps):
                 model.set_op_config(model.op_config.replace(grad_sink=self.flat))
             else:
                 _drop_stale_sink(model)
+
+    def _make_batches(self, gset, graphs, kind, batch_size, types):
+        """self.batches / self.global_sizes from the graph ids `graphs`, `batch_size` at a time: this rank's share of every batch (None
+        where it holds no graph of a short last batch: it still joins the step).  A contiguous run of ids is a slice of the set."""
+        self.batches, self.global_sizes = [], []
+        for b0 in range(0, len(graphs), batch_size):
+            ids_all = graphs[b0:b0 + batch_size]
+            ids = ids_all[self.rank::self.world]
+            self.global_sizes.append(len(ids_all))
+            if not ids:
+                self.batches.append(None)
+                continue
+            piece = gset.batch(ids[0], ids[-1] + 1, kind) if _is_range(ids) else gset.batch_ids(ids, kind)
+            self.batches.append(_cat_pieces([piece], kind, types))
+        self._form_targets()
+
+    def _form_targets(self):
         if self.task == "graph_reg":   # static per batch: formed now, not inside a (captured) step
             for b in self.batches:
                 if b is not None and "_tgt" not in b:
@@ -770,50 +761,36 @@ class GraphTrainer(_CapturedSteps):
 
     def _build_shuffled_graph(self):
         """Capture [assemble the batch at the device counter, forward, L1 loss, backward, Adam] once (PaddedBatchPlan.batch is static)."""
-        from . import ops
+        plan = self._plan
 
-        plan, dev = self._plan, self.flat.buf.device
-        bank = ops.SeedBank(max(len(getattr(self.model, "conv", [])), 1), dev)
-        saved_m = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        saved_o = (self.opt.m.clone(), self.opt.v.clone(), self.opt.step_count.clone())
-        prev = self.model.op_config
-        self.model.set_op_config(prev.replace(seed_bank=bank))
-        self.opt.seed_bank = bank
-        try:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with _accumulate_stream_guard() as guard, torch.cuda.stream(side):
-                for _ in range(2):   # warm-up (library workspaces, autograd buffers) on the epoch's first batch
-                    plan.step_idx.zero_()
-                    plan.assemble()
-                    bank.cursor = 0
-                    self._one(self._plan_batch(), loss_out=plan.loss_slot)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.model.load_state_dict(saved_m)
-            self.opt.m.copy_(saved_o[0]); self.opt.v.copy_(saved_o[1]); self.opt.step_count.copy_(saved_o[2])
-            self.flat.zero()
-            plan.step_idx.zero_(); plan.loss_sum.zero_(); plan.loss_slot.zero_()
-            if guard.mismatch:   # (see _accumulate_stream_guard) every batch of every epoch takes the eager way
-                self._shuffled_graph = "eager"
-                self.opt.seed_bank = None
-                return
+        def step(bank):
+            plan.assemble()
+            bank.cursor = 0
+            return self._one(self._plan_batch(), loss_out=plan.loss_slot)
+
+        def warm_up(bank):   # on the epoch's first batch
+            for _ in range(2):
+                plan.step_idx.zero_()
+                step(bank)
+
+        def record(bank):
             pool = torch.cuda.graph_pool_handle()
             graphs = []
             for reps in (1, max(int(getattr(self, "steps_per_graph", 8)), 1)):   # one step, and a run of steps (a replay costs ~10 us of its own)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
                     for _ in range(reps):
-                        plan.assemble()
-                        bank.cursor = 0
-                        r = self._one(self._plan_batch(), loss_out=plan.loss_slot)
+                        r = step(bank)
                         if r.data_ptr() != plan.loss_slot.data_ptr():   # (a loss that is not written to the slot by its own kernel)
                             plan.loss_slot.copy_(r.detach().view(1))
                 graphs.append((reps, g))
-            self._shuffled_graph, self._bank = graphs, bank
-            plan.step_idx.zero_(); plan.loss_sum.zero_(); plan.loss_slot.zero_()   # (capturing does not execute)
-        finally:
-            self.model.set_op_config(prev)
+            return graphs
+
+        def reset():
+            plan.step_idx.zero_(); plan.loss_sum.zero_(); plan.loss_slot.zero_()
+
+        self._bank, graphs = _capture(self.model, self.opt, self.flat, warm_up, record, reset=reset)
+        self._shuffled_graph = graphs if graphs is not None else "eager"   # (eager: every batch of every epoch takes the eager way)
 
     def _plan_batch(self):
         b = self._plan.batch
@@ -872,13 +849,7 @@ class GraphTrainer(_CapturedSteps):
     def _reshuffle(self):
         gset, graphs, kind, batch_size, types = self._rebuild
         perm = torch.randperm(len(graphs)).tolist()   # torch's generator, as the DataLoader's sampler; same on every rank
-        graphs = [graphs[i] for i in perm]            # when the ranks share the seed
-        self.batches, self.global_sizes = [], []
-        for b0 in range(0, len(graphs), batch_size):
-            ids_all = graphs[b0:b0 + batch_size]
-            ids = ids_all[self.rank::self.world]
-            self.global_sizes.append(len(ids_all))
-            self.batches.append(_cat_pieces([gset.batch_ids(ids, kind)], kind, types) if ids else None)
+        self._make_batches(gset, [graphs[i] for i in perm], kind, batch_size, types)   # when the ranks share the seed
 
     def step(self):
         self.model.train()

@@ -425,7 +425,8 @@ def test_graph_level_training_follows_the_reference_loops(mods, kind, extra):
 @pytest.mark.parametrize("kind", ["gs", "gc"])
 def test_captured_graph_steps_equal_eager_steps(mods, kind):
     """GraphTrainer(capture=True): every batch step replayed from a hipGraph == the eager steps (dropout off: same
-    losses and weights); with dropout on, successive replays draw different patterns (device-resident seeds)."""
+    losses and weights); with dropout on, successive replays draw different patterns (device-resident seeds).  Subgraph view: the
+    same for the plain step (lean_step=False), whose captured steps advance the seeds by a launch of their own."""
     from fitgnn_amd import graph_data, train
 
     network, fnn, gorc = mods
@@ -450,6 +451,25 @@ def test_captured_graph_steps_equal_eager_steps(mods, kind):
     t3 = train.GraphTrainer(m2, gset, list(range(16)), kind=kind, batch_size=16, prop=1, capture=True, lr=0.0)
     l1, l2 = float(t3.step()), float(t3.step())
     assert l1 != l2
+    if kind == "gs":
+        # the plain step (lean_step=False) captured: the seed bank advanced by a launch of its own, none on the optimiser
+        torch.manual_seed(3)
+        m4 = cls(args).cuda()
+        m5 = cls(args).cuda()
+        m5.load_state_dict(m4.state_dict())
+        m4.dropout_p = m5.dropout_p = 0.0
+        t4 = train.GraphTrainer(m4, gset, list(range(64)), kind=kind, batch_size=16, prop=1, lean_step=False)
+        t5 = train.GraphTrainer(m5, gset, list(range(64)), kind=kind, batch_size=16, prop=1, lean_step=False, capture=True)
+        for epoch in range(3):
+            a, b = float(t4.step()), float(t5.step())
+            assert a == pytest.approx(b, rel=1e-5), (epoch, a, b)
+        for (k, v), (_, w) in zip(m4.state_dict().items(), m5.state_dict().items()):
+            assert rel(w, v) < 1e-4, k
+        assert t5._graphs is not None and t5.opt.seed_bank is None
+        m5.dropout_p = 0.5
+        t6 = train.GraphTrainer(m5, gset, list(range(16)), kind=kind, batch_size=16, prop=1, lean_step=False, capture=True, lr=0.0)
+        l1, l2 = float(t6.step()), float(t6.step())
+        assert l1 != l2 and t6._graphs is not None and t6.opt.seed_bank is None
 
 
 def test_flat_artefact_round_trip(mods, tmp_path):
@@ -1250,6 +1270,7 @@ def test_gd_step_replayed_from_a_hipgraph_equals_the_eager_step(mods, hidden, cl
             assert torch.equal(p.detach(), q.detach()), (epoch, k)
             assert torch.equal(p.grad, q.grad), (epoch, k)
     assert t2._graph is not None
+    assert m2.op_config is t2.cfg and t2.cfg.seed_bank is None   # the capture put the config of before it back
     m2.dropout_p = 0.5
     t3 = train.GDTrainer(m2, batch, lr=0.0, weight_decay=0.0, capture=True)
     l1 = float(t3.step())
