@@ -82,6 +82,11 @@ SIGNATURES = {
     "fitgnn_sddmm_csr_rows_f32": (ctypes.c_int, [ptr, ptr, ptr, c_i64, ptr, c_i64, ptr, c_i32, c_i32, ptr, ptr]),
     "fitgnn_gat_softmax_bwd_rows_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_f32, ptr, c_i32, ptr, ptr, ptr]),
     "fitgnn_gat_softmax_bwd_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_f32, c_i32, ptr, ptr, ptr]),
+    "fitgnn_gat_heads_scores_f32": (ctypes.c_int, [ptr, c_i64, c_i32, c_i32, c_i32, ptr, ptr, ptr, ptr, ptr]),
+    "fitgnn_gat_heads_edge_softmax_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_f32, c_i32, c_i64, c_i32, ptr, ptr]),
+    "fitgnn_gat_heads_aggregate_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, ptr, c_i64, c_i32, c_i64, c_i32, c_i32, ptr, ptr]),
+    "fitgnn_gat_heads_sddmm_f32": (ctypes.c_int, [ptr, ptr, ptr, c_i64, ptr, c_i64, c_i32, c_i64, c_i32, c_i32, ptr, ptr]),
+    "fitgnn_gat_heads_softmax_bwd_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_f32, c_i32, c_i64, c_i32, ptr, ptr, ptr]),
     "fitgnn_l1_loss_f32": (ctypes.c_int, [ptr, ptr, c_i32, c_f32, ptr, ptr, ptr]),
     "fitgnn_softmax_nll_workspace_bytes": (c_size, [c_i32]),
     "fitgnn_softmax_nll_f32": (ctypes.c_int, [ptr, c_i64, c_i32, c_i32, ptr, ptr, c_i32, c_f32, ptr, ptr, ptr, c_size, ptr]),

@@ -27,13 +27,26 @@ def _make_convs(args):
         raise AttributeError(f"fitgnn_amd.nn has no layer '{args.layer_name}'")
     convs = nn.ModuleList()
     dims = [args.num_features] + [args.hidden] * args.num_layers1
+    heads = int(getattr(args, "heads", 1)) if args.layer_name == "GATConv" else 1   # (an extension: the reference passes one head)
+    if heads < 1:
+        raise ValueError(f"heads = {heads}: a GATConv layer has at least one attention head")
+    if args.hidden % heads != 0:
+        raise ValueError(f"hidden = {args.hidden} is not a multiple of heads = {heads}: every GATConv layer is "
+                         "GATConv(in, hidden // heads, heads=heads), its output hidden wide")
     for i in range(args.num_layers1):
         if args.layer_name == "GINConv":  # network.py:19-21: two-layer ReLU MLP, train_eps=True
             mlp = nn.Sequential(fnn.Linear(dims[i], args.hidden), nn.ReLU(), fnn.Linear(args.hidden, args.hidden), nn.ReLU())
             convs.append(cls(mlp, train_eps=True))
+        elif heads > 1:
+            convs.append(cls(dims[i], args.hidden // heads, heads=heads))
         else:
             convs.append(cls(dims[i], dims[i + 1]))
     return convs
+
+
+def _one_head_gat(conv):
+    """conv is a GATConv that runs the single-head kernels (ops.GATAggregate: fused epilogue, links, de-duplicated table, loss rows)."""
+    return isinstance(conv, fnn.GATConv) and conv.heads == 1
 
 
 class _Base(nn.Module):
@@ -70,7 +83,7 @@ class _Base(nn.Module):
         """Layer 0 on a de-duplicated feature table (x_index: ops.RowIndex mapping union rows to table rows).
         gat_link: the link an attention layer records for an aggregate-first attention layer right behind it (FusedGATLastLayerRows)."""
         conv, mask = self.conv[0], self._mask(0)
-        if isinstance(conv, fnn.GATConv) and x_table.is_cuda and link_out is None:
+        if _one_head_gat(conv) and x_table.is_cuda and link_out is None:   # (a multi-head layer: None, the caller gathers the rows)
             return conv.forward_elu_dropout(x_table, edge_index, p=self.dropout_p, training=self.training, mask=mask, x_index=x_index,
                                             link_out=gat_link)
         if not (isinstance(conv, fnn.GCNConv) and x_table.is_cuda):
@@ -116,11 +129,14 @@ class _Base(nn.Module):
                     x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask, link_in=link,
                                                  link_out=nxt)
                 link = nxt
-            elif isinstance(conv, fnn.GATConv) and x.is_cuda:
+            elif _one_head_gat(conv) and x.is_cuda:
                 mask = self._mask(i)
                 is_tail = i + 1 == (self.num_layers if last is None else last)
                 x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask,
                                              link_out=tail_link if is_tail else None)
+                link = None
+            elif isinstance(conv, fnn.GATConv) and x.is_cuda:   # heads > 1: conv -> elu -> dropout unfused, no link (the mask honoured)
+                x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=self._mask(i))
                 link = None
             else:
                 x = conv(x, edge_index)
@@ -177,7 +193,7 @@ class _Base(nn.Module):
         link = ops.EpilogueLink() if (L > 1 and x.is_cuda and isinstance(self.conv[1], fnn.GCNConv)) else None
         # an attention layer right below an aggregate-first attention layer hands its ELU' / dropout' to that layer's adjoint aggregation
         glink = None
-        if (not fused_tail and L > 1 and x.is_cuda and isinstance(last, fnn.GATConv) and isinstance(self.conv[L - 2], fnn.GATConv)
+        if (not fused_tail and L > 1 and x.is_cuda and _one_head_gat(last) and _one_head_gat(self.conv[L - 2])
                 and loss_rows is not None and self.op_config.last_layer_on_loss_rows and loss_rows.numel() > 0):
             glink = ops.EpilogueLink()
         if x_index is not None:
@@ -191,7 +207,7 @@ class _Base(nn.Module):
             link = None
         if not fused_tail:
             cfg = self.op_config
-            if (L > 0 and x.is_cuda and isinstance(last, fnn.GATConv) and loss_rows is not None and cfg.last_layer_on_loss_rows
+            if (L > 0 and x.is_cuda and _one_head_gat(last) and loss_rows is not None and cfg.last_layer_on_loss_rows
                     and loss_rows.numel() > 0 and last.lin.weight.shape[0] % 4 == 0 and last.lin.weight.shape[1] % 4 == 0
                     and ops.head_rows_supported(x.new_empty((1, last.lin.weight.shape[0])), self.lt1.weight)
                     and ops.head_fusable(self.lt1.in_features, self.lt1.out_features)

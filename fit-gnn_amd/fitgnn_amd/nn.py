@@ -4,7 +4,9 @@ FIT-GNN resolves its layer class by name -- `getattr(torch_geometric.nn, args.la
 (network.py:13,41,70,101,141,172) -- and calls `conv(x, edge_index)`.  This module is the namespace
 that lookup is pointed at instead: same constructor arguments, same `forward(x, edge_index)`, same
 parameter names (so `state_dict`s interchange: `lin.weight [out,in]`, `bias [out]` for GCNConv -- the
-layout pinned by Baselines/SGGC/GCN/params/checkpoint-best-acc.pkl).
+layout pinned by Baselines/SGGC/GCN/params/checkpoint-best-acc.pkl).  GATConv also takes PyG's `heads` and `concat`
+(`lin.weight [heads * out, in]`, `att_src` / `att_dst [1, heads, out]`): one head runs the fused single-head path, more heads
+the multi-head kernels of csrc/gat_heads.hip.
 """
 import math
 
@@ -129,29 +131,48 @@ class GINConv(_OpConfigured, nn.Module):
 
 
 class GATConv(_OpConfigured, nn.Module):
-    """PyG GATConv with the arguments FIT-GNN passes (network.py:13-17: `GATConv(in, out)` -> heads=1, concat,
-    negative_slope=0.2, dropout=0, add_self_loops, bias).  Parameters: lin.weight [out,in], att_src [1,1,out],
-    att_dst [1,1,out], bias [out] (PyG >= 2.4 naming)."""
+    """PyG GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True) with dropout=0 and
+    add_self_loops (network.py:13-17 passes `GATConv(in, out)`: one head).  Parameters (PyG >= 2.4 naming): lin.weight
+    [heads * out, in], att_src, att_dst [1, heads, out], bias [heads * out] with concat, else [out].
+    heads == 1 runs ops.GATAggregate (the tile-planned SpMM with the attention weights as its values, fused ELU / dropout epilogue,
+    de-duplicated first layer); heads > 1 runs ops.GATHeadsAggregate (csrc/gat_heads.hip: every head in one launch per step) with
+    ELU / dropout, the head mean of concat=False and its bias as torch operations around it.  No attention dropout."""
 
-    def __init__(self, in_channels, out_channels, heads=1, negative_slope=0.2, bias=True):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True):
         super().__init__()
-        if heads != 1:
-            raise NotImplementedError("FIT-GNN constructs GATConv with the default single head")
+        if int(heads) < 1:
+            raise ValueError(f"GATConv: heads = {heads}")
         self.in_channels, self.out_channels, self.negative_slope = in_channels, out_channels, negative_slope
-        self.lin = nn.Linear(in_channels, out_channels, bias=False)
-        self.att_src = nn.Parameter(torch.empty(1, 1, out_channels))
-        self.att_dst = nn.Parameter(torch.empty(1, 1, out_channels))
-        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.heads, self.concat = int(heads), bool(concat)
+        self.lin = nn.Linear(in_channels, self.heads * out_channels, bias=False)
+        self.att_src = nn.Parameter(torch.empty(1, self.heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, self.heads, out_channels))
+        self.bias = nn.Parameter(torch.empty(self.heads * out_channels if self.concat else out_channels)) if bias else None
         self.reset_parameters()
 
     def reset_parameters(self):
         glorot_(self.lin.weight)
-        glorot_(self.att_src)
+        glorot_(self.att_src)   # (bound sqrt(6 / (heads + out)), as PyG's glorot on [1, heads, out])
         glorot_(self.att_dst)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
+    def _forward_heads(self, x, edge_index):
+        """heads > 1: Linear, then every head's attention in one launch per step (ops.GATHeadsAggregate); concat=False takes the mean
+        over the heads of the concatenated result and adds the bias afterwards."""
+        g = csr_for(edge_index, x.shape[0], "gat")
+        cfg = self.op_config
+        h = ops.Linear.apply(x.float(), self.lin.weight, cfg)
+        att_src, att_dst = self.att_src.view(-1), self.att_dst.view(-1)
+        if self.concat:
+            return ops.GATHeadsAggregate.apply(h, att_src, att_dst, self.bias, g, self.heads, self.negative_slope, cfg)
+        out = ops.GATHeadsAggregate.apply(h, att_src, att_dst, None, g, self.heads, self.negative_slope, cfg)
+        out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
     def forward(self, x, edge_index):
+        if self.heads > 1:
+            return self._forward_heads(x, edge_index)
         g = csr_for(edge_index, x.shape[0], "gat")
         cfg = self.op_config
         h = ops.Linear.apply(x.float(), self.lin.weight, cfg)
@@ -162,7 +183,16 @@ class GATConv(_OpConfigured, nn.Module):
         """conv -> F.elu -> F.dropout (network.py:31-33) with the activation in the aggregation kernel's epilogue.
         x_index (ops.RowIndex, optional): x is a de-duplicated feature table and node r of the graph is a copy of table row
         x_index.index[r]: the Linear and the score dots run on the table (ops.GATAggregate, ridx).
-        link_out (ops.EpilogueLink): the output goes to exactly one consumer that may apply this layer's ELU' / dropout' itself."""
+        link_out (ops.EpilogueLink): the output goes to exactly one consumer that may apply this layer's ELU' / dropout' itself.
+        heads > 1: forward() followed by F.elu and the dropout as torch operations (an injected mask as z * mask / (1 - p)); a table
+        is gathered to the union rows first and link_out stays unrecorded (its consumer then takes the plain gradient)."""
+        if self.heads > 1:
+            if x_index is not None:
+                x = x.index_select(0, x_index.index.long())
+            z = F.elu(self._forward_heads(x, edge_index))
+            if mask is not None and training:
+                return z * mask.to(z.dtype) / (1.0 - p)
+            return F.dropout(z, p=p, training=training)
         n = x.shape[0] if x_index is None else int(x_index.index.numel())
         g = csr_for(edge_index, n, "gat")
         cfg = self.op_config
@@ -170,6 +200,9 @@ class GATConv(_OpConfigured, nn.Module):
         seed = ops.dropout_seed(cfg, training, p, mask)
         return ops.GATAggregate.apply(h, self.att_src.view(-1), self.att_dst.view(-1), self.bias, g, self.negative_slope,
                                       True, float(p), bool(training), seed, mask, cfg, x_index, link_out)
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + ("" if self.concat else ", concat=False")
 
 
 class APPNP(_OpConfigured, nn.Module):

@@ -1221,12 +1221,13 @@ def gat_query_gather(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, rows, xrow=No
 
 
 def _gat_query_shapes(model):
-    """(H2, C) when `model` is exactly two GATConv layers and a head with hidden sizes multiples of 16, the first at most 512 (a wave
-    holds a whole layer-0 row), and contiguous float32 parameters on the GPU; None otherwise.  The callers add their tail's LDS bound."""
+    """(H2, C) when `model` is exactly two single-head GATConv layers and a head with hidden sizes multiples of 16, the first at most
+    512 (a wave holds a whole layer-0 row), and contiguous float32 parameters on the GPU; None otherwise (a multi-head layer among
+    them: the query kernels take one score per row).  The callers add their tail's LDS bound."""
     from . import nn as fnn
     convs = list(getattr(model, "conv", ()))
     lt1 = getattr(model, "lt1", None)
-    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GATConv for c in convs):
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GATConv and c.heads == 1 for c in convs):
         return None
     W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
     att = [convs[0].att_src, convs[0].att_dst, convs[1].att_src, convs[1].att_dst]
@@ -2230,6 +2231,84 @@ class GATAggregate(torch.autograd.Function):
         else:
             db = dOut.sum(0) if ctx.has_bias and ctx.needs_input_grad[3] else None
         return dh, datt_src, datt_dst, db, None, None, None, None, None, None, None, None, None, None
+
+
+def _perm_t32(g):
+    """g._perm_t as the int32 member list fitgnn_segment_sum_f32 takes (made once per graph)."""
+    p = getattr(g, "_perm_t_i32", None)
+    if p is None:
+        p = g._perm_t.to(torch.int32).contiguous()
+        g._perm_t_i32 = p
+    return p
+
+
+class GATHeadsAggregate(torch.autograd.Function):
+    """out = per-head softmax-attention aggregation of h over the CSR graph g (GATConv.propagate, heads > 1, concat layout) + bias.
+    Inputs h [N, heads * C] (head hd owns columns hd*C .. (hd+1)*C), att_src, att_dst [heads * C], bias [heads * C] | None.  g as for
+    GATAggregate.  Scores are [N, heads], attention weights and their gradients [nnz, heads] entry-major (csrc/gat_heads.hip).
+    No fused ELU / dropout epilogue, no EpilogueLink, no row indirection: those stay single-head features."""
+
+    @staticmethod
+    def forward(ctx, h, att_src, att_dst, bias, g, heads, slope, cfg):
+        h = _f32c(h)
+        n, W = h.shape
+        Hd = int(heads)
+        if n != g.n or W % Hd != 0:
+            raise ValueError(f"GATHeadsAggregate: h is {tuple(h.shape)} for a graph of {g.n} rows and {Hd} heads")
+        C = W // Hd
+        dev = h.device
+        st = _lib.stream_ptr(dev)
+        att_src, att_dst = _f32c(att_src.reshape(-1)), _f32c(att_dst.reshape(-1))
+        a_src = torch.empty((n, Hd), dtype=torch.float32, device=dev)
+        a_dst = torch.empty((n, Hd), dtype=torch.float32, device=dev)
+        with _timed(cfg, "gat_heads_scores"):
+            _lib.call("fitgnn_gat_heads_scores_f32", h, W, n, Hd, C, att_src, att_dst, a_src, a_dst, st)
+        alpha = torch.empty((g.nnz, Hd), dtype=torch.float32, device=dev)
+        with _timed(cfg, "gat_heads_edge_softmax"):
+            _lib.call("fitgnn_gat_heads_edge_softmax_f32", g.f.rowptr, g.f.col, a_src, a_dst, float(slope), n, g.nnz, Hd, alpha, st)
+        out = torch.empty((n, W), dtype=torch.float32, device=dev)
+        b = None if bias is None else _f32c(bias)
+        with _timed(cfg, "gat_heads_aggregate"):
+            _lib.call("fitgnn_gat_heads_aggregate_f32", g.f.rowptr, g.f.col, alpha, h, W, out, W, n, g.nnz, Hd, C, b, st)
+        ctx.save_for_backward(h, att_src, att_dst, a_src, a_dst, alpha)
+        ctx.g, ctx.heads, ctx.slope, ctx.has_bias, ctx.cfg = g, Hd, slope, bias is not None, cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, dOut):
+        h, att_src, att_dst, a_src, a_dst, alpha = ctx.saved_tensors
+        g, Hd, cfg = ctx.g, ctx.heads, ctx.cfg
+        dOut = _f32c(dOut)
+        n, W = h.shape
+        C = W // Hd
+        dev = h.device
+        st = _lib.stream_ptr(dev)
+        dalpha = torch.empty_like(alpha)
+        with _timed(cfg, "gat_heads_sddmm"):
+            _lib.call("fitgnn_gat_heads_sddmm_f32", g.f.rowptr, g.f.col, dOut, W, h, W, n, g.nnz, Hd, C, dalpha, st)
+        ds = torch.empty_like(alpha)
+        da_dst = torch.empty((n, Hd), dtype=torch.float32, device=dev)
+        with _timed(cfg, "gat_heads_softmax_bwd"):
+            _lib.call("fitgnn_gat_heads_softmax_bwd_f32", g.f.rowptr, g.f.col, a_src, a_dst, alpha, dalpha, float(ctx.slope), n, g.nnz, Hd,
+                      ds, da_dst, st)
+        with _timed(cfg, "gat_heads_transpose_edges"):
+            # da_src[j, hd] = the sum of ds over column j, in the transposed order (fixed: no atomics)
+            da_src = segment_sum(g.t.rowptr, _perm_t32(g), ds, n)
+            alpha_t = alpha.index_select(0, g._perm_t)
+        dh = torch.empty((n, W), dtype=torch.float32, device=dev)
+        with _timed(cfg, "gat_heads_aggregate_t"):   # dh = A_alpha^T dOut, head by head in one launch
+            _lib.call("fitgnn_gat_heads_aggregate_f32", g.t.rowptr, g.t.col, alpha_t, dOut, W, dh, W, n, g.nnz, Hd, C, None, st)
+        h3 = h.view(n, Hd, C)
+        with _timed(cfg, "gat_heads_rank1"):
+            # dh[:, hd slice] += da_src[:, hd] (x) att_src[hd] + da_dst[:, hd] (x) att_dst[hd]
+            dh3 = dh.view(n, Hd, C)
+            dh3.addcmul_(da_src.unsqueeze(2), att_src.view(1, Hd, C))
+            dh3.addcmul_(da_dst.unsqueeze(2), att_dst.view(1, Hd, C))
+        # d att_src[hd] = sum_i da_src[i, hd] h[i, hd slice]
+        datt_src = (da_src.unsqueeze(2) * h3).sum(0).reshape(-1) if ctx.needs_input_grad[1] else None
+        datt_dst = (da_dst.unsqueeze(2) * h3).sum(0).reshape(-1) if ctx.needs_input_grad[2] else None
+        db = dOut.sum(0) if ctx.has_bias and ctx.needs_input_grad[3] else None
+        return dh, datt_src, datt_dst, db, None, None, None, None
 
 
 def _gat_rank2_csr(g, rows, pos):

@@ -73,6 +73,9 @@ def build_parser():
     p.add_argument('--data_root', type=str, default='./dataset')
     p.add_argument('--device', type=str, default='cuda')
     p.add_argument('--layer_name', type=str, default='GCNConv')
+    p.add_argument('--heads', type=int, default=1,
+                   help="attention heads of every --layer_name GATConv layer, each hidden / heads wide: the value the model was trained "
+                        "with (main.py --heads); other layers ignore it")
     p.add_argument('--n_graphs', type=int, default=2000)
     p.add_argument('--community_nodes', type=int, default=165000)
     p.add_argument('--query_engine', action='store_true',

@@ -82,6 +82,8 @@ def build_parser():
     p.add_argument('--community_method', type=str, default='label_propagation', choices=['label_propagation', 'modularity'])
     p.add_argument('--n_graphs', type=int, default=2000)  # size of the synthetic-qm9 stand-in (QM9 itself: 130 831)
     p.add_argument('--dropout', type=float, default=0.5)  # the reference calls F.dropout with its default p = 0.5 (network.py:33)
+    # attention heads of every --layer_name GATConv layer, each hidden / heads wide (the reference passes one head); other layers ignore it
+    p.add_argument('--heads', type=int, default=1)
     return p
 
 

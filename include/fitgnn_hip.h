@@ -552,6 +552,36 @@ int fitgnn_gat_softmax_bwd_rows_f32(const int32_t *rowptr, const int32_t *col, c
                                     float *ds, float *da_dst, void *stream);
 int fitgnn_csr_row_sum_f32(const int32_t *rowptr, const float *v, int32_t n, float *y, void *stream);
 
+/* ---- multi-head graph attention (torch_geometric.nn.GATConv(in, out, heads), concat layout; csrc/gat_heads.hip).  Rows of h, X, Y,
+ * dOut are W = heads * C floats wide, head hd owning columns hd*C .. (hd+1)*C.  Per-node scores a_src, a_dst, da_dst are [n, heads]
+ * row-major; per-entry quantities alpha, dalpha, ds are [nnz, heads] ENTRY-major (entry e, head hd at e * heads + hd).  Per head the
+ * operations are those of the single-head block above:
+ *   scores        a_src[i, hd] = h_i[hd slice] . att_src[hd slice],  a_dst likewise (att_src, att_dst: [W]); one pass over h
+ *   edge_softmax  alpha[e, hd] = softmax over CSR row i of LeakyReLU(a_src[col[e], hd] + a_dst[i, hd]); a row of 0 entries writes nothing
+ *   aggregate     Y[i, hd*C + c] = sum_e alpha[e, hd] X[col[e], hd*C + c] (+ bias[hd*C + c]; bias may be NULL), entries in CSR order.
+ *                 On the transposed pattern with alpha_t = alpha[perm_t] it is the adjoint (dh = A_alpha^T dOut)
+ *   sddmm         dalpha[e, hd] = dOut[i, hd slice] . h[col[e], hd slice]
+ *   softmax_bwd   ds[e, hd] = alpha (dalpha - sum_k alpha_k dalpha_k) LeakyReLU'(s);  da_dst[i, hd] = sum over row i of ds[., hd]
+ *                 (da_src = fitgnn_segment_sum_f32 of ds over the transposed order: offsets rowptr_t, members perm_t, F = heads)
+ * One wavefront per row (scores, aggregate, sddmm) or one thread / wavefront per (row, head) (the two softmax passes), no atomics, no
+ * LDS: two launches give the same bits.  16-byte lane loads with the row (of dOut, or the accumulator) in registers when C % 4 == 0
+ * (no float4 straddles two heads), W <= 1024, the leading dimensions are multiples of 4 and the row pointers 16-byte aligned; scores
+ * and sddmm also need C / 4 to be a power of two (a head's lanes are then contiguous and its sum a butterfly inside the wave).
+ * Anything else takes a scalar path: every heads >= 1, C >= 1 is served.  nnz = rowptr[n], handed in because no entry point reads
+ * device memory on the host.  FITGNN_E_BADARG, before any launch: a NULL pointer (n > 0), heads < 1, C < 1, n < 0, nnz < 0, a leading
+ * dimension below W, or n * heads, nnz * heads or W at or above 2^31 (the kernels index with 32 bits). */
+int fitgnn_gat_heads_scores_f32(const float *h, int64_t ldh, int32_t n, int32_t heads, int32_t C, const float *att_src,
+                                const float *att_dst, float *a_src, float *a_dst, void *stream);
+int fitgnn_gat_heads_edge_softmax_f32(const int32_t *rowptr, const int32_t *col, const float *a_src, const float *a_dst,
+                                      float negative_slope, int32_t n, int64_t nnz, int32_t heads, float *alpha, void *stream);
+int fitgnn_gat_heads_aggregate_f32(const int32_t *rowptr, const int32_t *col, const float *alpha, const float *X, int64_t ldx, float *Y,
+                                   int64_t ldy, int32_t n, int64_t nnz, int32_t heads, int32_t C, const float *bias, void *stream);
+int fitgnn_gat_heads_sddmm_f32(const int32_t *rowptr, const int32_t *col, const float *dOut, int64_t ldo, const float *h, int64_t ldh,
+                               int32_t n, int64_t nnz, int32_t heads, int32_t C, float *dalpha, void *stream);
+int fitgnn_gat_heads_softmax_bwd_f32(const int32_t *rowptr, const int32_t *col, const float *a_src, const float *a_dst,
+                                     const float *alpha, const float *dalpha, float negative_slope, int32_t n, int64_t nnz,
+                                     int32_t heads, float *ds, float *da_dst, void *stream);
+
 /* Propagation on narrow signals (APPNP, Baselines/SGGC/APPNP/networks.py:11,23: z <- (1-alpha) A_hat z + alpha z0 on
  * [rows x num_classes]): Y = beta * (A X) + gamma * Z0 (Z0 may be NULL), and optionally ACC += delta * X (the backward
  * pass accumulates d z0 while it propagates).  X, Y, Z0, ACC: dense row-major [n_rows x H], leading dimension H; A is
