@@ -8,6 +8,8 @@
 //     z_q   = ELU(W1 g_q + b1);  out_q = Wl z_q + bl  (log_softmax)         fitgnn_gcn_query_tail_f32
 // The union is block-diagonal, so both hops stay inside the query's subgraph: the values are the per-subgraph forward's.
 // Two GATConv layers take the same tail behind fitgnn_gat_query_gather_f32 (attention over both hops: see gat_query_hops_kernel).
+// Two GATConv layers of 2..8 heads have fitgnn_mhgat_query_gather_f32 (every head's attention over both hops: see mhgat_hops_kernel)
+// and fitgnn_mhgat_query_tail_f32 (the tail with a grouped first product: see mhgat_tail_kernel).
 // Two SAGEConv layers take it behind fitgnn_sage_query_gather_f32 (a gather plus a root term: see sage_query_gather_kernel).
 // Two GINConv layers have launches of their own, fitgnn_gin_query_hops_f32 and fitgnn_gin_query_tail_f32 (a dense product behind a
 // ReLU per one-hop row: see gin_query_hops_kernel).
@@ -339,6 +341,248 @@ __global__ __launch_bounds__(256) void gat_query_hops_kernel(const int32_t *__re
         if (live[s]) *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + s * 256 + lane * 4) = g[s];
 }
 
+// ---- attention over both hops, several heads (two GATConv layers with the same heads in 2..8, concat) ----
+//   h_r[c]      = ELU(sum_k alpha^{hd(c)}_rk T[t(k)][c] + b0[c]),  alpha^{hd}_r. = softmax_k lrelu(a0s[t(k)][hd] + a0d[t(r)][hd], slope0)
+//   G_q[hd H + c] = sum_j beta^{hd}_j h_j[c],                      beta^{hd} = softmax_j lrelu(U_s[hd] . h_j + U_d[hd] . h_q, slope1)
+// hd(c) = c / C0, C0 = H / heads, C0 % 4 == 0: a lane's float4 lies in one head.  Every head weighs the SAME rows h_j, by a dot over
+// all of H, so G is heads times as wide as h.  The operation order is gat_query_hops_kernel's, head by head (tests/
+// mhgat_query_reference.py mirrors it): "row r" with the maximum, the weights and l of the column's own head; "dot", "query q" and
+// "merge" once per head with (U_s[hd], U_d[hd]) and a state (M, L, P) of its own.  With equal layer-0 scores in every head, block hd
+// of G holds the bits of gat_query_hops_kernel on (a0s[:, 0], a0d[:, 0], U_s[hd], U_d[hd]).
+//
+// How the weights reach the lanes: entries ride on the lanes, as in gat_row; lane k forms expf(e_k^{hd} - m^{hd}) for every head and
+// writes it to a per-wave LDS tile wt[hd][64]; at entry k a lane reads wt[hd(its slot)][k], one broadcast per head group, and sums
+// l of its slot's head from those values in CSR order: the very floats gat_row's v_readlane hands out, so l and everything after it
+// have the single-head bits.
+// Registers and LDS: a lane keeps a, h and four table rows in flight (as gat_row); the per-head scalars (a0d, m, c_q, M, L) ride on
+// lane hd of one register each and are read by v_readlane; U_s[hd] and U_d[hd] are read from global memory per row (16 KiB: L1);
+// the heads accumulators P^{hd} live in a per-wave LDS slab [heads][NS][64] float4, each lane reading and writing its own entries.
+// LDS per workgroup: 4 heads NS KiB (P) + 8 KiB (wt) + 256 B (M, L): 72.25 KiB at heads = 8, H > 256 -- two workgroups per CU.
+constexpr int kMhMaxHeads = 8;
+
+__host__ __device__ constexpr size_t mhgat_hops_lds_bytes(int heads, int ns) {
+    return ((size_t)kHopsWaves * heads * ns * 64 * 4 + (size_t)kHopsWaves * kMhMaxHeads * 64 + (size_t)kHopsWaves * kMhMaxHeads * 2) * sizeof(float);
+}
+static_assert(2 * mhgat_hops_lds_bytes(kMhMaxHeads, 2) <= 160 * 1024, "two workgroups per CU at heads = 8, H = 512");
+
+__device__ __forceinline__ float lane_get(float v, int g) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), g)); }
+
+// the lanes of ONE wave exchange values through LDS: the wave's LDS operations run in order, the compiler keeps them so
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// gat_row with a softmax per head: hd[s] is the head of the lane's columns in slot s, wt the wave's weight tile [kMhMaxHeads][64].
+template <int NS>
+__device__ __forceinline__ void mhgat_row(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *const (&Tc)[NS],
+                                          int64_t ldt, const int32_t *__restrict__ xrow, const float *__restrict__ a_src0,
+                                          const float *__restrict__ a_dst0, int heads, float slope0, const float4 (&bias)[NS],
+                                          const int (&hd)[NS], float *wt, int r, int lane, float4 (&h)[NS]) {
+    const int n0 = __builtin_amdgcn_readfirstlane(rowptr[r]), n1 = __builtin_amdgcn_readfirstlane(rowptr[r + 1]);
+    const int tr = __builtin_amdgcn_readfirstlane(xrow ? xrow[r] : r);
+    const float adv = lane < heads ? a_dst0[(int64_t)tr * heads + lane] : 0.f;  // lane g: a0d[t(r)][g]
+    float mxv = -INFINITY;                                                     // lane g: the maximum of head g
+    for (int base = n0; base < n1; base += 64) {
+        const float *as = nullptr;
+        if (base + lane < n1) {
+            const int cc = col[base + lane];
+            as = a_src0 + (int64_t)(xrow ? xrow[cc] : cc) * heads;
+        }
+        for (int g = 0; g < heads; ++g) {
+            const float ad = lane_get(adv, g);
+            float e = -INFINITY;
+            if (as) e = lrelu1(as[g] + ad, slope0);
+            e = wave_max(e);
+            if (lane == g) mxv = fmaxf(mxv, e);
+        }
+    }
+    float l[NS];
+    float4 a[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        l[s] = 0.f;
+        a[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int base = n0; base < n1; base += 64) {
+        const int cnt = min(64, n1 - base);
+        int my = 0;
+        wave_lds_order();  // the previous tile has been read
+        if (lane < cnt) {
+            const int cc = col[base + lane];
+            my = xrow ? xrow[cc] : cc;
+        }
+        for (int g = 0; g < heads; ++g) {
+            const float ad = lane_get(adv, g), mx = lane_get(mxv, g);
+            if (lane < cnt) wt[g * 64 + lane] = expf(lrelu1(a_src0[(int64_t)my * heads + g] + ad, slope0) - mx);
+        }
+        wave_lds_order();
+        for (int k = 0; k < cnt; k += 4) {
+            float4 t[4][NS];
+            float wv[4][NS];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {  // always four loads: a missing one re-reads entry k and is not folded
+                const int idx = k + u < cnt ? k + u : k;
+                const int node = __builtin_amdgcn_readlane(my, idx);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    wv[u][s] = wt[hd[s] * 64 + idx];
+                    t[u][s] = *reinterpret_cast<const float4 *>(Tc[s] + (int64_t)node * ldt);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k + u < cnt) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        l[s] += wv[u][s];
+                        a[s].x = fmaf(wv[u][s], t[u][s].x, a[s].x);
+                        a[s].y = fmaf(wv[u][s], t[u][s].y, a[s].y);
+                        a[s].z = fmaf(wv[u][s], t[u][s].z, a[s].z);
+                        a[s].w = fmaf(wv[u][s], t[u][s].w, a[s].w);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const float inv = n1 > n0 ? 1.f / l[s] : 0.f;  // l >= 1: the head's largest score gives expf(0)
+        h[s].x = elu1(fmaf(a[s].x, inv, bias[s].x));
+        h[s].y = elu1(fmaf(a[s].y, inv, bias[s].y));
+        h[s].z = elu1(fmaf(a[s].z, inv, bias[s].z));
+        h[s].w = elu1(fmaf(a[s].w, inv, bias[s].w));
+    }
+}
+
+// One workgroup of four waves per query, every wave on whole rows of H <= 256 NS columns; per head the four online-softmax states
+// meet in LDS in wave order (wave w merges heads w, w + 4).  Dynamic LDS: mhgat_hops_lds_bytes(heads, NS).
+template <int NS>
+__global__ __launch_bounds__(256) void mhgat_hops_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                               const float *__restrict__ T, int64_t ldt, const int32_t *__restrict__ xrow,
+                                                               const float *__restrict__ a_src0, const float *__restrict__ a_dst0,
+                                                               int32_t heads, const float *__restrict__ b0, float slope0,
+                                                               const float *__restrict__ U_src, const float *__restrict__ U_dst,
+                                                               float slope1, const int64_t *__restrict__ rows, int32_t H,
+                                                               float *__restrict__ G, int64_t ldg) {
+    extern __shared__ float4 mh_smem[];
+    float4 *part = mh_smem;                                                              // [waves][heads][NS][64]
+    float *wt_all = reinterpret_cast<float *>(part + (size_t)kHopsWaves * heads * NS * 64);  // [waves][kMhMaxHeads][64]
+    float *ml = wt_all + kHopsWaves * kMhMaxHeads * 64;                                  // [waves][kMhMaxHeads][2]
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = blockIdx.x;
+    const int q = (int)rows[qi];
+    const int e0 = __builtin_amdgcn_readfirstlane(rowptr[q]), e1 = __builtin_amdgcn_readfirstlane(rowptr[q + 1]);
+    const int deg = e1 - e0;
+    const int C0 = H / heads;
+    float4 *Pw = part + (size_t)w * heads * NS * 64 + lane;  // head g, slot s: Pw[(g * NS + s) * 64]
+    float *wt = wt_all + w * kMhMaxHeads * 64;
+    const float *Tc[NS];
+    float4 bias[NS];
+    bool live[NS];
+    int hd[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int c = s * 256 + lane * 4;
+        live[s] = c < H;  // H % 4 == 0: a live lane owns four whole columns
+        Tc[s] = T + (live[s] ? c : 0);
+        hd[s] = live[s] ? c / C0 : 0;
+        bias[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live[s] && b0) bias[s] = make_float4(b0[c], b0[c + 1], b0[c + 2], b0[c + 3]);
+    }
+    for (int g = 0; g < heads * NS; ++g) Pw[g * 64] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float Mv = -INFINITY, Lv = 0.f;  // lane g: the state of head g
+    if (w < deg) {
+        float4 h[NS], u[NS];
+        float cqv = 0.f;  // lane g: U_d[g] . h_q
+        mhgat_row<NS>(rowptr, col, Tc, ldt, xrow, a_src0, a_dst0, heads, slope0, bias, hd, wt, q, lane, h);
+        for (int g = 0; g < heads; ++g) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                u[s] = live[s] ? *reinterpret_cast<const float4 *>(U_dst + (int64_t)g * H + s * 256 + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float c = row_dot<NS>(u, h);
+            if (lane == g) cqv = c;
+        }
+        for (int i = w; i < deg; i += kHopsWaves) {
+            const int j = __builtin_amdgcn_readfirstlane(col[e0 + i]);
+            mhgat_row<NS>(rowptr, col, Tc, ldt, xrow, a_src0, a_dst0, heads, slope0, bias, hd, wt, j, lane, h);
+            for (int g = 0; g < heads; ++g) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+                    u[s] = live[s] ? *reinterpret_cast<const float4 *>(U_src + (int64_t)g * H + s * 256 + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float f = lrelu1(row_dot<NS>(u, h) + lane_get(cqv, g), slope1);
+                const float M = lane_get(Mv, g);
+                float4 *Pg = Pw + g * NS * 64;
+                if (f > M) {  // wave-uniform: every lane holds the butterfly's bits
+                    const float x = expf(M - f);
+                    if (lane == g) {
+                        Lv = fmaf(Lv, x, 1.f);
+                        Mv = f;
+                    }
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        float4 p = Pg[s * 64];
+                        p.x = fmaf(p.x, x, h[s].x);
+                        p.y = fmaf(p.y, x, h[s].y);
+                        p.z = fmaf(p.z, x, h[s].z);
+                        p.w = fmaf(p.w, x, h[s].w);
+                        Pg[s * 64] = p;
+                    }
+                } else {
+                    const float x = expf(f - M);
+                    if (lane == g) Lv += x;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        float4 p = Pg[s * 64];
+                        p.x = fmaf(x, h[s].x, p.x);
+                        p.y = fmaf(x, h[s].y, p.y);
+                        p.z = fmaf(x, h[s].z, p.z);
+                        p.w = fmaf(x, h[s].w, p.w);
+                        Pg[s * 64] = p;
+                    }
+                }
+            }
+        }
+    }
+    if (lane < heads) {
+        ml[(w * kMhMaxHeads + lane) * 2] = Mv;
+        ml[(w * kMhMaxHeads + lane) * 2 + 1] = Lv;
+    }
+    __syncthreads();
+    for (int g = w; g < heads; g += kHopsWaves) {
+        float4 o4[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) o4[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (deg > 0) {
+            float Mx = ml[g * 2];
+#pragma unroll
+            for (int o = 1; o < kHopsWaves; ++o) Mx = fmaxf(Mx, ml[(o * kMhMaxHeads + g) * 2]);
+            float Ls = 0.f;
+#pragma unroll
+            for (int o = 0; o < kHopsWaves; ++o) {
+                const float x = expf(ml[(o * kMhMaxHeads + g) * 2] - Mx);  // a wave without entries: expf(-inf) = 0
+                Ls = fmaf(x, ml[(o * kMhMaxHeads + g) * 2 + 1], Ls);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const float4 r = part[((size_t)(o * heads + g) * NS + s) * 64 + lane];
+                    o4[s].x = fmaf(x, r.x, o4[s].x);
+                    o4[s].y = fmaf(x, r.y, o4[s].y);
+                    o4[s].z = fmaf(x, r.z, o4[s].z);
+                    o4[s].w = fmaf(x, r.w, o4[s].w);
+                }
+            }
+            const float inv = 1.f / Ls;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                o4[s].x *= inv; o4[s].y *= inv; o4[s].z *= inv; o4[s].w *= inv;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            if (live[s]) *reinterpret_cast<float4 *>(G + (int64_t)qi * ldg + (int64_t)g * H + s * 256 + lane * 4) = o4[s];
+    }
+}
+
 // ---- mean aggregation plus a root term (two SAGEConv layers) ----
 //   T     = X [W_l0 ; W_r0]^T                                   [n_table x 2H]: columns [0, H) = X W_l0^T, [H, 2H) = X W_r0^T
 //   h_r   = ELU(sum_{k in row r} val[k] T[t(col[k])][0:H] + T[t(r)][H:2H] + b_l0)           t(r) = xrow ? xrow[r] : r
@@ -571,6 +815,87 @@ __global__ __launch_bounds__(256) void query_tail_kernel(const float *__restrict
     const int nq = min(kTailQ, Q - q0);
 
     tail_tile_z<false>(G, ldg, q0, nq, W1, b1, H, H2, zs, zld, Ws, Gs);
+    __syncthreads();
+
+    tail_head(zs, zld, H2, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
+}
+
+// query_tail_kernel behind mhgat_hops_kernel: G is [Q][heads H] and z's block hd takes block hd of G only,
+//     z[n] = ELU(W1[n, :] . G[q][hd1(n) H : (hd1(n) + 1) H] + b1[n]),   hd1(n) = n / C1, C1 = H2 / heads, C1 % 16 == 0.
+// tail_tile_z's sweep with the A operand chosen per 16-column block: a pass of 256 columns of z walks k ONCE for all the heads it
+// touches -- a k-stage holds W1[n][k0 .. k0 + 32) of the pass's columns and G[.][hd H + k0 .. + 32) of each of its heads, and the
+// block of columns nb reads the rows of its own head -- so a tile costs the (H2 / 256) (H / 32) stages of the single-head tail, not
+// heads times as many.  Every z[n] is still ONE fmaf chain over its block's k ascending on v_mfma_f32_16x16x4_f32: the chain of
+// query_tail_kernel on the block-expanded W1 [H2][heads H] (zeros elsewhere: a product with 0 changes no finite partial sum).
+__host__ __device__ constexpr size_t mhgat_tail_lds_floats(int H2, int C, int heads) {
+    return (size_t)kTailQ * (H2 + 4) + (size_t)kTailCols * kTailLd + (size_t)heads * kTailQ * kTailLd + (size_t)kTailQ * C;
+}
+static_assert(mhgat_tail_lds_floats(512, 48, 8) * sizeof(float) <= kTailLdsMax, "the widest model's tail must fit LDS");
+
+__global__ __launch_bounds__(256) void mhgat_tail_kernel(const float *__restrict__ G, int64_t ldg, int32_t Q, const float *__restrict__ W1,
+                                                         const float *__restrict__ b1, const float *__restrict__ Wl,
+                                                         const float *__restrict__ bl, int32_t H, int32_t H2, int32_t heads, int32_t C,
+                                                         float *__restrict__ out, int64_t ldo, int32_t log_softmax) {
+    extern __shared__ float smem[];
+    const int zld = H2 + 4;
+    float *zs = smem;
+    float *Ws = zs + (size_t)kTailQ * zld;
+    float *Gs = Ws + kTailCols * kTailLd;                // [heads of the pass][16][kTailLd]
+    float *lg = Gs + (size_t)heads * kTailQ * kTailLd;
+    const int q0 = blockIdx.x * kTailQ;
+    const int nq = min(kTailQ, Q - q0);
+    const int C1 = H2 / heads;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r16 = lane & 15, kq = lane >> 4;
+
+    for (int n0 = 0; n0 < H2; n0 += kTailCols) {
+        const int ncols = min(kTailCols, H2 - n0);  // a multiple of 16
+        const int g0 = n0 / C1, ng = (n0 + ncols - 1) / C1 - g0 + 1;  // the heads of this pass
+        f32x4 acc[4];
+        int arow[4];  // the staged row of G that block u's lanes read: its head's slab, row r16
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int nb = (w * 4 + u) * 16;
+            arow[u] = (((nb < ncols ? (n0 + nb) / C1 : g0) - g0) * kTailQ + r16) * kTailLd;
+        }
+        for (int k0 = 0; k0 < H; k0 += kTailKS) {
+            const int k4 = min(kTailKS, H - k0) >> 2;  // float4 per staged row (H % 4 == 0)
+            __syncthreads();                           // the previous stage (and a previous tile's zs) has been consumed
+            for (int idx = tid; idx < ncols * k4; idx += 256) {
+                const int n = idx / k4, kk = idx - n * k4;
+                *reinterpret_cast<float4 *>(Ws + n * kTailLd + kk * 4) =
+                    *reinterpret_cast<const float4 *>(W1 + (int64_t)(n0 + n) * H + k0 + kk * 4);
+            }
+            for (int idx = tid; idx < ng * kTailQ * k4; idx += 256) {
+                const int gr = idx / k4, kk = idx - gr * k4, g = gr / kTailQ, r = gr - g * kTailQ;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);  // rows past Q: computed as zeros, never stored
+                if (r < nq) v = *reinterpret_cast<const float4 *>(G + (int64_t)(q0 + r) * ldg + (int64_t)(g0 + g) * H + k0 + kk * 4);
+                *reinterpret_cast<float4 *>(Gs + gr * kTailLd + kk * 4) = v;
+            }
+            __syncthreads();
+            for (int kk = 0; kk < k4; ++kk) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int nb = (w * 4 + u) * 16;
+                    if (nb < ncols) {  // wave-uniform
+                        const float a = Gs[arow[u] + kk * 4 + kq];
+                        const float b = Ws[(nb + r16) * kTailLd + kk * 4 + kq];
+                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[u], 0, 0, 0);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int nb = (w * 4 + u) * 16;
+            if (nb < ncols) {
+                const int n = n0 + nb + r16;
+                const float bias = b1 ? b1[n] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zs[(kq * 4 + r) * zld + n] = elu1(acc[u][r] + bias);
+            }
+        }
+    }
     __syncthreads();
 
     tail_head(zs, zld, H2, Wl, bl, C, lg, out, ldo, q0, nq, log_softmax);
@@ -1419,6 +1744,58 @@ extern "C" int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q,
     if (const int rc = fitgnn_lds_limit_once((const void *)query_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
     hipLaunchKernelGGL(query_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1, b1,
                        Wl, bl, H, H2, C, out, ldo, log_softmax);
+    return (int)hipGetLastError();
+}
+
+template <int NS>
+static int launch_mhgat_hops(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow, const float *a_src0,
+                             const float *a_dst0, int32_t heads, const float *b0, float slope0, const float *U_src, const float *U_dst,
+                             float slope1, const int64_t *rows, int32_t Q, int32_t H, float *G, int64_t ldg, hipStream_t stream) {
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)mhgat_hops_kernel<NS>, (int)mhgat_hops_lds_bytes(kMhMaxHeads, NS), lds_done))
+        return rc;
+    hipLaunchKernelGGL((mhgat_hops_kernel<NS>), dim3((unsigned)Q), dim3(256), mhgat_hops_lds_bytes(heads, NS), stream, rowptr, col, T, ldt,
+                       xrow, a_src0, a_dst0, heads, b0, slope0, U_src, U_dst, slope1, rows, H, G, ldg);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fitgnn_mhgat_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                             const float *a_src0, const float *a_dst0, int32_t heads, const float *b0, float slope0,
+                                             const float *U_src, const float *U_dst, float slope1, const int64_t *rows, int32_t Q, int32_t H,
+                                             float *G, int64_t ldg, void *stream) {
+    if (Q < 0 || heads < 2 || heads > kMhMaxHeads || H < 8 || H > 512 || (H % heads) != 0 || ((H / heads) % 4) != 0 || ldt < H ||
+        ldg < (int64_t)heads * H)
+        return FITGNN_E_BADARG;
+    if ((ldt % 4) != 0 || (ldg % 4) != 0) return FITGNN_E_ALIGN;
+    if (Q == 0) return 0;
+    if (!rowptr || !col || !T || !a_src0 || !a_dst0 || !U_src || !U_dst || !rows || !G) return FITGNN_E_BADARG;
+    if ((((uintptr_t)T | (uintptr_t)G | (uintptr_t)U_src | (uintptr_t)U_dst) % 16) != 0) return FITGNN_E_ALIGN;
+    const hipStream_t st = (hipStream_t)stream;
+    return H <= 256 ? launch_mhgat_hops<1>(rowptr, col, T, ldt, xrow, a_src0, a_dst0, heads, b0, slope0, U_src, U_dst, slope1, rows, Q, H, G, ldg, st)
+                    : launch_mhgat_hops<2>(rowptr, col, T, ldt, xrow, a_src0, a_dst0, heads, b0, slope0, U_src, U_dst, slope1, rows, Q, H, G, ldg, st);
+}
+
+extern "C" size_t fitgnn_mhgat_query_tail_lds_bytes(int32_t H2, int32_t C, int32_t heads) {
+    if (H2 <= 0 || C <= 0 || heads < 2 || heads > kMhMaxHeads) return 0;
+    return mhgat_tail_lds_floats(H2, C, heads) * sizeof(float);
+}
+
+extern "C" int fitgnn_mhgat_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl,
+                                           const float *bl, int32_t H, int32_t H2, int32_t heads, int32_t C, float *out, int64_t ldo,
+                                           int32_t log_softmax, void *stream) {
+    if (Q < 0 || heads < 2 || heads > kMhMaxHeads || H < 4 || (H % 4) != 0 || H2 < 16 || (H2 % heads) != 0 || ((H2 / heads) % 16) != 0 || C < 1 ||
+        ldg < (int64_t)heads * H || ldo < C)
+        return FITGNN_E_BADARG;
+    if ((ldg % 4) != 0) return FITGNN_E_ALIGN;
+    const size_t lds = fitgnn_mhgat_query_tail_lds_bytes(H2, C, heads);
+    if (lds > kTailLdsMax) return FITGNN_E_BADARG;  // z of the tile does not fit LDS
+    if (Q == 0) return 0;
+    if (!G || !W1 || !Wl || !out) return FITGNN_E_BADARG;
+    if ((((uintptr_t)G | (uintptr_t)W1 | (uintptr_t)Wl | (uintptr_t)out) % 16) != 0) return FITGNN_E_ALIGN;
+    static std::atomic<uint64_t> lds_done{0};
+    if (const int rc = fitgnn_lds_limit_once((const void *)mhgat_tail_kernel, (int)kTailLdsMax, lds_done)) return rc;
+    hipLaunchKernelGGL(mhgat_tail_kernel, dim3((unsigned)((Q + kTailQ - 1) / kTailQ)), dim3(256), lds, (hipStream_t)stream, G, ldg, Q, W1,
+                       b1, Wl, bl, H, H2, heads, C, out, ldo, log_softmax);
     return (int)hipGetLastError();
 }
 

@@ -143,6 +143,10 @@ SIGNATURES = {
                                                    c_i64, ptr]),
     "fitgnn_gcn_query_tail_lds_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_gcn_query_tail_f32": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, ptr, ptr, ptr, c_i32, c_i32, c_i32, ptr, c_i64, c_i32, ptr]),
+    "fitgnn_mhgat_query_gather_f32": (ctypes.c_int, [ptr, ptr, ptr, c_i64, ptr, ptr, ptr, c_i32, ptr, c_f32, ptr, ptr, c_f32, ptr, c_i32, c_i32,
+                                                     ptr, c_i64, ptr]),
+    "fitgnn_mhgat_query_tail_lds_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "fitgnn_mhgat_query_tail_f32": (ctypes.c_int, [ptr, c_i64, c_i32, ptr, ptr, ptr, ptr, c_i32, c_i32, c_i32, c_i32, ptr, c_i64, c_i32, ptr]),
     "fitgnn_gcn_graph_query_hops_lds_bytes": (c_size, [c_i32, c_i32]),
     "fitgnn_gcn_graph_query_hops_f32": (ctypes.c_int, [ptr, ptr, ptr, ptr, c_i64, ptr, ptr, ptr, ptr, ptr, c_i32, c_i32, c_i32, ptr, c_i64, ptr]),
     "fitgnn_gcn_graph_query_tail_lds_bytes": (c_size, [c_i32, c_i32]),

@@ -1247,6 +1247,55 @@ def gat_query_supported(model):
     return shapes is not None and _fits_lds(_lib.lib().fitgnn_gcn_query_tail_lds_bytes(*shapes))
 
 
+def mhgat_query_gather(rowptr, col, T, a_src0, a_dst0, U_src, U_dst, rows, xrow=None, b0=None, slope0=0.2, slope1=0.2, out=None):
+    """G [Q, heads H]: block hd of row i = head hd's layer-1 attention aggregation (before its Linear) of union row rows[i] over
+    layer-0 multi-head GAT rows made from T = X W0^T on the fly (fitgnn_mhgat_query_gather_f32).  a_src0 / a_dst0 [n_table, heads]:
+    the layer-0 score dots per TABLE row and head; U_src / U_dst [heads, H]: W1[block hd]^T att_src1[hd], W1[block hd]^T att_dst1[hd].
+    rows: int64, inside the CSR's rows (the caller checks: the kernel cannot)."""
+    _lib.require_cuda(T)   # T.device places the output and names the stream; the call checks the others
+    Q, H, heads = int(rows.numel()), int(T.shape[1]), int(U_src.shape[0])
+    G = out if out is not None else torch.empty((Q, heads * H), dtype=torch.float32, device=T.device)
+    _lib.call("fitgnn_mhgat_query_gather_f32", rowptr, col, T, T.stride(0), xrow, a_src0, a_dst0, heads, b0, float(slope0), U_src, U_dst,
+              float(slope1), rows, Q, H, G, G.stride(0), _lib.stream_ptr(T.device))
+    return G
+
+
+def mhgat_query_tail(G, W1, b1, Wl, bl, heads, log_softmax=False, out=None):
+    """[Q, C] = Wl ELU(z) + bl per row with the grouped product z[block hd] = W1[block hd] G[block hd] + b1[block hd], log-softmax on
+    request (fitgnn_mhgat_query_tail_f32).  G [Q, heads H], W1 [H2, H], Wl [C, H2] contiguous."""
+    _lib.require_cuda(G)   # G.device places the output and names the stream; the call checks the others
+    Q, H = int(G.shape[0]), int(W1.shape[1])
+    H2, C = int(W1.shape[0]), int(Wl.shape[0])
+    y = out if out is not None else torch.empty((Q, C), dtype=torch.float32, device=G.device)
+    _lib.call("fitgnn_mhgat_query_tail_f32", G, G.stride(0), Q, W1, b1, Wl, bl, H, H2, int(heads), C, y, y.stride(0), 1 if log_softmax else 0,
+              _lib.stream_ptr(G.device))
+    return y
+
+
+def mhgat_query_supported(model):
+    """fitgnn_mhgat_query_gather_f32 and fitgnn_mhgat_query_tail_f32 answer for `model`: exactly two GATConv layers and a head, both
+    layers concat with the same heads in 2..8, layer 0's width H = heads C0 a multiple of 16 and at most 512 with C0 % 4 == 0, layer
+    1's width H2 = heads C1 a multiple of 16 with C1 % 16 == 0, att sizes that match, a head the tail's LDS holds, contiguous float32
+    parameters on the GPU."""
+    from . import nn as fnn
+    convs = list(getattr(model, "conv", ()))
+    lt1 = getattr(model, "lt1", None)
+    if len(convs) != 2 or lt1 is None or not all(type(c) is fnn.GATConv and c.concat for c in convs):
+        return False
+    heads = convs[0].heads
+    if convs[1].heads != heads or not 2 <= heads <= 8:
+        return False
+    W0, W1, Wl = convs[0].lin.weight, convs[1].lin.weight, lt1.weight
+    att = [convs[0].att_src, convs[0].att_dst, convs[1].att_src, convs[1].att_dst]
+    if not _f32_on_gpu([W0, W1, Wl, convs[0].bias, convs[1].bias, lt1.bias] + att):
+        return False
+    H, H2, C = int(W0.shape[0]), int(W1.shape[0]), int(Wl.shape[0])
+    ok = (H % 16 == 0 and H <= 512 and H % heads == 0 and (H // heads) % 4 == 0 and H2 % 16 == 0 and H2 % heads == 0
+          and (H2 // heads) % 16 == 0 and int(W1.shape[1]) == H and int(Wl.shape[1]) == H2
+          and att[0].numel() == H and att[1].numel() == H and att[2].numel() == H2 and att[3].numel() == H2)
+    return ok and _fits_lds(_lib.lib().fitgnn_mhgat_query_tail_lds_bytes(H2, C, heads))
+
+
 def gat_graph_query_hops(rowptr, col, T, a_src0, a_dst0, u_src, u_dst, seg, prow, pptr, max_rows, xrow=None, b0=None, slope0=0.2,
                          slope1=0.2, out=None):
     """G [P, H]: row j = the layer-1 attention aggregation (before its Linear) of view row prow[j] over its graph's layer-0 GAT rows,

@@ -185,6 +185,55 @@ class GATPath(GCNPath):
         return ops.gat_graph_query_max_rows(self.g_width(state, m))
 
 
+class GATHeadsPath(GATPath):
+    """With gat_heads_kernels=True a model of two GATConv(heads, concat) layers with the same heads in 2..8 takes two launches of its
+    own on the node engine (ops.mhgat_query_gather, ops.mhgat_query_tail).  With H = heads C0 and H2 = heads C1 the layers' widths:
+
+        T, a0s, a0d [n_table, heads]                                        the per-head score dots of T, once per set of weights
+        U_s[hd] = W1[block hd]^T att_src1[hd], U_d[hd] likewise [heads, H]   (att . (W1 h)[block hd] = (W1[block hd]^T att) . h)
+        h_r[c]  = ELU(sum_k alpha^{hd(c)}_rk T[t(k)][c] + b0[c])            alpha^{hd}_r. = softmax_k lrelu(a0s[t(k), hd] + a0d[t(r), hd])
+        G_q[hd H + c] = sum_j beta^{hd}_j h_j[c]                            beta^{hd} = softmax_j lrelu(U_s[hd] . h_j + U_d[hd] . h_q)
+        out_q   = Wl ELU(z_q) + bl,  z_q[block hd] = W1[block hd] G_q[block hd] + b1[block hd]      (sum_j beta^{hd}_j = 1)
+
+    Every head weighs the same rows h_j, so G is heads times as wide as h and the tail's first product is grouped.  The graph engine
+    has no multi-head path (supported(m, graph=True) is False: it answers such a model with its forward).  Opt-in, as the other
+    kinds: tools/query_latency.py --layer GATConv --heads measures it against the per-subgraph forward."""
+    name, flag, csr_mode = "gat_heads", "gat_heads_kernels", "gat"
+
+    def key_params(self, m):
+        return GATPath.key_params(self, m) + [x for c in m.conv for x in (getattr(c, "heads", None), getattr(c, "concat", None))]
+
+    def supported(self, m, graph):
+        return False if graph else ops.mhgat_query_supported(m)
+
+    def prepare(self, X, m):
+        """(T, a0s, a0d, U_s, U_d): a0s / a0d [n_table, heads] = the per-head dots of T with att0 (fitgnn_gat_heads_scores_f32) and
+        U[hd] = W1[block hd]^T att1[hd] [heads, H], formed in float64 and rounded once."""
+        from . import _lib
+        W0, as0, ad0, W1, as1, ad1 = self.weights(m)
+        heads = m.conv[0].heads
+        T = _product(X, W0, m)
+        n, H = T.shape
+        a0s = torch.empty((n, heads), dtype=torch.float32, device=T.device)
+        a0d = torch.empty((n, heads), dtype=torch.float32, device=T.device)
+        as0, ad0 = as0.detach().reshape(-1).contiguous(), ad0.detach().reshape(-1).contiguous()
+        _lib.call("fitgnn_gat_heads_scores_f32", T, T.stride(0), n, heads, H // heads, as0, ad0, a0s, a0d, _lib.stream_ptr(T.device))
+        W1b = W1.detach().double().view(heads, -1, H)                        # [heads, C1, H]
+        U_s = torch.einsum("gc,gch->gh", as1.detach().double().view(heads, -1), W1b).float().contiguous()
+        U_d = torch.einsum("gc,gch->gh", ad1.detach().double().view(heads, -1), W1b).float().contiguous()
+        return (T, a0s, a0d, U_s, U_d)
+
+    def rows_hops(self, f, state, m, rows, xrow=None, out=None):
+        return ops.mhgat_query_gather(f.rowptr, f.col, *state, rows, xrow=xrow, b0=m.conv[0].bias, slope0=m.conv[0].negative_slope,
+                                      slope1=m.conv[1].negative_slope, out=out)
+
+    def g_width(self, state, m):
+        return int(state[0].shape[1]) * int(state[3].shape[0])
+
+    def node_tail(self, G, state, m, log_softmax):
+        return ops.mhgat_query_tail(G, *self._layer1(state, m), m.lt1.weight, m.lt1.bias, int(state[3].shape[0]), log_softmax=log_softmax)
+
+
 class SAGEPath(GCNPath):
     """With sage_kernels=True a model of two SAGEConv layers takes two launches as well: its layer is a gather plus a root term, over
     the union's mean CSR (no self loops added, val = 1 / max(deg, 1): what nn.SAGEConv.forward looks up), with t(r) the table row of
@@ -314,7 +363,7 @@ class GINPath(GCNPath):
         return ops.gin_graph_query_tail(G, pptr, *self._layer1(state, m), m.lt1.weight, m.lt1.bias, pool=pool, softmax=softmax)
 
 
-PATHS = (GCNPath(), GATPath(), SAGEPath(), GINPath())   # in precedence order
+PATHS = (GCNPath(), GATPath(), GATHeadsPath(), SAGEPath(), GINPath())   # in precedence order
 
 
 class _Engine:
@@ -322,9 +371,10 @@ class _Engine:
     kind's two `supported` it asks), calls _setup and defines _operand() -> (X, xrow)."""
 
     def _setup(self, model, flags, edge_index, csrs):
-        """flags: (gat_kernels, sage_kernels, gin_kernels); edge_index: what csr_for is keyed on; csrs: mode -> the CSRs at hand."""
+        """flags: (gat_kernels, sage_kernels, gin_kernels, gat_heads_kernels); edge_index: what csr_for is keyed on; csrs: mode -> the
+        CSRs at hand."""
         self.model = model
-        self.gat_kernels, self.sage_kernels, self.gin_kernels = (bool(f) for f in flags)
+        self.gat_kernels, self.sage_kernels, self.gin_kernels, self.gat_heads_kernels = (bool(f) for f in flags)
         self._edge_index, self._csrs = edge_index, dict(csrs)
         self._fused = None      # (key of the model's layers and parameters, the kind of PATHS that answers or None)
         self._state = None      # ([(tensor, version)] of the kind's weights(model), its prepared state: T first)
@@ -342,7 +392,7 @@ class _Engine:
         return self._fused[1]
 
     def _kind(self):
-        """The name of path(): "gcn", "gat", "sage", "gin" or None."""
+        """The name of path(): "gcn", "gat", "gat_heads", "sage", "gin" or None."""
         return getattr(self.path(), "name", None)
 
     @property
@@ -389,10 +439,11 @@ class QueryEngine(_Engine):
     not measured yet); it changes nothing for any other model.  sage_kernels: the same switch for a model of two SAGEConv layers
     (the mean-aggregation query kernel), off by default for the same reason.  gin_kernels: the same switch for a model of two GINConv
     layers with the reference's two-Linear ReLU MLP (the hops kernel with its dense product and the two-stage tail), off by default
-    for the same reason."""
+    for the same reason.  gat_heads_kernels: the same switch for a model of two GATConv(heads, concat) layers with the same heads in
+    2..8 (the per-head attention query kernel and its grouped tail); gat_kernels alone leaves such a model to its forward."""
     graph_level = False
 
-    def __init__(self, model, batch, gat_kernels=False, sage_kernels=False, gin_kernels=False):
+    def __init__(self, model, batch, gat_kernels=False, sage_kernels=False, gin_kernels=False, gat_heads_kernels=False):
         self.batch = batch
         self.log_softmax = not isinstance(model, _regressors())
         g = batch.graph
@@ -407,7 +458,8 @@ class QueryEngine(_Engine):
         self._core_row = torch.from_numpy(table).to(dev)
         self._subgraphs = {}    # the per-subgraph forward's inputs: s -> (x, edge_index, first row)
         # the GAT kernel ignores val and both modes have one pattern: no second CSR is built
-        self._setup(model, (gat_kernels, sage_kernels, gin_kernels), batch.edge_index, {m: g for m in (GCNPath.csr_mode, GATPath.csr_mode)})
+        self._setup(model, (gat_kernels, sage_kernels, gin_kernels, gat_heads_kernels), batch.edge_index,
+                    {m: g for m in (GCNPath.csr_mode, GATPath.csr_mode)})
 
     def _operand(self):
         b = self.batch
@@ -528,7 +580,7 @@ class GraphQueryEngine(_Engine):
             pp = np.searchsorted(prow.cpu().numpy(), ptr, side="left").astype(np.int64)
         self._prow, self._pp = prow, pp
         self._prow_host = prow.cpu().numpy()
-        self._setup(model, (gat_kernels, sage_kernels, gin_kernels), self._whole["edge_index"], {GCNPath.csr_mode: self.graph})
+        self._setup(model, (gat_kernels, sage_kernels, gin_kernels, False), self._whole["edge_index"], {GCNPath.csr_mode: self.graph})
 
     def _operand(self):
         return self.x, None

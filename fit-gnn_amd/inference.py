@@ -12,7 +12,9 @@ Extra flags: --data_root, --device, --layer_name (the reference hard-codes GCN i
 (opt-in: each sampled query answered by fitgnn_amd.serve.QueryEngine.predict_rows -- each sampled graph of the graph-level tasks by
 fitgnn_amd.serve.GraphQueryEngine.predict -- inside the same timing bracket; same CSV row),
 --query_attention (with --query_engine: a two-layer GATConv model is answered by the attention query kernel; on graph_cls / graph_reg
-by the GAT graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_sage (with
+by the GAT graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_attention_heads (with
+--query_engine on the node tasks: a two-layer GATConv model of 2..8 heads is answered by the per-head attention query kernel and its
+grouped tail), --query_sage (with
 --query_engine: a two-layer SAGEConv model is answered by the mean-aggregation query kernel; on graph_cls / graph_reg by the SAGE
 graph-query kernel in front of the graph tail, the baseline under --baseline included), --query_gin (with --query_engine: a
 two-layer GINConv model is answered by the GIN query kernels; on graph_cls / graph_reg by the GIN graph-query kernels, the baseline
@@ -88,6 +90,10 @@ def build_parser():
                         "(QueryEngine(gat_kernels=True)) instead of the per-subgraph forward; graph_cls / graph_reg: by the GAT graph-query "
                         "kernel (GraphQueryEngine(gat_kernels=True): every attention row of a graph and its two score dots formed once, in "
                         "LDS) instead of the model's own forward, the baseline under --baseline included; ignored without --query_engine")
+    p.add_argument('--query_attention_heads', action='store_true',
+                   help="with --query_engine, node_cls / node_reg: a --layer_name GATConv --heads 2..8 model of two layers is answered by the "
+                        "per-head attention query kernel and its grouped tail (QueryEngine(gat_heads_kernels=True)) instead of the "
+                        "per-subgraph forward; ignored without --query_engine, for other layers and on graph_cls / graph_reg")
     p.add_argument('--query_sage', action='store_true',
                    help="with --query_engine: a --layer_name SAGEConv model of two layers is answered by the mean-aggregation query kernel "
                         "(QueryEngine(sage_kernels=True)) instead of the per-subgraph forward; graph_cls / graph_reg: by the SAGE graph-query "
@@ -245,7 +251,8 @@ def main(argv=None):
     engine = None
     if args.query_engine:   # built outside the timed region, as the per-subgraph CSR is below; T = X W0^T is made here too
         from fitgnn_amd.serve import QueryEngine
-        engine = QueryEngine(model, batch, gat_kernels=args.query_attention, sage_kernels=args.query_sage, gin_kernels=args.query_gin)
+        engine = QueryEngine(model, batch, gat_kernels=args.query_attention, sage_kernels=args.query_sage, gin_kernels=args.query_gin,
+                             gat_heads_kernels=args.query_attention_heads)
         if engine.fused:
             engine.refresh()
         else:

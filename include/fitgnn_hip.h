@@ -709,6 +709,45 @@ size_t fitgnn_gcn_query_tail_lds_bytes(int32_t H2, int32_t C);
 int fitgnn_gcn_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl, const float *bl,
                               int32_t H, int32_t H2, int32_t C, float *out, int64_t ldo, int32_t log_softmax, void *stream);
 
+/* fitgnn_gat_query_gather_f32 for two GATConv layers with the same number of heads (2 <= heads <= 8, concat): G[i] [heads * H] for
+ * q = rows[i].  With H = heads * C0 layer 0's width, hd(c) = c / C0 the head of column c and t(r) = xrow ? xrow[r] : r:
+ *   h_r[c]          = ELU(sum_k alpha^{hd(c)}_rk T[t(k)][c] + b0[c]),
+ *                     alpha^{hd}_r. = softmax over CSR row r of LeakyReLU(a_src0[t(k)][hd] + a_dst0[t(r)][hd], slope0)
+ *   G[i][hd H + c]  = sum_j beta^{hd}_j h_j[c],
+ *                     beta^{hd}     = softmax over CSR row q of LeakyReLU(U_src[hd] . h_j + U_dst[hd] . h_q, slope1)   (dots over ALL of H)
+ * a_src0 / a_dst0 [n_table x heads] are the per-head layer-0 score dots per TABLE row (fitgnn_gat_heads_scores_f32 on T);
+ * U_src[hd] = W1[hd C1 : (hd + 1) C1, :]^T att_src1[hd] and U_dst likewise, [heads x H] contiguous: att . (W1 h)[block hd] =
+ * (W1[block hd]^T att) . h, and sum_j beta^{hd}_j = 1, so fitgnn_mhgat_query_tail_f32's grouped product W1[block hd] G^{hd} + b1[block
+ * hd] is conv1's output block.  Every head weighs the same rows h_j differently: G is heads times as wide as h.
+ * One workgroup of four waves per query, a wave on whole rows; the order is fitgnn_gat_query_gather_f32's, applied per head (entry i
+ * of row q to wave i % 4, each wave folding in ascending i, the waves merged per head in wave order, the same per-lane dot chain and
+ * butterfly, layer 0's CSR-order fmaf chain with l summed in CSR order and one 1 / l; csrc/query.hip): when all heads share their
+ * layer-0 scores, block hd of G is bit-equal to fitgnn_gat_query_gather_f32 with (a_src0[:, 0], a_dst0[:, 0], U_src[hd], U_dst[hd]).
+ * No atomics: two launches give the same bits.  A row without entries gives h_r = ELU(b0), a query without entries zeros over all
+ * heads * H.  xrow, b0 may be NULL.  rows (int64, values in [0, n_rows)) may repeat and need no order.  Writes
+ * G[0..Q) x [0..heads * H) only.  Requires 2 <= heads <= 8, 8 <= H <= 512, H % heads == 0, (H / heads) % 4 == 0, ldt >= H,
+ * ldg >= heads * H and no NULL pointer besides xrow, b0 when Q > 0 (FITGNN_E_BADARG); ldt, ldg multiples of 4 and T, G, U_src, U_dst
+ * 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+int fitgnn_mhgat_query_gather_f32(const int32_t *rowptr, const int32_t *col, const float *T, int64_t ldt, const int32_t *xrow,
+                                  const float *a_src0, const float *a_dst0, int32_t heads, const float *b0, float slope0,
+                                  const float *U_src, const float *U_dst, float slope1, const int64_t *rows, int32_t Q, int32_t H, float *G,
+                                  int64_t ldg, void *stream);
+
+/* fitgnn_gcn_query_tail_f32 with the grouped product behind fitgnn_mhgat_query_gather_f32: G [Q x heads * H], W1 [H2 x H] contiguous,
+ * C1 = H2 / heads, hd1(n) = n / C1:
+ *   z[n] = ELU(W1[n, :] . G[i][hd1(n) H : (hd1(n) + 1) H] + b1[n]),   out[i] = Wl z + bl  (+ log-softmax when log_softmax != 0).
+ * Every z[n] is ONE fmaf chain over its block's k ascending on the exact-fp32 MFMA (no split-k): the bits of
+ * fitgnn_gcn_query_tail_f32 on the same G with K = heads * H and the block-expanded W1 [H2 x heads * H] (row n holds W1[n, :] at
+ * columns hd1(n) H .., zeros elsewhere), for finite G.  A pass of 256 columns of z walks k once for all the heads it touches (a
+ * k-stage holds the rows of G of each of them), so a tile takes the k-stages of the single-head tail, not heads times as many.  The
+ * head and the log-softmax are that function's.  b1, bl may be NULL.  Requires 2 <= heads <= 8, H % 4 == 0, H2 % heads == 0,
+ * (H2 / heads) % 16 == 0, C >= 1, ldg >= heads * H, ldo >= C and fitgnn_mhgat_query_tail_lds_bytes(H2, C, heads) <= 160 KiB (its
+ * dynamic LDS: the GCN tail's plus 16 x 36 floats per head past the first; 0 for sizes it refuses) (FITGNN_E_BADARG); ldg a multiple
+ * of 4 and G, W1, Wl, out 16-byte aligned (FITGNN_E_ALIGN).  Q == 0 returns 0 without a launch. */
+size_t fitgnn_mhgat_query_tail_lds_bytes(int32_t H2, int32_t C, int32_t heads);
+int fitgnn_mhgat_query_tail_f32(const float *G, int64_t ldg, int32_t Q, const float *W1, const float *b1, const float *Wl, const float *bl,
+                                int32_t H, int32_t H2, int32_t heads, int32_t C, float *out, int64_t ldo, int32_t log_softmax, void *stream);
+
 /* Graph-level queries (inference.py:288-538 of the reference: graph_cls / graph_reg, the model on ONE graph of the set): two
  * GCNConv layers, a pool over the graph's rows, the head -- two launches for any number of graphs.  Both take the GCN-normalised CSR
  * (rowptr, col, val) of a whole view, all rows of all graphs, block-diagonal per graph.

@@ -5,6 +5,8 @@
     python tools/query_latency.py --workload S-pubmed [--layer GATConv | SAGEConv | GINConv] [--hidden 512] [--samples 256] [--rounds 5] [--out FILE]
 
 --layer GATConv: a two-layer GAT model through QueryEngine(gat_kernels=True) (fitgnn_gat_query_gather_f32 and the same tail).
+--layer GATConv --heads N (2..8): the model with N attention heads per layer through QueryEngine(gat_heads_kernels=True)
+(fitgnn_mhgat_query_gather_f32 and fitgnn_mhgat_query_tail_f32); writes profiles/query_latency_node_GATConv_heads<N>.json.
 --layer SAGEConv: a two-layer SAGE model through QueryEngine(sage_kernels=True) (fitgnn_sage_query_gather_f32 over the mean CSR and the
 same tail with K = 2H).
 --layer GINConv: a two-layer GIN model through QueryEngine(gin_kernels=True) (fitgnn_gin_query_hops_f32 over the sum CSR, with a dense
@@ -77,6 +79,7 @@ def main():
     ap.add_argument("--workload", default="S-pubmed")
     ap.add_argument("--layer", default="GCNConv", choices=["GCNConv", "GATConv", "SAGEConv", "GINConv"])
     ap.add_argument("--hidden", type=int, default=512)
+    ap.add_argument("--heads", type=int, default=1, help="--layer GATConv --task node: attention heads per layer (hidden // heads wide each)")
     ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4096)
@@ -85,6 +88,8 @@ def main():
     ap.add_argument("--n_graphs", type=int, default=2000)
     ap.add_argument("--view", default="gs", choices=["gs", "gc", "orig"])
     a = ap.parse_args()
+    if a.heads != 1 and (a.layer != "GATConv" or a.task != "node"):
+        ap.error("--heads goes with --layer GATConv --task node")
     if a.task != "node":
         return graph_main(a)
 
@@ -105,15 +110,16 @@ def main():
                                 torch.from_numpy(np.ascontiguousarray(wl["assign"])).to(dev), wl["n_clusters"])
     batch = workloads.batch_from_subgraphs(a.workload, sub, dev)
     del sub, wl
-    margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=F, hidden=a.hidden, num_classes=C)
+    margs = argparse.Namespace(num_layers1=2, layer_name=a.layer, num_features=F, hidden=a.hidden, num_classes=C, heads=a.heads)
     torch.manual_seed(2)
     model = network.Classify_node(margs).to(dev).eval()
     gat = a.layer == "GATConv"
+    mh = gat and a.heads > 1
     sage = a.layer == "SAGEConv"
     gin = a.layer == "GINConv"
-    engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage, gin_kernels=gin)
+    engine = serve.QueryEngine(model, batch, gat_kernels=gat, sage_kernels=sage, gin_kernels=gin, gat_heads_kernels=mh)
     path = engine.path()
-    assert path is not None and path.name == a.layer[:-4].lower()
+    assert path is not None and path.name == ("gat_heads" if mh else a.layer[:-4].lower())
     t0 = time.time()
     engine.refresh()
     torch.cuda.synchronize()
@@ -213,7 +219,7 @@ def main():
     sa, s1, s2 = _stats(ta), _stats(tb1), _stats(tb2)
     base = min(s1["median_us"], s2["median_us"])
     spread = abs(s1["median_us"] - s2["median_us"])
-    res = dict(workload=a.workload, layer=a.layer, hidden=a.hidden, classes=C, union_rows=int(batch.n_rows), nnz=int(batch.nnz), subgraphs=int(len(ptr) - 1),
+    res = dict(workload=a.workload, layer=a.layer, heads=a.heads, hidden=a.hidden, classes=C, union_rows=int(batch.n_rows), nnz=int(batch.nnz), subgraphs=int(len(ptr) - 1),
                samples=int(len(rows)), rounds=a.rounds, device=torch.cuda.get_device_name(0),
                table=dict(rows=int(T.shape[0]), bytes=engine.table_bytes, build_s=round(t_table, 4)),
                engine_single=sa, subgraph_forward_first=s1, subgraph_forward_second=s2, per_round=per_round,
@@ -224,7 +230,8 @@ def main():
                                  gather_kernel_s=round(t_gather, 6), gather_table_rows=table_rows, gather_bytes=gather_bytes,
                                  gather_GBps=round(gather_bytes / t_gather / 1e9, 1),
                                  stream_copy_GBps=round(2 * 4 * n / t_copy / 1e9, 1)))
-    out = a.out or os.path.join(ROOT, "profiles", f"query_latency_{a.workload}{'_' + a.layer if gat or sage or gin else ''}.json")
+    name = f"query_latency_node_GATConv_heads{a.heads}.json" if mh else f"query_latency_{a.workload}{'_' + a.layer if gat or sage or gin else ''}.json"
+    out = a.out or os.path.join(ROOT, "profiles", name)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
