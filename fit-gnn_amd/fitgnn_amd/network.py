@@ -13,6 +13,8 @@ Each layer is conv -> ELU -> dropout(p=0.5) (network.py:31-33); GCN layers run t
 SpMM with a fused epilogue.  The *_gs classes evaluate all subgraphs of a batch as ONE block-diagonal
 pass instead of the reference's Python double loop (identical arithmetic: subgraphs share no edges).
 """
+import collections
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -49,6 +51,32 @@ def _one_head_gat(conv):
     return isinstance(conv, fnn.GATConv) and conv.heads == 1
 
 
+# How a hidden layer runs conv -> ELU -> dropout (network.py:31-33) ...
+_GCN = "gcn"                 # ops.FusedGCNLayer (GCNConv.forward_elu_dropout)
+_GCN_NARROW = "gcn narrow"   # ops.FusedGCNLayerAggregatedInput: a narrow static input (QM9's 11 atom features), A_hat x formed once
+_GCN_TABLE = "gcn table"     # ops.FusedGCNLayerDedup: layer 0 on the de-duplicated feature table
+_GAT_TABLE = "gat table"     # a one-head GATConv.forward_elu_dropout on the table
+_GAT = "gat"                 # GATConv.forward_elu_dropout: one head fused (ops.GATAggregate), more heads as torch operations
+_PLAIN = "plain"             # conv, F.elu and F.dropout as they stand, for any layer class; an injected mask is ignored
+_GCN_KINDS = (_GCN, _GCN_NARROW, _GCN_TABLE)
+# ... and how the stack ends
+_EMBED = "embed"                  # with its last layer: the embedding is the result
+_HEAD = "head"                    # head(embedding)
+_GCN_HEAD = "gcn + head"          # ops.FusedGCNLayerHead
+_GCN_LOSS_ROWS = "gcn loss rows"  # ops.FusedGCNLastLayerRows
+_GAT_LOSS_ROWS = "gat loss rows"  # ops.FusedGATLastLayerRows
+_GCN_POOLED_ROWS = "gcn pooled rows"   # ops.FusedGCNLayerRows
+_GCN_OUT_ROWS = "gcn out rows"    # (A_hat[rows] h) W^T, activation and head as torch operations
+
+# What one forward runs, decided before any launch.  hidden: (kind, linked) per hidden layer -- every layer under _EMBED / _HEAD, all
+# but the last otherwise; linked: the layer shares an ops.EpilogueLink with its one consumer (the next layer or the tail).  gather: a
+# feature table is gathered to the union rows first (no layer 0 that reads it through the row index).
+# embed_rules: the hidden layers run as embed() runs them -- a narrow-input first GCN layer as _GCN_NARROW, an attention layer as _GAT
+# (its injected mask honoured).  Without (under a GCN tail with the head fused in, and under out_rows) a narrow first layer is a plain
+# _GCN and an attention layer off the table is _PLAIN (its mask ignored): kept as found, wanted or not.
+_Plan = collections.namedtuple("_Plan", "hidden tail gather embed_rules")
+
+
 class _Base(nn.Module):
     out_dim_from_classes = True
 
@@ -79,92 +107,127 @@ class _Base(nn.Module):
         """The dropout mask injected for layer i (tests), else None."""
         return self._inject_masks[i] if self._inject_masks is not None else None
 
-    def _first_layer_dedup(self, x_table, edge_index, x_index, link_out=None, gat_link=None):
-        """Layer 0 on a de-duplicated feature table (x_index: ops.RowIndex mapping union rows to table rows).
-        gat_link: the link an attention layer records for an aggregate-first attention layer right behind it (FusedGATLastLayerRows)."""
-        conv, mask = self.conv[0], self._mask(0)
-        if _one_head_gat(conv) and x_table.is_cuda and link_out is None:   # (a multi-head layer: None, the caller gathers the rows)
-            return conv.forward_elu_dropout(x_table, edge_index, p=self.dropout_p, training=self.training, mask=mask, x_index=x_index,
-                                            link_out=gat_link)
-        if not (isinstance(conv, fnn.GCNConv) and x_table.is_cuda):
-            return None
-        g = conv.graph(edge_index, int(x_index.index.numel()))
-        cfg = self.op_config
-        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
-        return ops.FusedGCNLayerDedup.apply(x_table.float(), conv.lin.weight, conv.bias, g, x_index, float(self.dropout_p),
-                                            bool(self.training), seed, mask, link_out, cfg)
+    def _dropout(self, i):
+        """(p, training, seed, mask) of layer i's dropout as the fused nodes take them; draws the layer's seed (ops.dropout_seed)."""
+        mask = self._mask(i)
+        return float(self.dropout_p), bool(self.training), ops.dropout_seed(self.op_config, self.training, self.dropout_p, mask), mask
+
+    def _plan(self, x, x_index=None, out_rows=None, loss_rows=None, pooled_rows=None, head=True):
+        """The _Plan of one forward over input x (x_index: x is a table), from what is known before any launch.  head=False: stop at
+        the embedding (embed(); with pooled_rows, the last layer on those rows where that applies, else tail _EMBED)."""
+        L, cfg, cuda, conv = self.num_layers, self.op_config, x.is_cuda, self.conv
+        top = conv[L - 1] if L > 0 else None
+
+        def head_fusable():
+            return ops.head_fusable(self.lt1.in_features, self.lt1.out_features)
+
+        def on_loss_rows():   # the last layer's dense part and the head on the loss rows alone: the hint, and shapes the row kernels take
+            W = top.lin.weight
+            return (loss_rows is not None and cfg.last_layer_on_loss_rows and loss_rows.numel() > 0 and W.shape[0] % 4 == 0
+                    and W.shape[1] % 4 == 0 and ops.head_rows_supported(x.new_empty((1, W.shape[0])), self.lt1.weight))
+
+        if out_rows is not None:
+            if not isinstance(top, fnn.GCNConv):
+                raise NotImplementedError("out_rows needs a GCNConv last layer")
+            tail = _GCN_OUT_ROWS
+        elif pooled_rows is not None:
+            ok = (cfg.pooled_rows_last_layer and cuda and isinstance(top, fnn.GCNConv) and pooled_rows.dtype == torch.int64
+                  and pooled_rows.numel() > 0 and top.lin.weight.shape[0] % 4 == 0 and all(isinstance(c, (fnn.GCNConv, fnn.GATConv)) for c in conv))
+            tail = _GCN_POOLED_ROWS if ok else _EMBED
+        elif not head:
+            tail = _EMBED
+        elif cuda and isinstance(top, fnn.GCNConv) and head_fusable():
+            tail = _GCN_LOSS_ROWS if on_loss_rows() else _GCN_HEAD
+        elif (cuda and _one_head_gat(top) and on_loss_rows() and head_fusable()
+                and (L == 1 or isinstance(conv[L - 2], (fnn.GATConv, fnn.GCNConv)))):
+            tail = _GAT_LOSS_ROWS
+        else:
+            tail = _HEAD
+        embed_rules = tail not in (_GCN_HEAD, _GCN_LOSS_ROWS, _GCN_OUT_ROWS)
+        table = x_index is not None and L > 1   # (a lone layer is the tail or reads gathered rows)
+
+        def kind(i):
+            c = conv[i]
+            if not cuda:
+                return _PLAIN
+            if isinstance(c, fnn.GCNConv):
+                if i == 0 and table:
+                    return _GCN_TABLE
+                return _GCN_NARROW if (i == 0 and embed_rules and ops.narrow_input_supported(x, c.lin.weight, cfg)) else _GCN
+            if i == 0 and table and _one_head_gat(c) and (tail == _GCN_OUT_ROWS or not isinstance(conv[1], fnn.GCNConv)):
+                return _GAT_TABLE
+            return _GAT if (embed_rules and isinstance(c, fnn.GATConv)) else _PLAIN
+
+        def linked(a, b, i):
+            """Layer i of kind a and its consumer of kind b share a link: consecutive fused GCN layers (the backward GEMM dH @ W of layer
+            i+1 applies layer i's ELU' / dropout' in its epilogue), and a one-head attention layer right below the aggregate-first
+            attention tail (which hands them to that layer's adjoint aggregation).  None under out_rows."""
+            if tail == _GCN_OUT_ROWS:
+                return False
+            if a in _GCN_KINDS:   # (the pooled-rows tail: only from a 4-column aligned layer below)
+                return b in (_GCN, _GCN_HEAD, _GCN_LOSS_ROWS) or (b == _GCN_POOLED_ROWS and top.lin.weight.shape[1] % 4 == 0)
+            return a in (_GAT, _GAT_TABLE) and b == _GAT_LOSS_ROWS and _one_head_gat(conv[i])
+
+        kinds = [kind(i) for i in range(L if tail in (_EMBED, _HEAD) else L - 1)]
+        hidden = tuple((a, linked(a, b, i)) for i, (a, b) in enumerate(zip(kinds, kinds[1:] + [tail])))
+        gather = x_index is not None and not (kinds and kinds[0] in (_GCN_TABLE, _GAT_TABLE))
+        return _Plan(hidden, tail, gather, embed_rules)
+
+    def _hidden(self, plan, x, edge_index, x_index=None, first=0, last=None, link=None):
+        """The layer loop: conv -> ELU -> dropout for the hidden layers first .. last - 1 of `plan` (default: all), seeds drawn in layer
+        order.  Returns the result and the link its last layer recorded for the tail (None: the tail takes the plain gradient)."""
+        cfg, p, training = self.op_config, self.dropout_p, self.training
+        x = x.float()
+        if plan.gather:
+            x = x.index_select(0, x_index.index.long())  # materialise the union rows
+        for i in range(first, len(plan.hidden) if last is None else last):
+            conv, (how, linked) = self.conv[i], plan.hidden[i]
+            nxt = ops.EpilogueLink() if linked else None
+            if how == _GCN:
+                x = conv.forward_elu_dropout(x, edge_index, p=p, training=training, mask=self._mask(i), link_in=link, link_out=nxt)
+            elif how == _GCN_NARROW:
+                ax = ops.aggregated_input(conv.graph(edge_index, x.shape[0]), x, cfg)
+                x = ops.FusedGCNLayerAggregatedInput.apply(ax, conv.lin.weight, conv.bias, *self._dropout(i), nxt, cfg)
+            elif how == _GCN_TABLE:
+                g = conv.graph(edge_index, int(x_index.index.numel()))
+                x = ops.FusedGCNLayerDedup.apply(x, conv.lin.weight, conv.bias, g, x_index, *self._dropout(i), nxt, cfg)
+            elif how in (_GAT, _GAT_TABLE):
+                x = conv.forward_elu_dropout(x, edge_index, p=p, training=training, mask=self._mask(i),
+                                             x_index=x_index if how == _GAT_TABLE else None, link_out=nxt)
+            else:
+                x = F.dropout(F.elu(conv(x, edge_index)), p=p, training=training)
+            link = nxt
+        return x, link
 
     def prepare_static(self, x, edge_index, pooled_rows=None):
         """Form ahead of time what the layers keep per (graph, input) -- A_hat x of a narrow static input (ops.aggregated_input), the
         compact positions of the pooled rows (ops.FusedGCNLayerRows' backward) -- e.g. before the steps over a
         set of static batches are captured in hipGraphs: made lazily inside a step they would be captured and replayed with it."""
-        conv = self.conv[0] if self.num_layers > 0 else None
-        if (isinstance(conv, fnn.GCNConv) and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
-                and ops.narrow_input_supported(x, conv.lin.weight, self.op_config)):
-            ops.aggregated_input(conv.graph(edge_index, x.shape[0]), x, self.op_config)
-        last = self.conv[self.num_layers - 1] if self.num_layers > 0 else None
-        if (pooled_rows is not None and torch.is_tensor(x) and x.is_cuda and isinstance(last, fnn.GCNConv) and self.op_config.pooled_rows_last_layer
-                and pooled_rows.dtype == torch.int64 and pooled_rows.numel() > 0):
-            ops._compact_positions(last.graph(edge_index, x.shape[0]), pooled_rows)
+        if not (torch.is_tensor(x) and x.is_cuda):
+            return
+        # (A_hat x is kept per input TENSOR: an input of another dtype is converted anew every step, nothing to warm)
+        hidden = self._plan(x, head=False).hidden
+        if x.dtype == torch.float32 and hidden and hidden[0][0] == _GCN_NARROW:
+            ops.aggregated_input(self.conv[0].graph(edge_index, x.shape[0]), x, self.op_config)
+        if pooled_rows is not None and self._plan(x, pooled_rows=pooled_rows, head=False).tail == _GCN_POOLED_ROWS:
+            ops.compact_positions(self.conv[self.num_layers - 1].graph(edge_index, x.shape[0]), pooled_rows)
 
-    def embed(self, x, edge_index, x_index=None, first=0, link=None, last=None, return_link=False, tail_link=None):
+    def embed(self, x, edge_index, x_index=None, first=0, link=None, last=None):
         """conv -> ELU -> dropout, layers first .. last - 1 (default: all; network.py:29-33).  link: the EpilogueLink recorded by the
-        layer that produced x (consecutive fused GCN layers are linked: see ops.EpilogueLink; the stack is strictly sequential).
-        return_link: also return the link the last evaluated layer recorded for its ONE consumer (None when it recorded none).
-        tail_link: the link the LAST evaluated layer records when it is an attention layer (its consumer: FusedGATLastLayerRows)."""
-        x = x.float()
-        for i in range(first, self.num_layers if last is None else last):
-            conv = self.conv[i]
-            if isinstance(conv, fnn.GCNConv) and x.is_cuda:
-                mask = self._mask(i)
-                nxt = ops.EpilogueLink() if i + 1 < self.num_layers else None   # the last output goes to lt1: plain gradient
-                if i == 0 and link is None and ops.narrow_input_supported(x, conv.lin.weight, self.op_config):
-                    # a narrow static input (QM9's 11 atom features): aggregate first, A_hat x formed once per (graph, input)
-                    cfg = self.op_config
-                    ax = ops.aggregated_input(conv.graph(edge_index, x.shape[0]), x, cfg)
-                    seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
-                    x = ops.FusedGCNLayerAggregatedInput.apply(ax, conv.lin.weight, conv.bias, float(self.dropout_p), bool(self.training),
-                                                               seed, mask, nxt, cfg)
-                else:
-                    x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask, link_in=link,
-                                                 link_out=nxt)
-                link = nxt
-            elif _one_head_gat(conv) and x.is_cuda:
-                mask = self._mask(i)
-                is_tail = i + 1 == (self.num_layers if last is None else last)
-                x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask,
-                                             link_out=tail_link if is_tail else None)
-                link = None
-            elif isinstance(conv, fnn.GATConv) and x.is_cuda:   # heads > 1: conv -> elu -> dropout unfused, no link (the mask honoured)
-                x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=self._mask(i))
-                link = None
-            else:
-                x = conv(x, edge_index)
-                x = F.elu(x)
-                x = F.dropout(x, p=self.dropout_p, training=self.training)
-                link = None
-        return (x, link) if return_link else x
+        layer that produced x (consecutive fused GCN layers are linked: see ops.EpilogueLink; the stack is strictly sequential)."""
+        return self._hidden(self._plan(x, head=False), x, edge_index, first=first, last=last, link=link)[0]
 
     def embed_pooled_rows(self, x, edge_index, rows):
         """embed() for a consumer that reads only `rows` of the result (the *_graph_gs models' pool over x[mask], network.py:129-131,
         :200-202): the last GCN layer aggregate-first on those rows, output compact [len(rows), hidden] (ops.FusedGCNLayerRows).
         None where that does not apply (the caller then embeds every row)."""
-        L, cfg = self.num_layers, self.op_config
-        last = self.conv[L - 1] if L > 0 else None
-        if not (cfg.pooled_rows_last_layer and x.is_cuda and isinstance(last, fnn.GCNConv) and rows.dtype == torch.int64 and rows.numel() > 0
-                and last.lin.weight.shape[0] % 4 == 0 and all(isinstance(c, (fnn.GCNConv, fnn.GATConv)) for c in self.conv)):
+        plan = self._plan(x, pooled_rows=rows, head=False)
+        if plan.tail != _GCN_POOLED_ROWS:
             return None
-        if L > 1:
-            h, link = self.embed(x, edge_index, last=L - 1, return_link=True)
-        else:
-            h, link = x.float(), None
-        if h.shape[1] % 4 != 0 and link is not None:
-            link = None
-        mask = self._mask(L - 1)
-        g = last.graph(edge_index, h.shape[0])
-        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
-        return ops.FusedGCNLayerRows.apply(h, last.lin.weight, last.bias, g, float(self.dropout_p), bool(self.training), seed, mask, rows, cfg,
-                                           link)
+        h, link = self._hidden(plan, x, edge_index)
+        top = self.conv[self.num_layers - 1]
+        g = top.graph(edge_index, h.shape[0])
+        return ops.FusedGCNLayerRows.apply(h, top.lin.weight, top.bias, g, *self._dropout(self.num_layers - 1), rows, self.op_config, link)
 
     def embed_and_head(self, x, edge_index, x_index=None, out_rows=None, loss_rows=None, compact_logits=False, forward_rows_only=False):
         """embed() followed by lt1; on the GPU the last GCN layer and the head form one autograd node.
@@ -181,110 +244,38 @@ class _Base(nn.Module):
         forward_rows_only (with loss_rows, sorted ascending): the last layer's forward aggregation runs on the loss rows alone
         (A_hat[rows, :] h: the rows nobody reads are not computed at all -- the pruned step); ignored where the aggregate-first
         last layer does not apply."""
-        L = self.num_layers
-        if out_rows is not None:
-            return self._embed_and_head_rows(x, edge_index, x_index, out_rows)
-        first = 0
-        last = self.conv[L - 1] if L > 0 else None
-        fused_tail = (L > 0 and x.is_cuda and isinstance(last, fnn.GCNConv) and
-                      ops.head_fusable(self.lt1.in_features, self.lt1.out_features))
-        # the conv stack is strictly sequential (network.py:29-33): consecutive fused GCN layers share an EpilogueLink, so
-        # that the backward GEMM dH @ W of layer i+1 applies layer i's ELU'/dropout' in its epilogue
-        link = ops.EpilogueLink() if (L > 1 and x.is_cuda and isinstance(self.conv[1], fnn.GCNConv)) else None
-        # an attention layer right below an aggregate-first attention layer hands its ELU' / dropout' to that layer's adjoint aggregation
-        glink = None
-        if (not fused_tail and L > 1 and x.is_cuda and _one_head_gat(last) and _one_head_gat(self.conv[L - 2])
-                and loss_rows is not None and self.op_config.last_layer_on_loss_rows and loss_rows.numel() > 0):
-            glink = ops.EpilogueLink()
-        if x_index is not None:
-            h = self._first_layer_dedup(x, edge_index, x_index, link_out=link, gat_link=glink if L == 2 else None) if L > 1 else None
-            if h is None:
-                x = x.index_select(0, x_index.index.long())  # materialise the union rows
-                link = None
+        plan = self._plan(x, x_index, out_rows=out_rows, loss_rows=loss_rows)
+        x, link = self._hidden(plan, x, edge_index, x_index)
+        if plan.tail == _HEAD:
+            return self.head(x)
+        L, cfg, lt1 = self.num_layers, self.op_config, self.lt1
+        top = self.conv[L - 1]
+        if plan.tail == _GCN_OUT_ROWS:
+            agg = ops.SpMMRows.apply(x, out_rows, cfg)                   # [m, H_in]
+            z = ops.Linear.apply(agg, top.lin.weight, cfg)
+            if top.bias is not None:
+                z = z + top.bias
+            mask = self._mask(L - 1)
+            z = F.elu(z)
+            if mask is not None and self.training:
+                z = z * mask.index_select(0, out_rows.rows).to(z.dtype) / (1.0 - self.dropout_p)
             else:
-                x, first = h, 1
-        else:
-            link = None
-        if not fused_tail:
-            cfg = self.op_config
-            if (L > 0 and x.is_cuda and _one_head_gat(last) and loss_rows is not None and cfg.last_layer_on_loss_rows
-                    and loss_rows.numel() > 0 and last.lin.weight.shape[0] % 4 == 0 and last.lin.weight.shape[1] % 4 == 0
-                    and ops.head_rows_supported(x.new_empty((1, last.lin.weight.shape[0])), self.lt1.weight)
-                    and ops.head_fusable(self.lt1.in_features, self.lt1.out_features)
-                    and (first == L - 1 or isinstance(self.conv[L - 2], (fnn.GATConv, fnn.GCNConv)))):
-                # the last attention layer aggregate-first: its dense part on the loss rows only (ops.FusedGATLastLayerRows)
-                x = self.embed(x, edge_index, first=first, link=link, last=L - 1, tail_link=glink)
-                mask = self._mask(L - 1)
-                g = fnn.csr_for(edge_index, x.shape[0], "gat")
-                seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
-                used = glink if (glink is not None and glink.epi != 0) else None   # (recorded by the layer below: it is an attention layer with act)
-                return ops.FusedGATLastLayerRows.apply(x, last.lin.weight, last.att_src.view(-1), last.att_dst.view(-1), last.bias,
-                                                       self.lt1.weight, self.lt1.bias, g, last.negative_slope, float(self.dropout_p),
-                                                       bool(self.training), seed, mask, loss_rows, cfg, bool(compact_logits), used)
-            return self.head(self.embed(x, edge_index, first=first, link=link))
-        x = x.float()
-        for i in range(first, L - 1):
-            conv = self.conv[i]
-            if isinstance(conv, fnn.GCNConv):
-                mask = self._mask(i)
-                nxt = ops.EpilogueLink()
-                x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask, link_in=link,
-                                             link_out=nxt)
-                link = nxt
-            else:
-                x = F.dropout(F.elu(conv(x, edge_index)), p=self.dropout_p, training=self.training)
-                link = None
-        mask = self._mask(L - 1)
-        g = last.graph(edge_index, x.shape[0])
-        cfg = self.op_config
-        seed = ops.dropout_seed(cfg, self.training, self.dropout_p, mask)
-        if (loss_rows is not None and cfg.last_layer_on_loss_rows and loss_rows.numel() > 0 and x.shape[1] % 4 == 0
-                and last.lin.weight.shape[0] % 4 == 0 and ops.head_rows_supported(x.new_empty((1, last.lin.weight.shape[0])), self.lt1.weight)):
+                z = F.dropout(z, p=self.dropout_p, training=self.training)
+            return self.head(z)
+        drop = self._dropout(L - 1)   # (the tail's draw comes last)
+        if plan.tail == _GAT_LOSS_ROWS:
+            # the last attention layer aggregate-first: its dense part on the loss rows only
+            g = fnn.csr_for(edge_index, x.shape[0], "gat")
+            return ops.FusedGATLastLayerRows.apply(x, top.lin.weight, top.att_src.view(-1), top.att_dst.view(-1), top.bias, lt1.weight, lt1.bias,
+                                                   g, top.negative_slope, *drop, loss_rows, cfg, bool(compact_logits), link)
+        g = top.graph(edge_index, x.shape[0])
+        if plan.tail == _GCN_LOSS_ROWS:
             # aggregate first, then the dense part on the loss rows only; the previous layer's epilogue backward rides on the
-            # backward SpMM's store (link)
-            fwd_sub = None
-            if forward_rows_only:   # A_hat[rows, :] and its tiles, built once per (graph, loss rows)
-                cache = getattr(g, "_rows_fwd", None)
-                if not ops._same_index(cache, loss_rows):
-                    from .csr import RowSubset
-                    cache = (loss_rows, loss_rows._version, RowSubset(g, loss_rows))
-                    g._rows_fwd = cache
-                fwd_sub = cache[2]
-            return ops.FusedGCNLastLayerRows.apply(x, last.lin.weight, last.bias, self.lt1.weight, self.lt1.bias, g,
-                                                   float(self.dropout_p), bool(self.training), seed, mask, loss_rows, cfg, link,
+            # backward SpMM's store (link).  forward_rows_only: A_hat[rows, :] and its tiles, built once per (graph, loss rows)
+            fwd_sub = ops.rows_forward_subset(g, loss_rows) if forward_rows_only else None
+            return ops.FusedGCNLastLayerRows.apply(x, top.lin.weight, top.bias, lt1.weight, lt1.bias, g, *drop, loss_rows, cfg, link,
                                                    bool(compact_logits), fwd_sub)
-        return ops.FusedGCNLayerHead.apply(x, last.lin.weight, last.bias, self.lt1.weight, self.lt1.bias, g,
-                                           float(self.dropout_p), bool(self.training), seed, mask, link, cfg, loss_rows)
-
-    def _embed_and_head_rows(self, x, edge_index, x_index, sub):
-        L = self.num_layers
-        last = self.conv[L - 1]
-        if not (L > 0 and isinstance(last, fnn.GCNConv)):
-            raise NotImplementedError("out_rows needs a GCNConv last layer")
-        first = 0
-        if x_index is not None:
-            h = self._first_layer_dedup(x, edge_index, x_index) if L > 1 else None
-            if h is None:
-                x = x.index_select(0, x_index.index.long())
-            else:
-                x, first = h, 1
-        x = x.float()
-        for i in range(first, L - 1):
-            conv = self.conv[i]
-            mask = self._mask(i)
-            x = conv.forward_elu_dropout(x, edge_index, p=self.dropout_p, training=self.training, mask=mask) \
-                if isinstance(conv, fnn.GCNConv) else F.dropout(F.elu(conv(x, edge_index)), p=self.dropout_p, training=self.training)
-        agg = ops.SpMMRows.apply(x, sub, self.op_config)                   # [m, H_in]
-        z = ops.Linear.apply(agg, last.lin.weight, self.op_config)
-        if last.bias is not None:
-            z = z + last.bias
-        mask = self._mask(L - 1)
-        z = F.elu(z)
-        if mask is not None and self.training:
-            z = z * mask.index_select(0, sub.rows).to(z.dtype) / (1.0 - self.dropout_p)
-        else:
-            z = F.dropout(z, p=self.dropout_p, training=self.training)
-        return self.head(z)
+        return ops.FusedGCNLayerHead.apply(x, top.lin.weight, top.bias, lt1.weight, lt1.bias, g, *drop, link, cfg, loss_rows)
 
     def head(self, x):
         """lt1 (network.py:34): same parameters as nn.Linear, evaluated as mm + broadcast add."""

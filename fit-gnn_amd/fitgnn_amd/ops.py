@@ -1073,7 +1073,7 @@ def epilogue_fwd_rows_(z, rows, bias, epilogue, p=0.0, seed=0, mask=None):
     return z
 
 
-def _compact_positions(g, rows):
+def compact_positions(g, rows):
     """int32 [g.n]: position of row r in `rows`, len(rows) + r % ZERO_ROWS for the others (a zero row of a compact operand); cached on the graph
     per index tensor (a trainer passes the same loss_rows every step)."""
     cache = getattr(g, "_compact_pos", None)
@@ -1082,6 +1082,20 @@ def _compact_positions(g, rows):
         pos[rows.long()] = torch.arange(rows.numel(), dtype=torch.int32, device=rows.device)
         cache = (rows, rows._version, pos)
         g._compact_pos = cache
+    return cache[2]
+
+
+_compact_positions = compact_positions   # (the name this module and its tests grew up with)
+
+
+def rows_forward_subset(g, rows):
+    """csr.RowSubset(g, rows) -- A_hat[rows, :] and its tiles, FusedGCNLastLayerRows' fwd_sub --, cached on the graph per index tensor
+    like compact_positions."""
+    cache = getattr(g, "_rows_fwd", None)
+    if not _same_index(cache, rows):
+        from .csr import RowSubset
+        cache = (rows, rows._version, RowSubset(g, rows))
+        g._rows_fwd = cache
     return cache[2]
 
 

@@ -299,8 +299,8 @@ class GDTrainer:
                 # the aggregate-first last layer with its forward aggregation on the loss rows alone (ops.FusedGCNLastLayerRows,
                 # fwd_sub): everything else of the step -- compact backward, two-hop pass -- is the full step's
                 self.prune_forward = True
-                self.sub = RowSubset(batch.graph, batch.train_idx)   # (also the trainer's record of what is aggregated: bench.py counts its entries)
-                batch.graph._rows_fwd = (batch.train_idx, batch.train_idx._version, self.sub)   # what embed_and_head looks up
+                # (what embed_and_head looks up; also the trainer's record of what is aggregated: bench.py counts its entries)
+                self.sub = _ops.rows_forward_subset(batch.graph, batch.train_idx)
             elif isinstance(last, _fnn.GCNConv):
                 core_rows = torch.nonzero(batch.core).flatten()
                 self.sub = RowSubset(batch.graph, core_rows)

@@ -22,3 +22,23 @@ def star_blocks(sizes, centres, seed, extra=0.02):
             dst += (off + b[k]).tolist() + (off + a[k]).tolist()
         off += s
     return torch.tensor(np.unique(np.array([src, dst]), axis=1), dtype=torch.long), off
+
+
+def subgraph_batches(seed=0):
+    """A small Gs: 40 clusters over a 400-node graph with extra nodes, as loader batches of 8 subgraphs."""
+    from fitgnn_amd import data as fdata
+
+    ei = fdata.synthetic_graph(400, 900, seed=seed)
+    rng = np.random.default_rng(seed)
+    assign = rng.integers(0, 40, size=400); assign[:40] = np.arange(40)
+    sub = fdata.assemble_subgraphs(ei, 400, assign, 40, extra_node=True)
+    X = torch.from_numpy(rng.standard_normal((400, 24)).astype(np.float32))
+    y = torch.from_numpy(rng.integers(0, 4, size=400))
+    tm = torch.from_numpy(rng.random(400) < 0.3)
+    batch = fdata.SubgraphBatch(sub, X, y, tm, device="cuda")
+    cpu = []
+    for r0, r1 in batch.slice_batches(8):
+        e = batch.edge_index.cpu()
+        k = (e[0] >= r0) & (e[0] < r1)
+        cpu.append(dict(x=batch.x[r0:r1].cpu(), edge_index=e[:, k] - r0, y=batch.y[r0:r1].cpu(), train_mask=batch.train_mask[r0:r1].cpu()))
+    return batch, cpu
